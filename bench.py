@@ -78,13 +78,16 @@ def parse():
                          "distribution (aircraft reach the ground within seconds: the contact-solve regime)")
     ap.add_argument("--flight-mode", type=int, default=0, help="QuadX flight mode -1..7 (auxiliary figures; the metric is quoted on mode 0)")
     ap.add_argument("--rollout-steps", type=int, default=100, help="env steps per pf_rollout launch of the second, state-resident figure (0 = skip)")
-    ap.add_argument("--min-timed-ms", type=float, default=25.0,
-                    help="floor on the timed region: the K steps are repeated (whole multiples of K, back to back, no host synchronisation in "
-                         "between) until the region lasts at least this long, and every figure stays per step. K = 20 steps of 11 us are "
+    ap.add_argument("--min-timed-ms", type=float, default=0.0,
+                    help="opt-in floor on the timed region: the K steps are repeated (whole multiples of K, back to back, no host synchronisation "
+                         "in between) until the region lasts at least this long, and every figure stays per step. K = 20 steps of 11 us are "
                          "0.2 ms: on one GPU that measures the launch and completion latency of the run as much as the kernels, and on eight "
-                         "the max over ranks of such a region measures launch skew. 0 = time exactly K steps. (25 ms since round 6: at 5 ms the one "
-                         "launch-to-first-kernel latency of the region, ~0.2 ms, was still 3 % of it -- 9.59 us per step by the wall clock against "
-                         "9.27 by the events on the same run)")
+                         "the max over ranks of such a region measures launch skew. 0 (the default) = time exactly K steps: --steps is the "
+                         "number of timed steps, and a caller that wants a longer region asks for more steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write what the timed path's last env step returned (obs, reward, terminated, truncated of "
+                         "this rank's lanes) as DIR/<name>.npy in float32, at most 64 MB in all: a larger batch is cut to a fixed, seeded "
+                         "sample of lanes, whose indices go to DIR/lanes.npy. Same arguments, same inputs: two builds compare output for output")
     ap.add_argument("--no-configs", action="store_true",
                     help="skip the secondary BASELINE configs (Hover 4 096, QuadX-Waypoints 65 536, Fixedwing-Waypoints 65 536) that the "
                          "default single-GPU hover run times after the headline and reports under `configs`")
@@ -485,6 +488,30 @@ def facade_block(device, args, ms_per_step):
     return res
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, eng, rank, world):
+    """--dump-outputs: the buffers the last timed env step wrote (what env_step returns to its caller), copied to the host as float32
+    .npy files. Every rank writes its own shard (rank r > 0 prefixes its files with `rank<r>_`); the ranks share the 64 MB budget, and
+    a shard over its share is cut to a sample of lanes drawn with a fixed seed (the same lanes on every run)."""
+    import numpy as np
+
+    arrays = {"obs": eng.obs, "reward": eng.reward, "terminated": eng.terminated, "truncated": eng.truncated}
+    arrays = {k: v.detach().to("cpu").numpy().astype(np.float32) for k, v in arrays.items()}
+    n = arrays["obs"].shape[0]
+    lane_bytes = sum(a[0].nbytes for a in arrays.values())
+    keep = (DUMP_BUDGET_BYTES // world) // (lane_bytes + 8)  # (+ 8: the float64 lane index of a sampled lane)
+    if n > keep:
+        lanes = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        arrays = {k: a[lanes] for k, a in arrays.items()}
+        arrays["lanes"] = lanes.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    prefix = f"rank{rank}_" if rank > 0 else ""
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{prefix}{k}.npy"), np.ascontiguousarray(a))
+
+
 def main():
     args = parse()
     import torch
@@ -649,6 +676,8 @@ def main():
         per_rank = [[float(x[0]), float(x[1])] for x in gathered]
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     wall_max, ev_max = float(t[0]), float(t[1])
+    if args.dump_outputs:  # (before the rollout figure below, which steps the same engine on)
+        dump_outputs(args.dump_outputs, eng, rank, world)
 
     # sanity: the simulation actually advanced and stayed finite
     ints = eng.ints()

@@ -33,7 +33,7 @@ from PyFlyt.gym_envs.quadx_envs.quadx_hover_env import QuadXHoverEnv  # noqa: E4
 from PyFlyt.gym_envs.quadx_envs.quadx_waypoints_env import QuadXWaypointsEnv  # noqa: E402
 
 
-OUT_DIR = HERE  # (--out DIR: write somewhere else -- tests/test_golden_regen.py regenerates into a scratch directory and compares)
+OUT_DIR = HERE  # (--out DIR: write somewhere else -- regenerate into a scratch directory and compare with the committed files byte for byte)
 
 
 def save(name, **arrays):

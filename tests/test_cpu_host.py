@@ -215,3 +215,33 @@ def test_bench_gpus_n_never_runs_as_one_process():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4"], capture_output=True, text=True, timeout=300,
                        env=dict(env, WORLD_SIZE="2", RANK="0", LOCAL_RANK="0"), cwd=ROOT)
     assert r.returncode != 0 and "WORLD_SIZE=2" in r.stderr
+
+
+def test_bench_dump_outputs_budget_and_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs writes the last step's buffers as float32 .npy; a batch over the 64 MB budget is cut to a sample of
+    lanes drawn with a fixed seed (the same lanes every time, their indices in lanes.npy), and the ranks share the budget."""
+    import types
+
+    import torch
+
+    import bench
+
+    n, d = 4096, 21
+    eng = types.SimpleNamespace(obs=torch.arange(n * d, dtype=torch.float32).view(n, d), reward=torch.arange(n, dtype=torch.float32),
+                                terminated=torch.arange(n) % 3 == 0, truncated=torch.arange(n) % 5 == 0)
+    bench.dump_outputs(str(tmp_path / "whole"), eng, rank=0, world=1)
+    got = {f[:-4]: np.load(tmp_path / "whole" / f) for f in os.listdir(tmp_path / "whole")}
+    assert sorted(got) == ["obs", "reward", "terminated", "truncated"]
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert np.array_equal(got["obs"], eng.obs.numpy()) and np.array_equal(got["terminated"], eng.terminated.numpy().astype(np.float32))
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 64 * 1024)
+    for out in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / out), eng, rank=1, world=2)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["rank1_lanes.npy", "rank1_obs.npy", "rank1_reward.npy", "rank1_terminated.npy", "rank1_truncated.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 32 * 1024 + 5 * 128  # (+ the .npy headers)
+    lanes = np.load(tmp_path / "a" / "rank1_lanes.npy").astype(np.int64)
+    assert np.array_equal(lanes, np.load(tmp_path / "b" / "rank1_lanes.npy")) and np.all(np.diff(lanes) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "rank1_obs.npy"), eng.obs.numpy()[lanes])
+    assert np.array_equal(np.load(tmp_path / "a" / "rank1_reward.npy"), eng.reward.numpy()[lanes])
