@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PF_ABI_VERSION 8
+#define PF_ABI_VERSION 9
 #define PF_MAX_TARGETS 8
 #define PF_MAX_BOXES 12
 #define PF_MAX_SURF 5
@@ -192,7 +192,10 @@ typedef struct pf_params {
    * ma_quadx_base_env.py:206-241). 0 / 1 = every lane alone in its world. A > 1: lanes [w A, (w+1) A) are one world -- a hit
    * between two of its drones enters both contact arrays and ends both episodes (ma_quadx_hover_env.py:181), and a contact
    * point anywhere in the world switches off every drone's rotational drag (quadx.py:509); the drones push each other (the
-   * pair stage above; box colliders). A must divide 64 and the lane count, and be at most 8. */
+   * pair stage above; box colliders). A must divide 64 and the lane count, and be at most 8.
+   * PF_TASK_NONE (the Aviary-level calls; QuadX or Fixedwing with plain box colliders): A in {1, 2, 4, 8} -- consecutive groups of A
+   * drones are one world, the reference's N-drone Aviary (core/aviary.py:69-216) is A = N; pf_aviary_step launches the shared-world
+   * step (drone-drone contacts reported in pf_buffers.out_contact_peers), pf_aviary_tick (the wind-field protocol) is unsupported. */
   int32_t agents_per_world;
   /* PF_TASK_DOGFIGHT (ma_fixedwing_dogfight_env.py:42-60): two teams of df_team_size aircraft in one shared world,
    * agents_per_world = 2 df_team_size <= 8 adjacent lanes, lanes [0, team) of a world one team, the rest the other.
@@ -278,6 +281,10 @@ typedef struct pf_buffers {
   float* actions_out;
   /* pf_body_tick only: [n][6] body-frame force (3) and torque (3) applied at the base link for every tick */
   const float* wrench;
+  /* ABI 9: pf_aviary_step on a context with agents_per_world = K > 1 (shared worlds, PF_TASK_NONE): [n] bytes, bit j = this drone
+   * touched drone j of its world (local index 0..K-1) in some physics tick of the last Aviary step -- the drone rows of the
+   * reference's contact_array (core/aviary.py:523-525); out_contact keeps its meaning (the floor). NULL = not reported. */
+  uint8_t* out_contact_peers;
 } pf_buffers;
 
 typedef struct pf_ctx pf_ctx;
@@ -319,6 +326,9 @@ int pf_aviary_reset(pf_ctx* ctx, const pf_buffers* b, void* stream);
 /* setpoints_out: [n][4] (or [n][6] for fixedwing mode -1), read-modify-written with the mode's default
  * setpoint (quadx.py:275-290) */
 int pf_aviary_set_mode(pf_ctx* ctx, const pf_buffers* b, int mode, float* setpoints_out, void* stream);
+/* agents_per_world = K > 1: the K drones of a world exchange poses before every physics tick, collide with each other (pair
+ * contacts with impulses when contact_response is on) and share the world-wide rotational-drag gate (quadx.py:509); b->out_contact
+ * is the floor, b->out_contact_peers the drone-drone part of the last Aviary step's contacts. */
 int pf_aviary_step(pf_ctx* ctx, const pf_buffers* b, int n_steps, void* stream);
 
 /* ONE physics tick of Aviary.step (aviary.py:510-531), for callers that must get between the ticks:
@@ -330,6 +340,7 @@ int pf_aviary_step(pf_ctx* ctx, const pf_buffers* b, int n_steps, void* stream);
  * subtracted from the link velocities; b->out_link_pos receives where to sample the field next;
  * b->out_contact the contact verdict of this tick. PF_NOISE_INJECT: b->xi holds this tick's draws [n].
  * The host side of the protocol is pyflyt_amd/core/aviary.py (Aviary.step with a wind field). */
+/* PF_ERR_UNSUPPORTED on a context with agents_per_world > 1 (a per-tick wind field in a shared world is not implemented). */
 int pf_aviary_tick(pf_ctx* ctx, const pf_buffers* b, int tick_index, void* stream);
 int pf_wind_links(const pf_ctx* ctx);
 

@@ -104,6 +104,10 @@ def lib():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950). pyflyt_amd has no CPU fallback."
         )
+    # torch for ROCm ships a HIP runtime of its own: loaded first, it is the one the library binds to. Loaded after the library's
+    # (the system's), the process holds two runtimes, and the one initialised second finds no device (`__graft_entry__.py smoke`).
+    import torch  # noqa: F401
+
     L = C.CDLL(LIB_PATH)
     for name in EXPORTS:
         if not hasattr(L, name):

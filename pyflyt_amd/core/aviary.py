@@ -1,5 +1,8 @@
-"""Batched `Aviary`: the reference's simulation orchestrator (core/aviary.py:47-531) for N drones
-that each live in their OWN world (independent lanes), stepped by the HIP kernels.
+"""Batched `Aviary`: the reference's simulation orchestrator (core/aviary.py:47-531) for N drones,
+stepped by the HIP kernels. By default every drone lives in its OWN world (independent lanes);
+`drones_per_world=K` puts consecutive groups of K drones in one shared world, where they hit each
+other and share the rotational-drag gate (quadx.py:509) -- the reference's N-drone Aviary is K = N,
+B copies of it are start_pos of shape [B*K, 3].
 
 Same surface as the reference where it is on the hot path:
   Aviary(start_pos[N,3], start_orn[N,3], drone_type, drone_options=..., physics_hz=240,
@@ -12,15 +15,18 @@ Same surface as the reference where it is on the hot path:
   set_mode(int) / set_setpoint(i, sp) / set_all_setpoints(sp) :440-478
   step()                                                      :480-531
   state(i) (4,3) / aux_state(i) / all_states / all_aux_states :335-421
-  contact_array  -> per-drone bool "touches the floor" (the reference's body-pair matrix collapses
-                    to this because every drone is alone in its world)
+  contact_array  -> K = 1: per-drone bool "touches the floor" (the reference's body-pair matrix
+                    collapses to this because every drone is alone in its world); K > 1: the body-pair
+                    matrix of each world, [K+1, K+1] (one world) or [W, K+1, K+1], index 0 the plane
+                    (aviary.py:322,505-525)
   wind_type / wind_options / register_wind_field_function()   :266-285,324-333 -- the field is a
                     function of (time, positions[M,3] device tensor) -> wind[M,3] device tensor,
                     sampled after every physics tick exactly where and when the reference samples
                     it (boring_bodies.py:93-96, lifting_surfaces.py:88-93)
 Several drone types in one Aviary are composed from one engine per type (core/mixed.py).
 Custom controllers (register_controller) run batch-wide on device tensors.
-Not carried over (out of scope): rendering/cameras, drone-drone contact.
+Not carried over (out of scope): rendering/cameras.
+Shared worlds (K > 1) take QuadX or Fixedwing airframes with plain box colliders and no wind field.
 """
 from __future__ import annotations
 
@@ -68,7 +74,8 @@ class Aviary:
 
     def __init__(self, start_pos, start_orn, drone_type: str | Sequence[str] = "quadx", drone_options: dict | None = None,
                  wind_type=None, wind_options=None, render: bool = False, physics_hz: int = 240, world_scale: float = 1.0,
-                 seed: None | int = None, device="cuda:0", motor_noise: bool = True, lane_offset: int = 0):
+                 seed: None | int = None, device="cuda:0", motor_noise: bool = True, lane_offset: int = 0,
+                 drones_per_world: int = 1):
         start_pos = np.asarray(start_pos, dtype=np.float64)
         start_orn = np.asarray(start_orn, dtype=np.float64)
         if len(start_pos.shape) != 2 or start_pos.shape[-1] != 3:  # core/aviary.py:125-128
@@ -87,6 +94,17 @@ class Aviary:
             if isinstance(wind_type, str):
                 raise AssertionError(f"Unknown wind field model {wind_type}.")
             raise LookupError("Invalid setting for wind field.")
+        # shared worlds: consecutive groups of K drones in one world (the kernels put a world in adjacent lanes of one wave)
+        K = int(drones_per_world)
+        if K not in (1, 2, 4, 8):
+            raise AviaryInitException(f"drones_per_world must be 1, 2, 4 or 8 (a world never straddles a wavefront, at most 8 drones share one), got {drones_per_world}")
+        if start_pos.shape[0] % K != 0:
+            raise AviaryInitException(f"drones_per_world ({K}) must divide the number of drones ({start_pos.shape[0]})")
+        if K > 1 and drone_type == "rocket":
+            raise AviaryInitException("shared worlds (drones_per_world > 1) are available for quadx and fixedwing drones, not the rocket")
+        if K > 1 and wind_type is not None:
+            raise AviaryInitException("a wind field runs per physics tick on the single-drone-world path: not available with drones_per_world > 1")
+        self.drones_per_world = K
         self.wind_type, self.wind_options = wind_type, dict(wind_options or {})
         self._registered_controllers: dict[int, Any] = {}
         self._registered_base_modes: dict[int, int] = {}
@@ -136,7 +154,10 @@ class Aviary:
         vopts.update(opts)
         P = build_params(drone_type, "none", noise="philox" if motor_noise else "off", autoreset="off",
                          seed=0 if seed is None else int(seed), vehicle_options=vopts,
-                         world_options={"physics_hz": self.physics_hz, "world_scale": float(world_scale)})
+                         world_options={"physics_hz": self.physics_hz, "world_scale": float(world_scale)}, agents_per_world=K)
+        if K > 1 and any(P.boxes[k].kind != 0 or P.boxes[k].yaw != 0.0 for k in range(P.n_boxes)):
+            raise AviaryInitException(f"shared worlds test plain, unyawed box colliders against each other; drone_model "
+                                      f"{vopts.get('drone_model', 'default')!r} has cylinders or yawed boxes (use drones_per_world=1)")
         self._seed = 0 if seed is None else int(seed)
         self.engine = BatchEngine(P, self.num_drones, device=self.device, lane_offset=lane_offset)
         if per_drone_hz is not None:
@@ -190,6 +211,8 @@ class Aviary:
         reference, a field registered after construction first acts on the tick after the next
         update_state: the velocities left by reset() are wind-free."""
         assert callable(wind_field), "`wind_field` function must be callable."
+        if self.drones_per_world > 1:
+            raise AviaryInitException("a wind field runs per physics tick on the single-drone-world path: not available with drones_per_world > 1")
         self._check_wind_field_validity(wind_field)
         self.wind_field = wind_field
         if self._wind is None:
@@ -342,7 +365,19 @@ class Aviary:
 
     @property
     def contact_array(self) -> torch.Tensor:
-        return self.engine.out_contact if self._contact_acc is None else self._contact_acc
+        """K = 1: [N] bool, the drone touched the floor. K > 1: the reference's body-pair matrix per world (aviary.py:505-525),
+        [K+1, K+1] for one world or [W, K+1, K+1], index 0 the plane, 1..K the world's drones; symmetric, false diagonal. Both hold
+        the OR over the physics ticks of the last Aviary step. Assembled on the device (no host synchronisation)."""
+        if self.drones_per_world == 1:
+            return self.engine.out_contact if self._contact_acc is None else self._contact_acc
+        K, W = self.drones_per_world, self.num_drones // self.drones_per_world
+        floor = self.engine.out_contact.view(W, K)
+        bits = self.engine.out_contact_peers.view(W, K, 1) >> torch.arange(K, dtype=torch.uint8, device=self.device)
+        m = torch.zeros(W, K + 1, K + 1, dtype=torch.bool, device=self.device)
+        m[:, 0, 1:] = floor
+        m[:, 1:, 0] = floor
+        m[:, 1:, 1:] = (bits & 1).bool()
+        return m[0] if W == 1 else m
 
     def disconnect(self) -> None:
         self.engine.close()

@@ -14,6 +14,8 @@ class MixedAviary:
     def __init__(self, start_pos, start_orn, drone_type: Sequence[str], drone_options=None, **kw):
         from .aviary import Aviary, AviaryInitException
 
+        if int(kw.get("drones_per_world", 1)) != 1:
+            raise AviaryInitException("drone-drone contact across drone types is not available: a MixedAviary takes drones_per_world=1 only")
         start_pos = np.asarray(start_pos, dtype=np.float64)
         start_orn = np.asarray(start_orn, dtype=np.float64)
         if len(start_pos.shape) != 2 or start_pos.shape[-1] != 3:

@@ -640,6 +640,99 @@ __global__ void __launch_bounds__(kWave) aviary_step_kernel(const pf_params P, c
   if (B.out_contact) B.out_contact[li] = contact ? 1 : 0;
 }
 
+// Aviary.step for drones that share a world (pf_params.agents_per_world = K > 1 with PF_TASK_NONE): the reference's N-drone Aviary
+// is ONE Bullet world, whose drones hit each other and whose rotational-drag gate looks at every contact point in it (quadx.py:509).
+// A world's K drones are adjacent lanes of one wave (K divides 64 and n: a world never straddles a wave, and a partial last wave
+// holds whole worlds only). Before every physics tick the lanes exchange pose and contact bit through LDS (world_exchange: the
+// drone-drone box tests, the drag gate from the previous tick's world-wide contact bit), then tick<true> runs the pair stage with
+// its impulses (contact_response) between the velocity update and the ground solve. Every lane of a world runs every tick -- a
+// disarmed drone with zero force and torque, as PyBullet still integrates it -- so that the wave-wide exchange and pair stage see
+// all of them. With no contact anywhere in a world the tick does the solo kernel's arithmetic (the pair stage's shift is +0).
+// out_contact: the floor part of the last Aviary step's contacts; out_contact_peers: bit j = touched drone j of the world.
+template <class VEH>
+__global__ void __launch_bounds__(kWave) aviary_world_step_kernel(const pf_params P, const pf_buffers B, const int n,
+                                                                  const uint64_t lane0, const int n_steps,
+                                                                  const pf_params* __restrict__ Pdev) {
+  __shared__ __attribute__((aligned(16))) float ktab[VEH::TABLE_FLOATS];
+  VEH::fill_table(ktab, Pdev, threadIdx.x);
+  __syncthreads();
+  const int tid = threadIdx.x;
+  const int lane = blockIdx.x * kWave + tid;
+  if (lane >= n) return;  // (whole worlds: the lanes that stay are every lane of their worlds)
+  const size_t li = lane, N = n;
+  const int K = P.agents_per_world;
+  __shared__ __attribute__((aligned(16))) float cws[kAviaryContactFloats];  // the contact solvers' LDS regions (floor and pair stage)
+  __shared__ float wpose[kWave * 8];                                         // each lane's pose and contact bit, once per tick
+  __shared__ float wvel[kWave * kPairVelStride];                             // ... and its new velocities for the pair stage
+  VEH V;
+  V.b.pdev = Pdev;
+  V.b.cws = (lds_fptr)cws;
+  V.b.contact_regions(P, kAviaryContactFloats);
+  V.bind(ktab);
+  V.b.wpose_ = wpose; V.b.wvel_ = wvel; V.b.wtid = tid; V.b.wA = K;
+  float nd;
+  int4 ints;
+  const int mode = B.modes ? B.modes[li] : P.flight_mode;
+  V.load(reinterpret_cast<const float4*>(B.state), N, li, mode, nd, ints);
+  V.b.rpy = euler_from_quat_fast(V.b.q);
+  uint32_t rng_ctr = (uint32_t)ints.z;
+  Noise nz;
+  nz.mode = P.noise_mode; nz.n = n; nz.lane = lane;
+  nz.k0 = (uint32_t)P.seed; nz.k1 = (uint32_t)(P.seed >> 32);
+  nz.c0 = (uint32_t)(lane0 + li); nz.nmot = (float)P.n_motors; nz.cached = -1; nz.xi = nullptr;
+  float sp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  const int spn = (P.vehicle == PF_FIXEDWING && mode == -1) ? 6 : 4;
+#pragma unroll
+  for (int k = 0; k < 8; ++k)
+    if (k < spn) sp[k] = B.setpoints[li * spn + k];
+  const int ratio = B.ctrl_ratio ? B.ctrl_ratio[li] : 0;
+  const int rr = ratio > 0 ? ratio : P.ticks_per_control;  // this drone's own control rate, or once per Aviary step
+  const bool armed = !B.armed || B.armed[li] != 0;         // aviary.py:423-438
+  // The QuadX controller reads its constants from the device copy of the parameter block: taken from the kernel argument, the
+  // compiler keeps them in registers across the tick loop, whose pair-stage call leaves half the register file to the values that
+  // live across it, and the instantiation spilled to scratch memory. The copy's flight_mode is the one of pf_ctx_create: the lane's
+  // mode is passed to control() explicitly. (Fixedwing: stateless mixing that reads flight_mode itself, and no pressure to relieve.)
+  const pf_params& Pc = std::is_same<VEH, QuadX>::value ? *Pdev : P;
+  bool floor = false;
+  uint32_t peers = 0u;
+  for (int s = 0; s < n_steps; ++s) {
+    nz.begin_event(rng_ctr, 0u, B.xi ? B.xi + (size_t)s * P.ticks_per_control * N : nullptr);
+    floor = false;  // (aviary.py:507: the contact array of the last Aviary step)
+    peers = 0u;
+    for (int t = 0; t < P.ticks_per_control; ++t) {
+      if (armed && t % rr == 0) {
+        if (t > 0) V.b.rpy = euler_from_quat_fast(V.b.q);
+        V.template control<kRuntimeMode>(Pc, sp, ratio > 0 ? ratio * P.dt : 0.0f, mode);
+      }
+      uint32_t bits;
+      world_exchange(V.b, wpose, tid, K, P.bound_radius, Pdev, false, nullptr, false, &bits);  // (shared_world.hpp)
+      v3 F{0.0f, 0.0f, 0.0f}, tau{0.0f, 0.0f, 0.0f};
+      if (armed) V.forces(P, nz.get(t), nullptr, F, tau);  // (a disarmed drone: no control, no forces -- gravity only)
+      V.b.template tick<true>(P, F, tau);                   // (every lane of the world together: the pair stage is wave-wide)
+      floor = floor || V.b.floor_now;
+      peers |= bits;
+    }
+    V.b.peer_contact = false;
+    if (armed) V.b.rpy = euler_from_quat_fast(V.b.q);
+    rng_ctr += 1;
+  }
+  int flags = (ints.y & ~PF_F_CONTACT) | (V.b.contact_now ? PF_F_CONTACT : 0);
+  V.store(reinterpret_cast<float4*>(B.state), N, li, mode, nd, int4{ints.x, flags, (int)rng_ctr, ints.w});
+  if (B.out_state && armed) {
+    float4* o = reinterpret_cast<float4*>(B.out_state + li * 12);
+    o[0] = float4{V.b.wb.x, V.b.wb.y, V.b.wb.z, V.b.rpy.x};
+    o[1] = float4{V.b.rpy.y, V.b.rpy.z, V.b.vb.x, V.b.vb.y};
+    o[2] = float4{V.b.vb.z, V.b.p.x, V.b.p.y, V.b.p.z};
+  }
+  if (B.out_aux && armed) {
+    float aux[VEH::AUX];
+    V.aux(aux);
+    for (int k = 0; k < VEH::AUX; ++k) B.out_aux[li * VEH::AUX + k] = aux[k];
+  }
+  if (B.out_contact) B.out_contact[li] = floor ? 1 : 0;
+  if (B.out_contact_peers) B.out_contact_peers[li] = (uint8_t)peers;
+}
+
 // One physics tick of Aviary.step (pf_aviary_tick): the wind-field protocol needs the host between
 // ticks. QuadX carries the motor commands of the step's control tick in state group 12.
 template <class VEH>
@@ -909,8 +1002,8 @@ int pf_ctx_create(const pf_params* params, int n_lanes, int device, uint64_t lan
     if (P.df_action_dim != 0 && P.df_action_dim != 4 && P.df_action_dim != 6) return fail(nullptr, PF_ERR_ARG, "dogfight: df_action_dim is 4 or 6");
   }
   if (P.agents_per_world > 1) {
-    if (!((P.vehicle == PF_QUADX && P.task == PF_TASK_MA_HOVER) || P.task == PF_TASK_DOGFIGHT))
-      return fail(nullptr, PF_ERR_UNSUPPORTED, "agents_per_world > 1 (a shared world) exists for the PettingZoo tasks only (QuadX hover, fixedwing dogfight)");
+    if (!((P.vehicle == PF_QUADX && P.task == PF_TASK_MA_HOVER) || P.task == PF_TASK_DOGFIGHT || (P.task == PF_TASK_NONE && P.vehicle != PF_ROCKET)))
+      return fail(nullptr, PF_ERR_UNSUPPORTED, "agents_per_world > 1 (a shared world) exists for the Aviary (QuadX, Fixedwing) and the PettingZoo tasks (QuadX hover, fixedwing dogfight)");
     if ((P.task != PF_TASK_DOGFIGHT && 64 % P.agents_per_world != 0) || n_lanes % P.agents_per_world != 0)
       return fail(nullptr, PF_ERR_ARG, "agents_per_world must divide 64 (the lanes of a world share a wavefront) and the lane count");
     // (the pair stage keeps one deepest-contact slot per agent of a world in registers: shared_world.hpp, pair_stage_dev)
@@ -1120,7 +1213,12 @@ int pf_aviary_step(pf_ctx* ctx, const pf_buffers* b, int n_steps, void* stream) 
   if (rc) return rc;
   const int grid = (ctx->n + pf::kWave - 1) / pf::kWave;
   hipStream_t s = (hipStream_t)stream;
-  if (ctx->P.vehicle == PF_QUADX)
+  if (ctx->P.agents_per_world > 1) {  // shared worlds (pf_ctx_create admitted QuadX / Fixedwing with plain boxes only)
+    if (ctx->P.vehicle == PF_QUADX)
+      hipLaunchKernelGGL(pf::aviary_world_step_kernel<pf::QuadX>, dim3(grid), dim3(pf::kWave), 0, s, ctx->P, *b, ctx->n, ctx->lane0, n_steps, ctx->P_dev);
+    else
+      hipLaunchKernelGGL(pf::aviary_world_step_kernel<pf::Fixedwing>, dim3(grid), dim3(pf::kWave), 0, s, ctx->P, *b, ctx->n, ctx->lane0, n_steps, ctx->P_dev);
+  } else if (ctx->P.vehicle == PF_QUADX)
     hipLaunchKernelGGL(pf::aviary_step_kernel<pf::QuadX>, dim3(grid), dim3(pf::kWave), 0, s, ctx->P, *b, ctx->n, ctx->lane0, n_steps, ctx->P_dev);
   else if (ctx->P.vehicle == PF_ROCKET)
     hipLaunchKernelGGL(pf::aviary_step_kernel<pf::Rocket>, dim3(grid), dim3(pf::kWave), 0, s, ctx->P, *b, ctx->n, ctx->lane0, n_steps, ctx->P_dev);
@@ -1132,6 +1230,7 @@ int pf_aviary_step(pf_ctx* ctx, const pf_buffers* b, int n_steps, void* stream) 
 int pf_aviary_tick(pf_ctx* ctx, const pf_buffers* b, int tick_index, void* stream) {
   if (!ctx || !b || !b->state || !b->setpoints) return fail(ctx, PF_ERR_ARG, "pf_aviary_tick: state and setpoints buffers are required");
   if (tick_index < 0 || tick_index >= ctx->P.ticks_per_control) return fail(ctx, PF_ERR_ARG, "pf_aviary_tick: tick_index must be in [0, ticks_per_control)");
+  if (ctx->P.agents_per_world > 1) return fail(ctx, PF_ERR_UNSUPPORTED, "pf_aviary_tick: no per-tick protocol (wind field) in shared worlds; use pf_aviary_step");
   if (ctx->P.noise_mode == PF_NOISE_INJECT && !b->xi) return fail(ctx, PF_ERR_ARG, "pf_aviary_tick: PF_NOISE_INJECT needs b->xi");
   int rc = ensure_device(ctx);
   if (rc) return rc;

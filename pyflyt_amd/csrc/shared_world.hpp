@@ -29,6 +29,36 @@ PF_DEV bool widen_to_world(const bool selected, const int tid, const int A) {
   return (m & wm) != 0ull;
 }
 
+// ONE test per pair, whichever of its two lanes evaluates it: the box of the drone with the LOWER index (a) in the frame of the
+// other's (b), b's box enlarged by the report distance (oracle: drones_overlap(i, j), i < j). With an enlargement the verdict is not
+// symmetric -- a against b + rd is another shape than b against a + rd -- and the two lanes of a pair that separates through the
+// breaking distance disagreed about the tick in which the report ends (tests/test_gpu_onestep.py).
+// o: the peer's exchanged pose slot; d: this body's position minus the peer's; me_first: this body has the lower index.
+PF_DEV bool pair_boxes_overlap(const pf_params* __restrict__ Pd, const float* o, const v3 d, const m3& Ra, const bool me_first, const bool mine) {
+  const float rd_fresh = Pd->contact_report_distance, rd_kept = Pd->contact_break_distance;
+  bool peer = false;
+  const m3 Rp = rot_from_quat(quat{o[3], o[4], o[5], o[6]});
+  m3 RA, RB;
+  v3 dab;
+  if (me_first) { RA = Ra; RB = Rp; dab = d; }
+  else { RA = Rp; RB = Ra; dab = v3{-d.x, -d.y, -d.z}; }
+  const m3 Rrel{RB.m00 * RA.m00 + RB.m10 * RA.m10 + RB.m20 * RA.m20, RB.m00 * RA.m01 + RB.m10 * RA.m11 + RB.m20 * RA.m21, RB.m00 * RA.m02 + RB.m10 * RA.m12 + RB.m20 * RA.m22,
+                RB.m01 * RA.m00 + RB.m11 * RA.m10 + RB.m21 * RA.m20, RB.m01 * RA.m01 + RB.m11 * RA.m11 + RB.m21 * RA.m21, RB.m01 * RA.m02 + RB.m11 * RA.m12 + RB.m21 * RA.m22,
+                RB.m02 * RA.m00 + RB.m12 * RA.m10 + RB.m22 * RA.m20, RB.m02 * RA.m01 + RB.m12 * RA.m11 + RB.m22 * RA.m21, RB.m02 * RA.m02 + RB.m12 * RA.m12 + RB.m22 * RA.m22};
+  const int nb = Pd->n_boxes;
+  for (int k = 0; k < nb; ++k) {
+    for (int l = 0; l < nb; ++l) {
+      const pf_box bk = Pd->boxes[k], bl = Pd->boxes[l];
+      const v3 ca = dab + mul(RA, v3{bk.c[0], bk.c[1], bk.c[2]}) - mul(RB, v3{bl.c[0], bl.c[1], bl.c[2]});
+      // (reported from the gap rd on -- up to the breaking distance when either drone holds contact points: b's box enlarged)
+      const float rd = (mine || slot_contact(o[7])) ? rd_kept : rd_fresh;
+      const float hb[3] = {bl.h[0] + rd, bl.h[1] + rd, bl.h[2] + rd};
+      peer |= box_overlaps_aabb(mulT(RB, ca), Rrel, bk.h, v3{0.f, 0.f, 0.f}, hb);
+    }
+  }
+  return peer;
+}
+
 // The drone-drone box tests of one body against its touching peers, out of line: they run only when bounding spheres touch, and
 // inlined they put the tick loops of their callers over the register budget (the shared-world instantiation of the QuadX
 // kernel spilled to scratch memory). This drone's boxes in the peer's box frames, 15 axes each (btBoxBoxDetector's verdict).
@@ -37,40 +67,30 @@ __device__ __noinline__ bool peers_overlap_dev(const pf_params* __restrict__ Pd,
   const m3 Ra = rot_from_quat(q);
   bool peer = false;
   const bool mine = slot_contact(wpose[(wbase + wlocal) * 8 + 7]);  // this body held contact points after the previous tick
-  const float rd_fresh = Pd->contact_report_distance, rd_kept = Pd->contact_break_distance;
   for (int j = 1; j < A; ++j) {
     int jj = wlocal + j;
     jj = jj >= A ? jj - A : jj;
     const float* o = wpose + (wbase + jj) * 8;
     const v3 d{px - o[0], py - o[1], pz - o[2]};
-    if (dot(d, d) <= rr2) {
-      // ONE test per pair, whichever of its two lanes evaluates it: the box of the drone with the LOWER index (a) in the frame of the
-      // other's (b), b's box enlarged by the report distance (oracle: drones_overlap(i, j), i < j). With an enlargement the verdict
-      // is not symmetric -- a against b + rd is another shape than b against a + rd -- and the two lanes of a pair that separates
-      // through the breaking distance disagreed about the tick in which the report ends (tests/test_gpu_onestep.py).
-      const bool me_first = wlocal < jj;
-      const m3 Rp = rot_from_quat(quat{o[3], o[4], o[5], o[6]});
-      m3 RA, RB;
-      v3 dab;
-      if (me_first) { RA = Ra; RB = Rp; dab = d; }
-      else { RA = Rp; RB = Ra; dab = v3{-d.x, -d.y, -d.z}; }
-      const m3 Rrel{RB.m00 * RA.m00 + RB.m10 * RA.m10 + RB.m20 * RA.m20, RB.m00 * RA.m01 + RB.m10 * RA.m11 + RB.m20 * RA.m21, RB.m00 * RA.m02 + RB.m10 * RA.m12 + RB.m20 * RA.m22,
-                    RB.m01 * RA.m00 + RB.m11 * RA.m10 + RB.m21 * RA.m20, RB.m01 * RA.m01 + RB.m11 * RA.m11 + RB.m21 * RA.m21, RB.m01 * RA.m02 + RB.m11 * RA.m12 + RB.m21 * RA.m22,
-                    RB.m02 * RA.m00 + RB.m12 * RA.m10 + RB.m22 * RA.m20, RB.m02 * RA.m01 + RB.m12 * RA.m11 + RB.m22 * RA.m21, RB.m02 * RA.m02 + RB.m12 * RA.m12 + RB.m22 * RA.m22};
-      const int nb = Pd->n_boxes;
-      for (int k = 0; k < nb; ++k) {
-        for (int l = 0; l < nb; ++l) {
-          const pf_box bk = Pd->boxes[k], bl = Pd->boxes[l];
-          const v3 ca = dab + mul(RA, v3{bk.c[0], bk.c[1], bk.c[2]}) - mul(RB, v3{bl.c[0], bl.c[1], bl.c[2]});
-          // (reported from the gap rd on -- up to the breaking distance when either drone holds contact points: b's box enlarged)
-          const float rd = (mine || slot_contact(o[7])) ? rd_kept : rd_fresh;
-          const float hb[3] = {bl.h[0] + rd, bl.h[1] + rd, bl.h[2] + rd};
-          peer |= box_overlaps_aabb(mulT(RB, ca), Rrel, bk.h, v3{0.f, 0.f, 0.f}, hb);
-        }
-      }
-    }
+    if (dot(d, d) <= rr2) peer |= pair_boxes_overlap(Pd, o, d, Ra, wlocal < jj, mine);
   }
   return peer;
+}
+// The same tests, with the verdict kept per peer: bit jj = this body touches the world's drone jj (the Aviary's contact_array rows,
+// pf_buffers.out_contact_peers).
+__device__ __noinline__ uint32_t peers_overlap_bits_dev(const pf_params* __restrict__ Pd, const float* wpose, const int wbase, const int wlocal, const int A,
+                                                        const float px, const float py, const float pz, const quat q, const float rr2) {
+  const m3 Ra = rot_from_quat(q);
+  uint32_t bits = 0u;
+  const bool mine = slot_contact(wpose[(wbase + wlocal) * 8 + 7]);
+  for (int j = 1; j < A; ++j) {
+    int jj = wlocal + j;
+    jj = jj >= A ? jj - A : jj;
+    const float* o = wpose + (wbase + jj) * 8;
+    const v3 d{px - o[0], py - o[1], pz - o[2]};
+    if (dot(d, d) <= rr2 && pair_boxes_overlap(Pd, o, d, Ra, wlocal < jj, mine)) bits |= 1u << jj;
+  }
+  return bits;
 }
 
 // ---------------------------------------------------------------- contact response between the drones of a world
@@ -288,9 +308,10 @@ __device__ __noinline__ void pair_stage_dev(const pf_params* __restrict__ Pd, co
 // at_rest: this body is not integrated any more (a wreck at rest): it still publishes its pose and reads the world's contact bit,
 // but runs no box tests of its own -- two wrecks that came down within a wingspan of each other would otherwise run 36 box
 // pairs x 15 axes in every tick for the rest of the episode (one such pair in 16 384 worlds made every launch 5x longer).
+// peer_bits (optional): receives this tick's drone-drone verdict per peer (bit = the peer's index in the world).
 template <class BODY>
 PF_DEV void world_exchange(BODY& b, float* wpose, const int tid, const int A, const float bound_radius, const pf_params* __restrict__ Pd,
-                           const bool at_rest = false, float* wvel = nullptr, const bool frozen = false) {
+                           const bool at_rest = false, float* wvel = nullptr, const bool frozen = false, uint32_t* peer_bits = nullptr) {
   const int wbase = (tid / A) * A, wlocal = tid - wbase;
   float* me = wpose + tid * 8;
   if (wvel != nullptr && at_rest) {  // (a wreck at rest sits this tick out: what the pair stage finds for it is a body standing still)
@@ -327,7 +348,14 @@ PF_DEV void world_exchange(BODY& b, float* wpose, const int tid, const int A, co
   touch = touch && (!at_rest || b.woken);
   b.world_touch = widen_to_world(near, tid, A);
   bool peer = false;
-  if (__any(touch)) {
+  if (peer_bits != nullptr) {
+    uint32_t bits = 0u;
+    if (__any(touch)) {
+      if (touch) bits = peers_overlap_bits_dev(Pd, wpose, wbase, wlocal, A, b.p.x, b.p.y, b.p.z, b.q, rr2);
+    }
+    *peer_bits = bits;
+    peer = bits != 0u;
+  } else if (__any(touch)) {
     if (touch) peer = peers_overlap_dev(Pd, wpose, wbase, wlocal, A, b.p.x, b.p.y, b.p.z, b.q, rr2);
   }
   b.world_contact = world;

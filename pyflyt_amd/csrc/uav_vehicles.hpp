@@ -567,6 +567,7 @@ struct Body {
   v3 rpy;       // quadx.py:526 (refreshed once per Aviary step)
   bool contact_now, contact_step;
   bool persisted = false;  // this tick: the body held contact points after the previous tick (they persist up to the breaking distance)
+  bool floor_now = false;  // this tick's verdict against the ground alone: contact_now without the drone-drone hits (shared-world Aviary)
   // shared world (PF_TASK_MA_HOVER with agents_per_world > 1); both false for a drone that is alone in its world
   int ccap = kContactSlotFloats;  // floats of LDS behind `cws` for the solver's contact records (at least one worst-case region)
   PF_DEV void contact_regions(const pf_params&, int floats) { ccap = floats; }
@@ -622,7 +623,8 @@ struct Body {
   template <bool SHARED = false>
   PF_DEV void tick(const pf_params& P, v3 F, v3 tau) {
     persisted = contact_now;
-    contact_now = detect_contact(P, persisted ? P.contact_break_distance : P.contact_report_distance) || peer_contact;
+    floor_now = detect_contact(P, persisted ? P.contact_break_distance : P.contact_report_distance);
+    contact_now = floor_now || peer_contact;
     v3 com{P.com[0], P.com[1], P.com[2]};
     if (P.has_com_offset) tau = tau - cross(com, F);
     v3 h = symmul(P.I_pa, wb);
@@ -909,10 +911,16 @@ struct QuadX {
   PF_DEV v3 link_pos(const pf_params&, int) const { return b.p; }  // centre-of-mass link at the base origin
   template <bool SHARED = false>
   PF_DEV void tick(const pf_params& P, float xi, const float* wind = nullptr) {
+    v3 F, tau;
+    forces(P, xi, wind, F, tau);
+    b.template tick<SHARED>(P, F, tau);
+  }
+  // update_physics alone: the motors' new state, body-frame force and torque about the base origin for this tick
+  PF_DEV void forces(const pf_params& P, float xi, const float* wind, v3& F, v3& tau) {
     v3 vd = b.vb;
     if (wind) vd = vd - mulT(b.R, v3{wind[0], wind[1], wind[2]});
-    v3 F{-P.drag_const[0] * sq_signed(vd.x), -P.drag_const[1] * sq_signed(vd.y), -P.drag_const[2] * sq_signed(vd.z)};
-    v3 tau{0.0f, 0.0f, 0.0f};
+    F = v3{-P.drag_const[0] * sq_signed(vd.x), -P.drag_const[1] * sq_signed(vd.y), -P.drag_const[2] * sq_signed(vd.z)};
+    tau = v3{0.0f, 0.0f, 0.0f};
 #pragma unroll
     for (int i = 0; i < 4; ++i) {  // motors.py:131-138,182-193
       float t = fmaf(P.motor_dt_over_tau[i], pwm[i] - thr[i], thr[i]);
@@ -930,7 +938,6 @@ struct QuadX {
       tau.y = fmaf(-P.drag_coef_pqr, sq_signed(b.wb.y), tau.y);
       tau.z = fmaf(-P.drag_coef_pqr, sq_signed(b.wb.z), tau.z);
     }
-    b.template tick<SHARED>(P, F, tau);
   }
   PF_DEV void tick_unarmed(const pf_params& P) { b.tick(P, v3{0.f, 0.f, 0.f}, v3{0.f, 0.f, 0.f}); }  // aviary.py:510-521
   // one Aviary.step (aviary.py:480-531): control on the first tick, pwm held afterwards
@@ -1112,7 +1119,14 @@ struct Fixedwing {
   }
   template <bool SHARED = false>
   PF_DEV void tick(const pf_params& P, float xi, const float* wind = nullptr) {
-    v3 F{0.0f, 0.0f, 0.0f}, tau{0.0f, 0.0f, 0.0f};
+    v3 F, tau;
+    forces(P, xi, wind, F, tau);
+    b.template tick<SHARED>(P, F, tau);
+  }
+  // update_physics alone: the surfaces' and the motor's new state, body-frame force and torque about the base origin for this tick
+  PF_DEV void forces(const pf_params& P, float xi, const float* wind, v3& F, v3& tau) {
+    F = v3{0.0f, 0.0f, 0.0f};
+    tau = v3{0.0f, 0.0f, 0.0f};
 #pragma unroll 1
     for (int i = 0; i < PF_MAX_SURF; ++i) {
       const pf_surface S = row(sk + i * TABLE_STRIDE);
@@ -1141,7 +1155,6 @@ struct Fixedwing {
       F = F + f;
       tau = tau + cross(r, f) + (k * P.motor_tmax[0]) * u;
     }
-    b.template tick<SHARED>(P, F, tau);
   }
   PF_DEV void tick_unarmed(const pf_params& P) { b.tick(P, v3{0.f, 0.f, 0.f}, v3{0.f, 0.f, 0.f}); }
   template <int MODE_T>

@@ -68,6 +68,7 @@ class BatchEngine:
         self.armed = None       # [n] bool: Aviary.set_armed, or None = all armed
         self.out_aux = None
         self.out_contact = None
+        self.out_contact_peers = None  # [n] uint8, shared worlds only: bit j = touched drone j of the world (pf_buffers.out_contact_peers)
         self._buf = L.PfBuffers()
         self._index = index
         # env_step's hot path: {id(action tensor): (the tensor, its filled pf_buffers block)} -- see env_step
@@ -117,6 +118,7 @@ class BatchEngine:
         b.final_info = _ptr(self.final_info)
         b.actions_out = _ptr(actions_out)
         b.wrench = _ptr(wrench)
+        b.out_contact_peers = _ptr(self.out_contact_peers)
         return b
 
     def _check_f32(self, t, shape, name):
@@ -285,6 +287,8 @@ class BatchEngine:
             self.out_state = torch.zeros(self.n, 12, dtype=torch.float32, device=self.device)
             self.out_aux = torch.zeros(self.n, aux, dtype=torch.float32, device=self.device)
             self.out_contact = torch.zeros(self.n, dtype=torch.bool, device=self.device)
+            if self.params.agents_per_world > 1:
+                self.out_contact_peers = torch.zeros(self.n, dtype=torch.uint8, device=self.device)
             # world positions of the links a wind field is sampled at (QuadX: body link; Fixedwing: 5 surfaces)
             self.wind_links = int(self.lib.pf_wind_links(self._ctx))
             self.link_pos = torch.zeros(self.n, self.wind_links, 3, dtype=torch.float32, device=self.device)

@@ -490,6 +490,7 @@ def build_params(
     # ---- task constants (defaults of the reference's env constructors)
     if task == "none":
         P.task = L.TASK_NONE
+        P.agents_per_world = int(agents_per_world)  # > 1: the Aviary's drones share worlds of that many (pf_aviary_step)
         d_dome, d_dur, d_hz, d_reach = math.inf, 10.0, 30, 0.2
         P.env_step_ratio = 1
     elif task == "hover":  # quadx_hover_env.py:32-37
