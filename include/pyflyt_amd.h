@@ -29,16 +29,20 @@
 extern "C" {
 #endif
 
-#define PF_ABI_VERSION 9
+#define PF_ABI_VERSION 10
 #define PF_MAX_TARGETS 8
 #define PF_MAX_BOXES 12
 #define PF_MAX_SURF 5
 #define PF_MAX_CONTACTS 48 /* contact vertices solved per body per tick (first in collider / vertex order) */
 
 enum pf_status { PF_OK = 0, PF_ERR_ARG = -1, PF_ERR_UNSUPPORTED = -2, PF_ERR_NO_DEVICE = -3 };
-enum pf_vehicle { PF_QUADX = 0, PF_FIXEDWING = 1, PF_ROCKET = 2 /* Aviary-level entry points only */ };
+enum pf_vehicle { PF_QUADX = 0, PF_FIXEDWING = 1, PF_ROCKET = 2 /* Aviary-level entry points and PF_TASK_ROCKET_LANDING */ };
 enum pf_task { PF_TASK_NONE = 0, PF_TASK_HOVER = 1, PF_TASK_WAYPOINTS = 2, PF_TASK_MA_HOVER = 3,
-               PF_TASK_DOGFIGHT = 4 /* MAFixedwingDogfightEnv (pz_envs/fixedwing_envs/ma_fixedwing_dogfight_env.py), fixedwing only */ };
+               PF_TASK_DOGFIGHT = 4 /* MAFixedwingDogfightEnv (pz_envs/fixedwing_envs/ma_fixedwing_dogfight_env.py), fixedwing only */,
+               PF_TASK_ROCKET_LANDING = 5 /* RocketLandingEnv (gym_envs/rocket_envs/rocket_landing_env.py), rocket + flight mode 0 only */ };
+/* bits of pf_params.rl_reset_options (PF_TASK_ROCKET_LANDING): the reset's `options` (rocket_base_env.py:177-214). The reference's
+ * reset(options=None) -- what gymnasium.make passes -- turns on both; options={} neither. */
+enum pf_rl_option { PF_RL_RANDOMIZE_DROP = 1, PF_RL_ACCELERATE_DROP = 2 };
 enum pf_noise { PF_NOISE_OFF = 0, PF_NOISE_INJECT = 1, PF_NOISE_PHILOX = 2 };
 enum pf_autoreset { PF_AUTORESET_OFF = 0, PF_AUTORESET_NEXT_STEP = 1, PF_AUTORESET_SAME_STEP = 2 };
 
@@ -49,7 +53,10 @@ enum pf_flag {
   /* a state word of the lane is NaN/Inf after an env step (the reference would carry the NaN on silently:
    * e.g. 0 * inf in the mixer's saturation rescale, quadx.py:490-491, when hi == pmin). Sticky until the
    * lane is reset; surfaced as infos["nonfinite"]; counted by bench.py. */
-  PF_F_NONFINITE = 64
+  PF_F_NONFINITE = 64,
+  /* PF_TASK_ROCKET_LANDING: the landing-pad contact value the observation shows (its last entry). It is set by the pad check of the
+   * previous Aviary step (rocket_landing_env.py:222-226 runs after compute_state), so it lags one Aviary step and is 0 after a reset. */
+  PF_F_PAD_CONTACT = 128
 };
 
 typedef struct pf_pid {
@@ -222,6 +229,17 @@ typedef struct pf_params {
   float df_spawn_min_radius, df_spawn_max_radius;
   float df_damage_per_hit, df_lethal_distance, df_lethal_angle, df_aggressiveness, df_cooperativeness;
   pf_rocket rocket;
+  /* ABI 10: PF_TASK_ROCKET_LANDING (gym_envs/rocket_envs/rocket_landing_env.py, rocket_base_env.py). The landing pad
+   * (models/landing_pad.urdf loaded at basePosition (0, 0, 0.1), fixed): a static upright cylinder, the second collider of the world
+   * next to the ground slab. A collider vertex touches the pad when its horizontal distance from the pad's axis is <= pad_radius and
+   * its height lies in [pad bottom, pad top + reach] (reach: the ground slab's margin / report / break distance rule); the top face,
+   * normal +z, is a contact plane of the same Gauss-Seidel solve as the slab's. The rim and the side wall are not modelled. */
+  float pad_pos[3];          /* centre (0, 0, 0.1) */
+  float pad_radius;          /* 2 */
+  float pad_half_height;     /* 0.05: the top face at z = 0.15 */
+  float ceiling;             /* z above this: out of bounds (500) */
+  float max_displacement;    /* |xy| above this: out of bounds (200) */
+  int32_t rl_reset_options;  /* pf_rl_option bits */
 } pf_params;
 
 /* Device buffers of one call. state layout: float4 groups, [n_groups][n_lanes][4]. The state belongs to the
@@ -239,7 +257,8 @@ typedef struct pf_params {
  * their float32 roundings in groups 0-5 / 7-11. A hand-written state leaves them zero (the value is then its float32 word). */
 typedef struct pf_buffers {
   float* state;            /* [pf_state_groups()][n][4] fp32/int32, persistent */
-  const float* actions;    /* [n][4]   gym action (quadx_base_env.py:269); PF_TASK_DOGFIGHT with df_action_dim 6: [n][6] */
+  const float* actions;    /* [n][4]   gym action (quadx_base_env.py:269); PF_TASK_DOGFIGHT with df_action_dim 6: [n][6];
+                            * PF_TASK_ROCKET_LANDING: [n][7] finlet x, finlet y, finlet roll, ignition, throttle, gimbal 1, gimbal 2 */
   float* obs;              /* [n][pf_obs_dim()] row-major */
   float* final_obs;        /* [n][pf_obs_dim()] or NULL; written for finished lanes under SAME_STEP */
   float* reward;           /* [n] */
@@ -247,7 +266,10 @@ typedef struct pf_buffers {
   uint8_t* truncated;      /* [n] */
   const float* xi;         /* PF_NOISE_INJECT: [env_step_ratio*ticks_per_control][n] raw motor-noise draws */
   const float* xi_reset;   /* PF_NOISE_INJECT: [settle_steps*ticks_per_control][n] */
-  const float* u_targets;  /* PF_NOISE_INJECT, waypoint tasks: [3*num_targets][n] theta|phi|dist draws (+ [num_targets][n] yaw with use_yaw_targets) */
+  const float* u_targets;  /* PF_NOISE_INJECT, waypoint tasks: [3*num_targets][n] theta|phi|dist draws (+ [num_targets][n] yaw with use_yaw_targets);
+                            * PF_TASK_ROCKET_LANDING: [6][n] the reset's spawn draws as the reference takes them (rocket_base_env.py:184-189) --
+                            * x, y (in +-0.1 max_displacement), z (in [0.8, 0.9] ceiling), roll, pitch, yaw (in +-0.3); read with
+                            * PF_RL_RANDOMIZE_DROP only */
   /* Aviary-level calls only */
   const float* setpoints;  /* [n][4] (quadx, fixedwing mode 0), [n][6] (fixedwing mode -1) or [n][7] (rocket) */
   float* out_state;        /* [n][12]: ang_vel, ang_pos, lin_vel, lin_pos rows of Aviary.state(i) */
@@ -346,7 +368,8 @@ int pf_wind_links(const pf_ctx* ctx);
 
 /* Synthetic uniform actions inside [action_low, action_high] for benchmark rollouts
  * (the role of env.action_space.sample(), tests/test_gym_envs.py:104), keyed by
- * (seed, global lane, step_index). */
+ * (seed, global lane, step_index). [n][4]; PF_TASK_ROCKET_LANDING: [n][7] in low = (-1, -1, -1, 0, 0, -1, -1), high = 1
+ * (rocket_base_env.py:95-119). */
 int pf_sample_actions(pf_ctx* ctx, float* actions, uint32_t step_index, void* stream);
 
 /* k_steps consecutive env.step() calls (quadx_base_env.py:269-301 incl. auto-reset) in ONE launch with the
@@ -357,7 +380,8 @@ int pf_sample_actions(pf_ctx* ctx, float* actions, uint32_t step_index, void* st
  * [k_steps][n], b->final_obs / final_info (SAME_STEP) [k_steps][n][..]. Actions: b->actions == NULL samples
  * step s of lane i exactly as pf_sample_actions(step_index0 + s) would (same Philox keys) and, if
  * b->actions_out != NULL, stores it there; otherwise b->actions is a given open-loop sequence
- * [k_steps][n][4]. Results are bit-identical to k_steps x (pf_sample_actions + pf_env_step).
+ * [k_steps][n][4] ([k_steps][n][7] for PF_TASK_ROCKET_LANDING, actions_out likewise). Results are bit-identical to
+ * k_steps x (pf_sample_actions + pf_env_step).
  * State-resident on every env kernel: the specialised ones (QuadX Hover / Waypoints / multi-agent Hover with level spawns in any
  * flight mode, Fixedwing-Waypoints), the dogfight on either aircraft model (ma_fixedwing_base_env.py:272-334 in a loop,
  * tests/test_pz_envs.py:71-93; sampled actions four-wide, or a given sequence of either width [k_steps][n][4 | 6]) and the generic

@@ -11,10 +11,12 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PF_LIB_PATH") or os.path.join(_HERE, "libpyflyt_amd.so")
 
 QUADX, FIXEDWING, ROCKET = 0, 1, 2
-TASK_NONE, TASK_HOVER, TASK_WAYPOINTS, TASK_MA_HOVER, TASK_DOGFIGHT = 0, 1, 2, 3, 4
+TASK_NONE, TASK_HOVER, TASK_WAYPOINTS, TASK_MA_HOVER, TASK_DOGFIGHT, TASK_ROCKET_LANDING = 0, 1, 2, 3, 4, 5
+RL_RANDOMIZE_DROP, RL_ACCELERATE_DROP = 1, 2
 NOISE_OFF, NOISE_INJECT, NOISE_PHILOX = 0, 1, 2
 AUTORESET_OFF, AUTORESET_NEXT_STEP, AUTORESET_SAME_STEP = 0, 1, 2
 F_TERMINATED, F_TRUNCATED, F_CONTACT, F_INFO_COLLISION, F_INFO_OOB, F_INFO_COMPLETE, F_NONFINITE = 1, 2, 4, 8, 16, 32, 64
+F_PAD_CONTACT = 128
 
 # --------------------------------------------------------------------------- structs from the header
 # The ctypes mirrors of pf_pid / pf_box / pf_surface / pf_rocket / pf_params / pf_buffers are GENERATED
@@ -86,6 +88,8 @@ EXPORTS = tuple(_PROTOS)  # every function the header declares
 PF_MAX_BOXES, PF_MAX_SURF, PF_MAX_TARGETS = _DEFINES["PF_MAX_BOXES"], _DEFINES["PF_MAX_SURF"], _DEFINES["PF_MAX_TARGETS"]
 assert (QUADX, FIXEDWING, ROCKET) == (_ENUMS["PF_QUADX"], _ENUMS["PF_FIXEDWING"], _ENUMS["PF_ROCKET"])
 assert (F_CONTACT, F_INFO_COMPLETE) == (_ENUMS["PF_F_CONTACT"], _ENUMS["PF_F_INFO_COMPLETE"])
+assert (TASK_ROCKET_LANDING, F_PAD_CONTACT) == (_ENUMS["PF_TASK_ROCKET_LANDING"], _ENUMS["PF_F_PAD_CONTACT"])
+assert (RL_RANDOMIZE_DROP, RL_ACCELERATE_DROP) == (_ENUMS["PF_RL_RANDOMIZE_DROP"], _ENUMS["PF_RL_ACCELERATE_DROP"])
 
 _lib = None
 

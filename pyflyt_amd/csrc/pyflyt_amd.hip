@@ -487,6 +487,11 @@ __global__ void __launch_bounds__(kWave) env_kernel(const pf_params P, const pf_
   }  // (env steps of this launch)
 }
 
+}  // namespace pf
+// Rocket-Landing: env_kernel<Rocket, PF_TASK_ROCKET_LANDING, kRuntimeMode> and the landing pad
+#include "rocket_landing.hpp"
+namespace pf {
+
 // Settled spawn state for contexts whose settle phase is lane-independent (see env_kernel).
 template <class VEH>
 __global__ void settle_template_kernel(const pf_params P, float4* tmpl, const pf_params* __restrict__ Pdev) {
@@ -969,6 +974,11 @@ static void launch_env_t(pf_ctx* ctx, const pf_buffers* b, int op, const uint8_t
   else
     hipLaunchKernelGGL((pf::env_kernel<VEH, TASK, pf::kRuntimeMode>), dim3(grid), dim3(pf::kWave), 0, s, ctx->P, *b, ctx->n, ctx->lane0, op, mask, ctx->tmpl, ctx->P_dev, roll_steps, step0);
 }
+static void launch_rocket_landing(pf_ctx* ctx, const pf_buffers* b, int op, const uint8_t* mask, hipStream_t s, int roll_steps = 0, uint32_t step0 = 0u) {
+  const int grid = (ctx->n + pf::kWave - 1) / pf::kWave;
+  hipLaunchKernelGGL((pf::env_kernel<pf::Rocket, PF_TASK_ROCKET_LANDING, pf::kRuntimeMode>), dim3(grid), dim3(pf::kWave), 0, s, ctx->P, *b, ctx->n, ctx->lane0, op, mask,
+                     (const float4*)nullptr, ctx->P_dev, roll_steps, step0);
+}
 extern "C" {
 
 int pf_abi_version(void) { return PF_ABI_VERSION; }
@@ -984,8 +994,13 @@ int pf_ctx_create(const pf_params* params, int n_lanes, int device, uint64_t lan
   if (device < 0 || device >= count) return fail(nullptr, PF_ERR_ARG, "pf_ctx_create: bad device index");
   const pf_params& P = *params;
   if (P.vehicle != PF_QUADX && P.vehicle != PF_FIXEDWING && P.vehicle != PF_ROCKET) return fail(nullptr, PF_ERR_ARG, "unknown vehicle");
-  if (P.vehicle == PF_ROCKET && P.task != PF_TASK_NONE)
-    return fail(nullptr, PF_ERR_UNSUPPORTED, "the Rocket is available through the Aviary-level entry points only (Rocket-Landing needs a resting contact)");
+  if (P.vehicle == PF_ROCKET && P.task != PF_TASK_NONE && P.task != PF_TASK_ROCKET_LANDING)
+    return fail(nullptr, PF_ERR_UNSUPPORTED, "the Rocket flies the Aviary-level entry points and the Rocket-Landing task (PF_TASK_ROCKET_LANDING) only");
+  if (P.task == PF_TASK_ROCKET_LANDING) {  // gym_envs/rocket_envs/rocket_landing_env.py
+    if (P.vehicle != PF_ROCKET) return fail(nullptr, PF_ERR_UNSUPPORTED, "the Rocket-Landing task flies the Rocket");
+    if (!(P.pad_radius > 0.0f) || !(P.pad_half_height >= 0.0f)) return fail(nullptr, PF_ERR_ARG, "Rocket-Landing: pad_radius must be > 0, pad_half_height >= 0");
+    if ((P.rl_reset_options & ~(PF_RL_RANDOMIZE_DROP | PF_RL_ACCELERATE_DROP)) != 0) return fail(nullptr, PF_ERR_ARG, "Rocket-Landing: unknown reset option bits");
+  }
   if (P.vehicle == PF_ROCKET && P.flight_mode != 0) return fail(nullptr, PF_ERR_ARG, "rocket flight_mode must be 0");
   if (P.task == PF_TASK_WAYPOINTS && (P.num_targets < 1 || P.num_targets > 4))
     return fail(nullptr, PF_ERR_UNSUPPORTED, "num_targets must be in 1..4");
@@ -1105,6 +1120,7 @@ void pf_ctx_destroy(pf_ctx* ctx) {
 }
 int pf_state_groups(const pf_ctx* ctx) {
   if (ctx->P.task == PF_TASK_DOGFIGHT) return pf::kDfGroups;
+  if (ctx->P.task == PF_TASK_ROCKET_LANDING) return pf::kRlGroups;
   // (the specialised QuadX kernel in a cascaded flight mode, no shared world: eleven more groups, the float32 remainders of its fp64
   //  rigid-body state and PID memories -- quadx_fast.hpp: QuadStateD)
   if (ctx->fast && ctx->K.mode != 0 && ctx->K.apw == 1) return pf::QuadX::GROUPS + 11;  // (16-19 state, 20-21 rate PID, 22-26 cascade)
@@ -1113,6 +1129,7 @@ int pf_state_groups(const pf_ctx* ctx) {
 int pf_obs_dim(const pf_ctx* ctx) {
   const pf_params& P = ctx->P;
   if (P.task == PF_TASK_DOGFIGHT) return 19 + (P.df_action_dim == 6 ? 6 : 4) + (P.agents_per_world - 1) * 14;  // ma_fixedwing_dogfight_env.py:128-160
+  if (P.task == PF_TASK_ROCKET_LANDING) return (P.angle_repr ? 13 : 12) + pf::kRlActionDim + pf::Rocket::AUX + 1;  // rocket_landing_env.py:141-169
   int aux = P.vehicle == PF_QUADX ? 4 : 6;
   return (P.angle_repr ? 13 : 12) + 4 + aux + (P.task == PF_TASK_WAYPOINTS ? (P.use_yaw_targets ? 4 : 3) * P.num_targets : (P.task == PF_TASK_MA_HOVER ? 3 : 0));
 }
@@ -1146,6 +1163,8 @@ static int launch_env(pf_ctx* ctx, const pf_buffers* b, int op, const uint8_t* m
     if (ctx->df_fast) { PF_DFA(pf::DfFastVeh) } else { PF_DFA(pf::DfGenericVeh) }
 #undef PF_DFA
 #undef PF_DF
+  } else if (P.task == PF_TASK_ROCKET_LANDING) {
+    launch_rocket_landing(ctx, b, op, mask, s);
   } else if (ctx->fast) {
     if (P.task == PF_TASK_HOVER) launch_fast<PF_TASK_HOVER>(ctx, b, op, mask, s);
     else if (P.task == PF_TASK_MA_HOVER) launch_fast<PF_TASK_MA_HOVER>(ctx, b, op, mask, s);
@@ -1252,7 +1271,10 @@ int pf_sample_actions(pf_ctx* ctx, float* actions, uint32_t step_index, void* st
   if (!ctx || !actions) return fail(ctx, PF_ERR_ARG, "pf_sample_actions: bad argument");
   int rc = ensure_device(ctx);
   if (rc) return rc;
-  hipLaunchKernelGGL(pf::sample_actions_kernel, dim3((ctx->n + 255) / 256), dim3(256), 0, (hipStream_t)stream, ctx->P, actions, ctx->n, ctx->lane0, step_index);
+  if (ctx->P.task == PF_TASK_ROCKET_LANDING)
+    hipLaunchKernelGGL(pf::sample_actions7_kernel, dim3((ctx->n + 255) / 256), dim3(256), 0, (hipStream_t)stream, ctx->P, actions, ctx->n, ctx->lane0, step_index);
+  else
+    hipLaunchKernelGGL(pf::sample_actions_kernel, dim3((ctx->n + 255) / 256), dim3(256), 0, (hipStream_t)stream, ctx->P, actions, ctx->n, ctx->lane0, step_index);
   PF_HIP(ctx, hipGetLastError());
   return PF_OK;
 }
@@ -1289,7 +1311,9 @@ int pf_rollout(pf_ctx* ctx, const pf_buffers* b, int k_steps, uint32_t step_inde
     int rc = ensure_device(ctx);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (P.vehicle == PF_QUADX) {
+    if (P.task == PF_TASK_ROCKET_LANDING) {
+      launch_rocket_landing(ctx, b, pf::OP_STEP, nullptr, s, k_steps, step_index0);
+    } else if (P.vehicle == PF_QUADX) {
       if (P.task == PF_TASK_HOVER) launch_env_t<pf::QuadX, PF_TASK_HOVER>(ctx, b, pf::OP_STEP, nullptr, s, k_steps, step_index0);
       else if (P.task == PF_TASK_MA_HOVER) launch_env_t<pf::QuadX, PF_TASK_MA_HOVER>(ctx, b, pf::OP_STEP, nullptr, s, k_steps, step_index0);
       else launch_env_t<pf::QuadX, PF_TASK_WAYPOINTS>(ctx, b, pf::OP_STEP, nullptr, s, k_steps, step_index0);

@@ -3,11 +3,16 @@
 // gimbal (abstractions/boosters.py:160-263, gimbals.py:151-217), per-axis body drag
 // (boring_bodies.py:113-127), on a composite rigid body whose fuel-tank mass and inertia change every
 // tick (boosters.py:193-198 -> changeDynamics), so mass, centre of mass and inertia are rebuilt per tick.
-// No env uses it on the GPU (Rocket-Landing needs a resting contact): core/aviary.py surface only.
+// The Aviary-level kernels fly it on the ground slab alone; the Rocket-Landing env (rocket_landing.hpp) adds the landing pad
+// through the PAD parameter of tick() / integrate().
 #pragma once
+#include <type_traits>
+
 #include "uav_vehicles.hpp"
 
 namespace pf {
+
+struct NoPad {};  // tick() / integrate() without a landing pad: the ground slab alone (Body::tick_var)
 
 struct Rocket {
   // g0 p, fuel_ratio | g1 q | g2 v, w.x | g3 w.yz, fin0, fin1 | g4 fin2, fin3, throttle, ignition
@@ -77,7 +82,9 @@ struct Rocket {
     return b.p + mul(b.R, v3{P.surf[k - 1].r[0], P.surf[k - 1].r[1], P.surf[k - 1].r[2]});
   }
   // update_physics (rocket.py:268-290) + stepSimulation + update_state for one tick
-  PF_DEV void tick(const pf_params& P, float xi, const float* wind = nullptr) {
+  // (PAD: the world's second static collider, rocket_landing.hpp: PadWorld -- NoPad compiles to the slab-only tick)
+  template <class PAD = NoPad>
+  PF_DEV void tick(const pf_params& P, float xi, const float* wind = nullptr, PAD* pad = nullptr) {
     const pf_rocket& K = P.rocket;
     v3 F{0.0f, 0.0f, 0.0f}, tau{0.0f, 0.0f, 0.0f};
     {  // body drag at the fuel tank link (rocket.py:88-112,271)
@@ -122,11 +129,12 @@ struct Rocket {
       F = F + f;
       tau = tau + cross(rb, f);
     }
-    integrate(P, F, tau);
+    integrate(P, F, tau, pad);
   }
   PF_DEV void tick_unarmed(const pf_params& P) { integrate(P, v3{0.f, 0.f, 0.f}, v3{0.f, 0.f, 0.f}); }
   // stepSimulation on the composite body with the current fuel mass / inertia (fuel tank at tank_r, diagonal inertia)
-  PF_DEV void integrate(const pf_params& P, v3 F, v3 tau) {
+  template <class PAD = NoPad>
+  PF_DEV void integrate(const pf_params& P, v3 F, v3 tau, PAD* pad = nullptr) {
     const pf_rocket& K = P.rocket;
     const float mf = fuel * K.total_fuel;
     const float M = K.dry_mass + mf, iM = 1.0f / M;
@@ -149,7 +157,8 @@ struct Rocket {
     const float Iinv[6] = {C00 * idet, C01 * idet, C02 * idet, C11 * idet, C12 * idet, C22 * idet};
     float H[6] = {Ipa[0], Ipa[1], Ipa[2], Ipa[3], Ipa[4], Ipa[5]};  // gyroscopic inertia: own part gated by the Bullet flag
     if (P.use_gyro_term) { H[0] += Io[0]; H[3] += Io[1]; H[5] += Io[2]; }
-    b.tick_var(P, F, tau, iM, c, H, Iinv);
+    if constexpr (std::is_same<PAD, NoPad>::value) b.tick_var(P, F, tau, iM, c, H, Iinv);
+    else pad->tick_var(b, P, F, tau, iM, c, H, Iinv);
   }
   template <int MODE_T>
   PF_DEV void aviary_step(const pf_params& P, const float sp[8], Noise& nz, int flat_base) {

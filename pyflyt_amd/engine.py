@@ -175,7 +175,10 @@ class BatchEngine:
 
     @property
     def action_dim(self):
-        """Width of the env action: 4, or 6 for the dogfight task with assisted_flight=False (pf_params.df_action_dim)."""
+        """Width of the env action: 4, 6 for the dogfight task with assisted_flight=False (pf_params.df_action_dim), 7 for
+        Rocket-Landing."""
+        if self.params.task == L.TASK_ROCKET_LANDING:
+            return 7
         return 6 if (self.params.task == L.TASK_DOGFIGHT and self.params.df_action_dim == 6) else 4
 
     def env_step(self, actions, xi=None, xi_reset=None, u_targets=None):
@@ -236,11 +239,12 @@ class BatchEngine:
 
     def _check_targets(self, u_targets):
         if u_targets is not None:
-            rows = (4 if self.params.use_yaw_targets else 3) * self.params.num_targets
+            # (Rocket-Landing: the reset's six spawn draws)
+            rows = 6 if self.params.task == L.TASK_ROCKET_LANDING else (4 if self.params.use_yaw_targets else 3) * self.params.num_targets
             self._check_f32(u_targets, (rows, self.n), "u_targets")
 
     def sample_actions(self, out, step_index: int):
-        self._check_f32(out, (self.n, 4), "out")
+        self._check_f32(out, (self.n, 7 if self.params.task == L.TASK_ROCKET_LANDING else 4), "out")
         with torch.cuda.device(self.device):
             L.check(self.lib.pf_sample_actions(self._ctx, _ptr(out), int(step_index) & 0xFFFFFFFF, self._stream()), self._ctx)
         return out
@@ -258,7 +262,7 @@ class BatchEngine:
             t = dict(k=k, obs=torch.empty(k, self.n, self.obs_dim, **f32), reward=torch.empty(k, self.n, **f32),
                      terminated=torch.empty(k, self.n, dtype=torch.bool, device=self.device),
                      truncated=torch.empty(k, self.n, dtype=torch.bool, device=self.device),
-                     actions=torch.empty(k, self.n, 4, **f32),
+                     actions=torch.empty(k, self.n, 7 if self.params.task == L.TASK_ROCKET_LANDING else 4, **f32),
                      final_obs=torch.zeros(k, self.n, self.obs_dim, **f32) if self.final_obs is not None else None,
                      final_info=torch.zeros(k, self.n, 2, dtype=torch.int32, device=self.device) if self.final_info is not None else None)
             self._traj = t

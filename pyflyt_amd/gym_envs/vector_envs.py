@@ -4,6 +4,7 @@ They mirror, per lane, the reference's single-env classes (file:line under /root
   QuadXHoverVecEnv        <- gym_envs/quadx_envs/quadx_hover_env.py:10-138 (+ quadx_base_env.py)
   QuadXWaypointsVecEnv    <- gym_envs/quadx_envs/quadx_waypoints_env.py:11-204
   FixedwingWaypointsVecEnv<- gym_envs/fixedwing_envs/fixedwing_waypoints_env.py:11-190
+  RocketLandingVecEnv     <- gym_envs/rocket_envs/rocket_landing_env.py (+ rocket_base_env.py)
 with the same constructor keywords, action/observation layouts, reward, termination and info keys.
 The reference has no vector env; the batch dimension and auto-reset follow gymnasium.vector
 (num_envs, single_*_space, reset(seed=, options=), step(actions) -> 5-tuple, autoreset_mode).
@@ -302,6 +303,69 @@ class FixedwingWaypointsVecEnv(_WaypointsMixin, _VecEnvBase):
         super().__init__(num_envs, sparse_reward=sparse_reward, num_targets=num_targets, goal_reach_distance=goal_reach_distance,
                          flight_mode=flight_mode, flight_dome_size=flight_dome_size, max_duration_seconds=max_duration_seconds,
                          angle_representation=angle_representation, agent_hz=agent_hz, **kw)
+
+
+class RocketLandingVecEnv(_VecEnvBase):
+    """PyFlyt/Rocket-Landing-v4, batched: gym_envs/rocket_envs/rocket_landing_env.py (+ rocket_base_env.py). Keywords as
+    rocket_landing_env.py:37-46. Actions [n, 7]: finlet x, finlet y, finlet roll, ignition, throttle, gimbal 1, gimbal 2 in
+    low (-1, -1, -1, 0, 0, -1, -1), high 1. Observation [n, 30] (quaternion) or [n, 29] (euler): ang_vel, attitude, lin_vel,
+    lin_pos, action (7), aux (9), landing-pad contact -- the pad value lags one Aviary step, as the reference's does.
+    reset(options=...): None (what gymnasium.make passes) turns on randomize_drop and accelerate_drop, a dict each key it holds
+    (options={}: neither); auto-resets reuse the options of the last reset(). A different set rebuilds the context, so it cannot
+    come with a reset_mask; a dict holding only reset_mask keeps the current set. (The reference keeps a randomized spawn in
+    self.start_pos, so its next reset with options={} starts there; here such a reset starts from `start_pos`.)
+    Not in make_vec / make yet: "PyFlyt/Rocket-Landing-v4" stays the unknown-id probe of the existing API tests; registering it
+    is a one-line follow-up together with a new probe id."""
+    _vehicle, _task = "rocket", "rocket_landing"
+    _LOW = (-1.0, -1.0, -1.0, 0.0, 0.0, -1.0, -1.0)  # rocket_base_env.py:95-119
+
+    def __init__(self, num_envs: int, *, sparse_reward: bool = False, ceiling: float = 500.0, max_displacement: float = 200.0,
+                 max_duration_seconds: float = 30.0, angle_representation: str = "quaternion", agent_hz: int = 40, **kw):
+        super().__init__(num_envs, sparse_reward=sparse_reward, ceiling=ceiling, max_displacement=max_displacement,
+                         max_duration_seconds=max_duration_seconds, angle_representation=angle_representation, agent_hz=agent_hz,
+                         reset_options=L.RL_RANDOMIZE_DROP | L.RL_ACCELERATE_DROP, **kw)
+        self.single_action_space = Box(low=np.array(self._LOW, dtype=np.float32), high=np.ones(7, dtype=np.float32), dtype=np.float32)
+        self.action_space = batch_box(self.single_action_space, self.num_envs)
+
+    def _make_obs_space(self):
+        P = self.engine.params
+        self.attitude_dim = (13 if P.angle_repr else 12) + 7 + 9  # rocket_base_env.py:77-126 (combined_space)
+        low = np.full(self.attitude_dim + 1, -np.inf, dtype=np.float32)
+        high = np.full(self.attitude_dim + 1, np.inf, dtype=np.float32)
+        low[-1], high[-1] = 0.0, 1.0  # the pad contact (rocket_landing_env.py:69-73)
+        self.single_observation_space = Box(low=low, high=high, dtype=np.float32)
+        self.observation_space = batch_box(self.single_observation_space, self.num_envs)
+
+    def reset(self, *, seed: int | None = None, options: dict | None = None):
+        if options is None:
+            bits = L.RL_RANDOMIZE_DROP | L.RL_ACCELERATE_DROP
+        elif not ({"randomize_drop", "accelerate_drop"} & set(options)) and "reset_mask" in options:
+            bits = self._kwargs["reset_options"]
+        else:
+            bits = (L.RL_RANDOMIZE_DROP if options.get("randomize_drop", False) else 0) | \
+                   (L.RL_ACCELERATE_DROP if options.get("accelerate_drop", False) else 0)
+        if bits != self._kwargs["reset_options"]:
+            if options is not None and options.get("reset_mask") is not None:
+                raise ValueError("cannot change the reset options in a partial reset")
+            self._kwargs["reset_options"] = bits
+            self._seed = self._seed if seed is None else int(seed)
+            self.engine.close()
+            self._build(self._seed)
+        return super().reset(seed=seed, options=options)
+
+    def sample_actions(self, step_index: int = 0):
+        """Device-side uniform sample of the seven-wide action box (the role of action_space.sample())."""
+        out = torch.empty(self.num_envs, 7, dtype=torch.float32, device=self.device)
+        return self.engine.sample_actions(out, step_index)
+
+    def _infos(self, flags=None, n_left=None) -> LazyInfos:
+        f = self.engine.flags() if flags is None else flags
+        return LazyInfos({
+            "out_of_bounds": lambda: (f & L.F_INFO_OOB) != 0,          # rocket_base_env.py:293-299
+            "fatal_collision": lambda: (f & L.F_INFO_COLLISION) != 0,  # rocket_base_env.py:287-291, rocket_landing_env.py:228-232
+            "env_complete": lambda: (f & L.F_INFO_COMPLETE) != 0,      # rocket_landing_env.py:234-242
+            "nonfinite": lambda: (f & L.F_NONFINITE) != 0,
+        })
 
 
 _REGISTRY = {

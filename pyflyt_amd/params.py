@@ -218,6 +218,11 @@ WORLD: dict[str, Any] = {
     "contact_break_distance": 0.02,      # persisting points / reports: btPersistentManifold's contact breaking threshold
     "contact_manifold_points": 4,        # per collider box: the incident face's four vertices (8: every vertex)
     "contact_slop": 1e-5,                # PyBullet's m_linearSlop: what a resting body overlaps the floor by
+    # Rocket-Landing's landing pad (models/landing_pad.urdf: cylinder radius 2, length 0.1; loaded at basePosition (0, 0, 0.1),
+    # rocket_landing_env.py:97-101): its top face at z = 0.15. The rim and the side wall are not modelled.
+    "landing_pad_pos": (0.0, 0.0, 0.1),
+    "landing_pad_radius": 2.0,
+    "landing_pad_length": 0.1,
 }
 
 
@@ -309,8 +314,13 @@ def build_params(
     start_orn=None,
     vehicle_options: dict | None = None,
     world_options: dict | None = None,
+    ceiling: float | None = None,
+    max_displacement: float | None = None,
+    reset_options: int = L.RL_RANDOMIZE_DROP | L.RL_ACCELERATE_DROP,
 ) -> L.PfParams:
-    """vehicle in {'quadx','fixedwing','rocket'}; task in {'none','hover','waypoints','ma_hover','dogfight'}.
+    """vehicle in {'quadx','fixedwing','rocket'}; task in {'none','hover','waypoints','ma_hover','dogfight','rocket_landing'}.
+    rocket_landing (rocket + task 'rocket_landing' only): ceiling, max_displacement and the reset options (pf_rl_option bits:
+    reset(options=None) in the reference means both, options={} neither -- rocket_landing_env.py:86-91).
     dogfight: overrides of DOGFIGHT (team_size, spawn radii, damage_per_hit, lethal_distance, lethal_angle, aggressiveness,
     cooperativeness, sample_spawn)."""
     W = dict(WORLD, **(world_options or {}))
@@ -426,8 +436,8 @@ def build_params(
         default_start, start_vel = (0.0, 0.0, 10.0), V["starting_velocity"]  # fixedwing_waypoints_env.py:63
         low, high = (-1.0,) * 4, (1.0,) * 4  # fixedwing_base_env.py:78-80
     elif vehicle == "rocket":
-        if task != "none":
-            raise ValueError("the Rocket is available at the Aviary level only (Rocket-Landing needs a resting contact)")
+        if task not in ("none", "rocket_landing"):
+            raise ValueError("the Rocket flies the Aviary level and the rocket_landing task only (rocket_landing_env.py)")
         V = copy.deepcopy(ROCKET)
         V.update(vehicle_options or {})
         P.vehicle = L.ROCKET
@@ -474,7 +484,7 @@ def build_params(
             Sf.half_rho_area = 0.5 * 1.225 * f["chord"] * f["span"]; Sf.chord = f["chord"]
         _fill(P.drag_const, [0.5 * 1.225 * c * a for c, a in zip(V["drag_coef"], V["drag_area"])])  # boring_bodies.py:63
         default_start, start_vel = (0.0, 0.0, 1.0), (0.0, 0.0, 0.0)
-        low, high = (-1.0,) * 4, (1.0,) * 4
+        low, high = (-1.0,) * 4, (1.0,) * 4  # (Rocket-Landing's seven-wide box is fixed in the kernel: rocket_landing.hpp)
     else:
         raise ValueError(f"unknown vehicle {vehicle!r}")
 
@@ -517,6 +527,25 @@ def build_params(
         P.df_aggressiveness, P.df_cooperativeness = float(DF["aggressiveness"]), float(DF["cooperativeness"])
         P.throttle_remap = 1  # ma_fixedwing_base_env.py:300-301
         d_dome, d_dur, d_hz, d_reach = 800.0, 60.0, 30, 0.0
+    elif task == "rocket_landing":  # rocket_landing_env.py:37-66, rocket_base_env.py:134-143
+        if vehicle != "rocket":
+            raise ValueError("the rocket_landing task flies the Rocket")
+        if int(flight_mode) != 0:
+            raise ValueError("the rocket_landing task flies the Rocket in flight mode 0 (rocket_base_env.py:219)")
+        P.task = L.TASK_ROCKET_LANDING
+        d_dome, d_dur, d_hz, d_reach = math.inf, 30.0, 40, 0.0
+        P.ceiling = min(500.0 if ceiling is None else float(ceiling), 3.0e38)
+        P.max_displacement = min(200.0 if max_displacement is None else float(max_displacement), 3.0e38)
+        if reset_options & ~(L.RL_RANDOMIZE_DROP | L.RL_ACCELERATE_DROP):
+            raise ValueError("reset_options: RL_RANDOMIZE_DROP | RL_ACCELERATE_DROP bits only")
+        P.rl_reset_options = int(reset_options)
+        _fill(P.pad_pos, [float(x) * W["world_scale"] for x in W["landing_pad_pos"]])
+        P.pad_radius = float(W["landing_pad_radius"]) * W["world_scale"]
+        P.pad_half_height = 0.5 * float(W["landing_pad_length"]) * W["world_scale"]
+        if not (P.pad_radius > 0.0 and P.pad_half_height >= 0.0):
+            raise ValueError("landing_pad_radius must be > 0 and landing_pad_length >= 0")
+        P.rocket.starting_fuel_ratio = 0.05  # rocket_landing_env.py:92 (drone_options)
+        default_start = (0.0, 0.0, 0.9 * P.ceiling)  # rocket_landing_env.py:56
     elif task == "waypoints":
         P.task = L.TASK_WAYPOINTS
         if vehicle == "quadx":  # quadx_waypoints_env.py:38-47,87
