@@ -867,25 +867,35 @@ __global__ void __launch_bounds__(256) sample_actions_kernel(const pf_params P, 
 }  // namespace pf
 
 // ====================================================================== C ABI
+// The env kernel a context runs, chosen once at pf_ctx_create (select_env_kernel).
+enum class env_family : uint8_t {
+  none,              // no env task: the pf_aviary_* calls only
+  quadx,             // quadx_m0_env_kernel (quadx_fast.hpp)
+  fixedwing_wp,      // fixedwing_wp_env_kernel (fixedwing_fast.hpp)
+  dogfight_fast,     // dogfight_env_kernel<A, DfFastVeh>: the aircraft run on the specialised Fixedwing tick (dogfight.hpp)
+  dogfight_generic,  // dogfight_env_kernel<A, DfGenericVeh>
+  rocket_landing,    // env_kernel<Rocket, PF_TASK_ROCKET_LANDING, kRuntimeMode> (rocket_landing.hpp)
+  generic,           // env_kernel<QuadX / Fixedwing, TASK, MODE_T>
+};
+struct env_choice {
+  env_family family;
+  bool cr, md, sh;  // quadx: quadx_m0_env_kernel's CR / MD / SH, as K implies them
+  bool wps1;        // quadx, fixedwing_wp: the one-wave-per-SIMD instantiation (WPS = 1, 512 registers)
+};
+
 struct pf_ctx {
   pf_params P;
   int n;
   int device;
   uint64_t lane0;
   char err[256];
-  // hot-path specialisation (quadx_fast.hpp)
-  bool fast;
+  env_choice ek;
   uint32_t* launch_ctr;  // device, one word per workgroup of the specialised QuadX kernel: env steps taken so far -- the cadence its waves refill their spares on (quadx_fast.hpp: QuadSpare)
-  bool one_wave; // the batch is at most one wave per SIMD of the device (the 512-register instantiations' condition)
-  bool lean;     // the batch is at most one wave per SIMD of the device: the specialised QuadX kernel's 512-register instantiation
   pf::QuadK K;
   pf_params* P_dev;  // device copy of P for the rarely-taken floor paths (contact detection and response) and the LDS constant tables
   float4* tmpl;      // settled spawn state for lane-independent resets (env_kernel), or null
-  // Fixedwing-Waypoints specialisation (fixedwing_fast.hpp)
-  bool fast_fw;
   pf::FwK FK;
   pf::FwTable* surf_dev;  // pre-combined surface + body constants (scalar-loaded per tick)
-  bool df_fast;           // dogfight: the aircraft run on the specialised Fixedwing tick (dogfight.hpp: DfFastVeh)
 };
 static thread_local char g_err[256] = "";
 
@@ -905,80 +915,157 @@ static int hip_fail(pf_ctx* ctx, hipError_t e, const char* where) {
     if (e__ != hipSuccess) return hip_fail(ctx, e__, #call); \
   } while (0)
 
-template <int TASK>
-static void launch_fast(pf_ctx* ctx, const pf_buffers* b, int op, const uint8_t* mask, hipStream_t s) {
-  const int grid = (ctx->n + 64 * pf::kQuadWPB - 1) / (64 * pf::kQuadWPB);
-  // (the one-wave-per-SIMD instantiation -- quadx_fast.hpp, WPS -- where the batch is no more than that and the kernel has it; since
-  //  round 6 the PettingZoo task with independent lanes as well; since round 5 the cascaded flight modes: their fp64 controller needs the 512 registers -- 408 B of stack per lane under 256)
-#define PF_FAST4(NZ, CR, MD, SH) do { constexpr int W1 = ((CR) && !(SH)) ? 1 : 2; \
-    if (W1 == 1 && ctx->lean) hipLaunchKernelGGL((pf::quadx_m0_env_kernel<TASK, NZ, 64, 0, CR, MD, SH, W1>), dim3(grid), dim3(64 * pf::kQuadWPB), 0, s, ctx->K, *b, ctx->P_dev, ctx->n, ctx->lane0, op, mask, 1, 0u, ctx->launch_ctr); \
-    else hipLaunchKernelGGL((pf::quadx_m0_env_kernel<TASK, NZ, 64, 0, CR, MD, SH, 2>), dim3(grid), dim3(64 * pf::kQuadWPB), 0, s, ctx->K, *b, ctx->P_dev, ctx->n, ctx->lane0, op, mask, 1, 0u, ctx->launch_ctr); } while (0)
-  // (flight modes other than 0: the MODES instantiation, contact response compiled in -- quadk_from_params)
-  // (shared worlds: PF_TASK_MA_HOVER with the contact response on -- quadk_from_params)
-#define PF_FAST3(NZ, CR, MD) do { if (TASK == PF_TASK_MA_HOVER && CR && ctx->K.apw > 1) PF_FAST4(NZ, CR, MD, (TASK == PF_TASK_MA_HOVER && CR)); else PF_FAST4(NZ, CR, MD, false); } while (0)
-#define PF_FAST(NZ) do { if (ctx->K.mode != 0) PF_FAST3(NZ, true, true); else if (ctx->P.contact_response) PF_FAST3(NZ, true, false); else PF_FAST3(NZ, false, false); } while (0)
-  if (ctx->P.noise_mode == PF_NOISE_PHILOX) PF_FAST(PF_NOISE_PHILOX);
-  else if (ctx->P.noise_mode == PF_NOISE_INJECT) PF_FAST(PF_NOISE_INJECT);
-  else PF_FAST(PF_NOISE_OFF);
-#undef PF_FAST
-#undef PF_FAST3
-#undef PF_FAST4
-}
-template <int TASK>
-static void launch_rollout(pf_ctx* ctx, const pf_buffers* b, int k_steps, uint32_t step0, hipStream_t s) {
-  const int grid = (ctx->n + 64 * pf::kQuadWPB - 1) / (64 * pf::kQuadWPB);
-#define PF_ROLL4(NZ, R, CR, MD, SH) do { constexpr int W1 = ((CR) && !(SH)) ? 1 : 2; \
-    if (W1 == 1 && ctx->lean) hipLaunchKernelGGL((pf::quadx_m0_env_kernel<TASK, NZ, 64, R, CR, MD, SH, W1>), dim3(grid), dim3(64 * pf::kQuadWPB), 0, s, ctx->K, *b, ctx->P_dev, ctx->n, ctx->lane0, 0, (const uint8_t*)nullptr, k_steps, step0, ctx->launch_ctr); \
-    else hipLaunchKernelGGL((pf::quadx_m0_env_kernel<TASK, NZ, 64, R, CR, MD, SH, 2>), dim3(grid), dim3(64 * pf::kQuadWPB), 0, s, ctx->K, *b, ctx->P_dev, ctx->n, ctx->lane0, 0, (const uint8_t*)nullptr, k_steps, step0, ctx->launch_ctr); } while (0)
-#define PF_ROLL3(NZ, R, CR, MD) do { if (TASK == PF_TASK_MA_HOVER && CR && ctx->K.apw > 1) PF_ROLL4(NZ, R, CR, MD, (TASK == PF_TASK_MA_HOVER && CR)); else PF_ROLL4(NZ, R, CR, MD, false); } while (0)
-#define PF_ROLL(NZ, R) do { if (ctx->K.mode != 0) PF_ROLL3(NZ, R, true, true); else if (ctx->P.contact_response) PF_ROLL3(NZ, R, true, false); else PF_ROLL3(NZ, R, false, false); } while (0)
-  if (b->actions == nullptr) {
-    if (ctx->P.noise_mode == PF_NOISE_PHILOX) PF_ROLL(PF_NOISE_PHILOX, 1);
-    else PF_ROLL(PF_NOISE_OFF, 1);
-  } else {
-    if (ctx->P.noise_mode == PF_NOISE_PHILOX) PF_ROLL(PF_NOISE_PHILOX, 2);
-    else PF_ROLL(PF_NOISE_OFF, 2);
+// Which env kernel a context runs, and its launch-invariant template arguments; fills K, FK and fsurf for the specialised kernels.
+// The only reader of the environment overrides, which exist for the tests: PF_DISABLE_FAST forces the generic kernels,
+// PF_NO_LEAN_KERNEL the two-wave instantiations, PF_NO_CALM_PATH turns the specialised QuadX kernel's calm-wave ticks off.
+static env_choice select_env_kernel(const pf_params& P, int n_lanes, int device, pf::QuadK& K, pf::FwK& FK, pf::FwTable& fsurf) {
+  env_choice c{env_family::generic, false, false, false, false};
+  const bool fast = getenv("PF_DISABLE_FAST") == nullptr;
+  int cus = 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) cus = 0;
+  // the batch is at most one wave per SIMD of the device (4 SIMDs per CU): a second resident wave would have nothing to run
+  const bool one_wave = cus > 0 && ((long)n_lanes + 63) / 64 <= 4L * cus && getenv("PF_NO_LEAN_KERNEL") == nullptr;
+  if (P.task == PF_TASK_NONE) {
+    c.family = env_family::none;
+  } else if (P.task == PF_TASK_ROCKET_LANDING) {
+    c.family = env_family::rocket_landing;
+  } else if (P.task == PF_TASK_DOGFIGHT) {
+    c.family = fast && pf::fw_table_from_params(P, fsurf) ? env_family::dogfight_fast : env_family::dogfight_generic;
+  } else if (fast && pf::quadk_from_params(P, K)) {
+    c.family = env_family::quadx;
+    if (getenv("PF_NO_CALM_PATH") != nullptr) K.calm_on = 0;
+    // (flight modes other than 0: the MODES instantiation, contact response compiled in; shared worlds: PF_TASK_MA_HOVER with the
+    //  contact response on -- quadk_from_params)
+    c.md = K.mode != 0;
+    c.cr = c.md || P.contact_response;
+    c.sh = P.task == PF_TASK_MA_HOVER && c.cr && K.apw > 1;
+    // (the one-wave-per-SIMD instantiation -- quadx_fast.hpp, WPS -- exists where CR && !SH: since round 6 the PettingZoo task with
+    //  independent lanes as well; since round 5 the cascaded flight modes: their fp64 controller needs the 512 registers -- 408 B of
+    //  stack per lane under 256. It solves floor contacts in registers, four slots = the incident face: quad_floor_solve)
+    c.wps1 = one_wave && P.contact_manifold_points < 8 && c.cr && !c.sh;
+  } else if (fast && pf::fwk_from_params(P, FK, fsurf)) {
+    c.family = env_family::fixedwing_wp;
+    c.wps1 = one_wave;
   }
-#undef PF_ROLL
-#undef PF_ROLL3
-#undef PF_ROLL4
+  return c;
 }
-static void launch_fast_fw(pf_ctx* ctx, const pf_buffers* b, int op, const uint8_t* mask, hipStream_t s) {
-  const int grid = (ctx->n + 63) / 64;
-  // (the one-wave-per-SIMD instantiation -- fixedwing_fast.hpp, WPS -- where the batch is no more than that)
-#define PF_FAST(NZ) do { if (ctx->one_wave) hipLaunchKernelGGL((pf::fixedwing_wp_env_kernel<NZ, 0, 1>), dim3(grid), dim3(64), 0, s, ctx->FK, ctx->surf_dev, *b, ctx->P_dev, ctx->tmpl, ctx->n, ctx->lane0, op, mask, 1, 0u); \
-    else hipLaunchKernelGGL((pf::fixedwing_wp_env_kernel<NZ, 0, 2>), dim3(grid), dim3(64), 0, s, ctx->FK, ctx->surf_dev, *b, ctx->P_dev, ctx->tmpl, ctx->n, ctx->lane0, op, mask, 1, 0u); } while (0)
-  if (ctx->P.noise_mode == PF_NOISE_PHILOX) PF_FAST(PF_NOISE_PHILOX);
-  else if (ctx->P.noise_mode == PF_NOISE_INJECT) PF_FAST(PF_NOISE_INJECT);
-  else PF_FAST(PF_NOISE_OFF);
-#undef PF_FAST
+
+// The instantiation of a per-vehicle kernel for the context's vehicle. Each call passes those of the vehicles it admits (none for
+// the Rocket where the call or pf_ctx_create refuses it).
+template <class KERNEL>
+static KERNEL vehicle_kernel(const pf_ctx* ctx, KERNEL quadx, KERNEL fixedwing, KERNEL rocket = nullptr) {
+  return ctx->P.vehicle == PF_QUADX ? quadx : (ctx->P.vehicle == PF_ROCKET && rocket) ? rocket : fixedwing;
 }
-static void launch_rollout_fw(pf_ctx* ctx, const pf_buffers* b, int k_steps, uint32_t step0, hipStream_t s) {
-  const int grid = (ctx->n + 63) / 64;
-#define PF_ROLL(NZ, R) do { if (ctx->one_wave) hipLaunchKernelGGL((pf::fixedwing_wp_env_kernel<NZ, R, 1>), dim3(grid), dim3(64), 0, s, ctx->FK, ctx->surf_dev, *b, ctx->P_dev, ctx->tmpl, ctx->n, ctx->lane0, 0, (const uint8_t*)nullptr, k_steps, step0); \
-    else hipLaunchKernelGGL((pf::fixedwing_wp_env_kernel<NZ, R, 2>), dim3(grid), dim3(64), 0, s, ctx->FK, ctx->surf_dev, *b, ctx->P_dev, ctx->tmpl, ctx->n, ctx->lane0, 0, (const uint8_t*)nullptr, k_steps, step0); } while (0)
-  if (b->actions == nullptr) {
-    if (ctx->P.noise_mode == PF_NOISE_PHILOX) PF_ROLL(PF_NOISE_PHILOX, 1);
-    else PF_ROLL(PF_NOISE_OFF, 1);
-  } else {
-    if (ctx->P.noise_mode == PF_NOISE_PHILOX) PF_ROLL(PF_NOISE_PHILOX, 2);
-    else PF_ROLL(PF_NOISE_OFF, 2);
+
+// The env kernels' instantiations. A launch takes the context's choice (env_choice) and the call's ROLL: 0 for pf_env_reset and
+// pf_env_step, 1 for pf_rollout with the actions drawn on the device, 2 for pf_rollout over the given b->actions. The pickers
+// name exactly the instantiations that can run.
+template <int V>
+using int_c = std::integral_constant<int, V>;
+
+// pick(NOISE, ROLL) (pf_rollout refuses PF_NOISE_INJECT: the rollouts have no such instantiation)
+template <class Pick>
+static auto by_noise_roll(int noise, int roll, Pick pick) {
+  const bool philox = noise == PF_NOISE_PHILOX;
+  if (roll == 1) return philox ? pick(int_c<PF_NOISE_PHILOX>{}, int_c<1>{}) : pick(int_c<PF_NOISE_OFF>{}, int_c<1>{});
+  if (roll == 2) return philox ? pick(int_c<PF_NOISE_PHILOX>{}, int_c<2>{}) : pick(int_c<PF_NOISE_OFF>{}, int_c<2>{});
+  if (noise == PF_NOISE_INJECT) return pick(int_c<PF_NOISE_INJECT>{}, int_c<0>{});
+  return philox ? pick(int_c<PF_NOISE_PHILOX>{}, int_c<0>{}) : pick(int_c<PF_NOISE_OFF>{}, int_c<0>{});
+}
+
+template <int TASK, int NZ, int R>
+static auto quadx_m0_kernel(const env_choice& c) {
+  constexpr bool MA = TASK == PF_TASK_MA_HOVER;  // (c.sh: a shared world, the PettingZoo task only)
+  using namespace pf;
+  if (c.md)
+    return c.sh ? quadx_m0_env_kernel<TASK, NZ, 64, R, true, true, MA, 2>
+                : c.wps1 ? quadx_m0_env_kernel<TASK, NZ, 64, R, true, true, false, 1> : quadx_m0_env_kernel<TASK, NZ, 64, R, true, true, false, 2>;
+  if (c.cr)
+    return c.sh ? quadx_m0_env_kernel<TASK, NZ, 64, R, true, false, MA, 2>
+                : c.wps1 ? quadx_m0_env_kernel<TASK, NZ, 64, R, true, false, false, 1> : quadx_m0_env_kernel<TASK, NZ, 64, R, true, false, false, 2>;
+  return quadx_m0_env_kernel<TASK, NZ, 64, R, false, false, false, 2>;
+}
+
+template <class VEH, bool ROLLOUT>
+static auto dogfight_kernel(int agents_per_world) {
+  switch (agents_per_world) {
+    case 2: return pf::dogfight_env_kernel<2, VEH, ROLLOUT>;
+    case 4: return pf::dogfight_env_kernel<4, VEH, ROLLOUT>;
+    case 6: return pf::dogfight_env_kernel<6, VEH, ROLLOUT>;
+    default: return pf::dogfight_env_kernel<8, VEH, ROLLOUT>;
   }
-#undef PF_ROLL
 }
-template <class VEH, int TASK>
-static void launch_env_t(pf_ctx* ctx, const pf_buffers* b, int op, const uint8_t* mask, hipStream_t s, int roll_steps = 0, uint32_t step0 = 0u) {
-  const int grid = (ctx->n + pf::kWave - 1) / pf::kWave;
-  if (ctx->P.vehicle == PF_QUADX && ctx->P.flight_mode == 0)
-    hipLaunchKernelGGL((pf::env_kernel<VEH, TASK, 0>), dim3(grid), dim3(pf::kWave), 0, s, ctx->P, *b, ctx->n, ctx->lane0, op, mask, ctx->tmpl, ctx->P_dev, roll_steps, step0);
-  else
-    hipLaunchKernelGGL((pf::env_kernel<VEH, TASK, pf::kRuntimeMode>), dim3(grid), dim3(pf::kWave), 0, s, ctx->P, *b, ctx->n, ctx->lane0, op, mask, ctx->tmpl, ctx->P_dev, roll_steps, step0);
+
+// env_kernel: MODE_T = 0 for a QuadX in flight mode 0, else the runtime mode -- the context's flight mode at this call, which
+// pf_aviary_set_mode and pf_aviary_reset change
+static auto generic_env_kernel(const pf_ctx* ctx) {
+  using namespace pf;
+  const pf_params& P = ctx->P;
+  if (ctx->ek.family == env_family::rocket_landing) return env_kernel<Rocket, PF_TASK_ROCKET_LANDING, kRuntimeMode>;
+  if (P.vehicle != PF_QUADX) return env_kernel<Fixedwing, PF_TASK_WAYPOINTS, kRuntimeMode>;
+  const bool m0 = P.flight_mode == 0;
+  if (P.task == PF_TASK_HOVER) return m0 ? env_kernel<QuadX, PF_TASK_HOVER, 0> : env_kernel<QuadX, PF_TASK_HOVER, kRuntimeMode>;
+  if (P.task == PF_TASK_MA_HOVER) return m0 ? env_kernel<QuadX, PF_TASK_MA_HOVER, 0> : env_kernel<QuadX, PF_TASK_MA_HOVER, kRuntimeMode>;
+  return m0 ? env_kernel<QuadX, PF_TASK_WAYPOINTS, 0> : env_kernel<QuadX, PF_TASK_WAYPOINTS, kRuntimeMode>;
 }
-static void launch_rocket_landing(pf_ctx* ctx, const pf_buffers* b, int op, const uint8_t* mask, hipStream_t s, int roll_steps = 0, uint32_t step0 = 0u) {
-  const int grid = (ctx->n + pf::kWave - 1) / pf::kWave;
-  hipLaunchKernelGGL((pf::env_kernel<pf::Rocket, PF_TASK_ROCKET_LANDING, pf::kRuntimeMode>), dim3(grid), dim3(pf::kWave), 0, s, ctx->P, *b, ctx->n, ctx->lane0, op, mask,
-                     (const float4*)nullptr, ctx->P_dev, roll_steps, step0);
+
+static int ensure_device(pf_ctx* ctx) {
+  int cur = -1;
+  PF_HIP(ctx, hipGetDevice(&cur));
+  if (cur != ctx->device) PF_HIP(ctx, hipSetDevice(ctx->device));
+  return PF_OK;
 }
+
+// One launch of the context's env kernel: a reset or a step (roll 0, op and mask) or a rollout (roll 1 / 2, k_steps steps from step
+// index step0). The callers have checked the arguments.
+static int launch_env(pf_ctx* ctx, const pf_buffers* b, int op, const uint8_t* mask, int roll, int k_steps, uint32_t step0, void* stream) {
+  int rc = ensure_device(ctx);
+  if (rc) return rc;
+  const pf_params& P = ctx->P;
+  const env_choice& c = ctx->ek;
+  hipStream_t s = (hipStream_t)stream;
+  switch (c.family) {
+    case env_family::quadx: {
+      const auto kernel = by_noise_roll(P.noise_mode, roll, [&](auto NZ, auto R) {
+        if (P.task == PF_TASK_HOVER) return quadx_m0_kernel<PF_TASK_HOVER, NZ, R>(c);
+        if (P.task == PF_TASK_MA_HOVER) return quadx_m0_kernel<PF_TASK_MA_HOVER, NZ, R>(c);
+        return quadx_m0_kernel<PF_TASK_WAYPOINTS, NZ, R>(c);
+      });
+      const int grid = (ctx->n + 64 * pf::kQuadWPB - 1) / (64 * pf::kQuadWPB);
+      hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * pf::kQuadWPB), 0, s, ctx->K, *b, ctx->P_dev, ctx->n, ctx->lane0, op, mask, k_steps, step0,
+                         ctx->launch_ctr);
+      break;
+    }
+    case env_family::fixedwing_wp: {
+      const auto kernel = by_noise_roll(P.noise_mode, roll, [&](auto NZ, auto R) {
+        return c.wps1 ? pf::fixedwing_wp_env_kernel<NZ, R, 1> : pf::fixedwing_wp_env_kernel<NZ, R, 2>;
+      });
+      hipLaunchKernelGGL(kernel, dim3((ctx->n + 63) / 64), dim3(64), 0, s, ctx->FK, ctx->surf_dev, *b, ctx->P_dev, ctx->tmpl, ctx->n, ctx->lane0, op,
+                         mask, k_steps, step0);
+      break;
+    }
+    case env_family::dogfight_fast:
+    case env_family::dogfight_generic: {
+      const int apw = P.agents_per_world, lpw = (64 / apw) * apw;  // whole worlds per wave
+      const bool fast = c.family == env_family::dogfight_fast;
+      const auto kernel = roll ? (fast ? dogfight_kernel<pf::DfFastVeh, true>(apw) : dogfight_kernel<pf::DfGenericVeh, true>(apw))
+                               : (fast ? dogfight_kernel<pf::DfFastVeh, false>(apw) : dogfight_kernel<pf::DfGenericVeh, false>(apw));
+      hipLaunchKernelGGL(kernel, dim3((ctx->n + lpw - 1) / lpw), dim3(64), 0, s, ctx->P, *b, ctx->n, ctx->lane0, op, mask, ctx->P_dev, ctx->surf_dev,
+                         k_steps, step0);
+      break;
+    }
+    case env_family::rocket_landing:
+    case env_family::generic:  // (roll_steps 0: one step)
+      hipLaunchKernelGGL(generic_env_kernel(ctx), dim3((ctx->n + pf::kWave - 1) / pf::kWave), dim3(pf::kWave), 0, s, ctx->P, *b, ctx->n, ctx->lane0,
+                         op, mask, ctx->tmpl, ctx->P_dev, roll ? k_steps : 0, step0);
+      break;
+    case env_family::none:  // (refused by the callers)
+      break;
+  }
+  PF_HIP(ctx, hipGetLastError());
+  return PF_OK;
+}
+
 extern "C" {
 
 int pf_abi_version(void) { return PF_ABI_VERSION; }
@@ -1053,18 +1140,9 @@ int pf_ctx_create(const pf_params* params, int n_lanes, int device, uint64_t lan
     c->P.contact_max_points = pts < 1 ? 1 : (pts > PF_MAX_CONTACTS ? PF_MAX_CONTACTS : pts);
   }
   c->P_dev = nullptr; c->tmpl = nullptr; c->surf_dev = nullptr;
-  c->fast = pf::quadk_from_params(P, c->K) && getenv("PF_DISABLE_FAST") == nullptr;
-  {
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) cus = 0;
-    const long waves = ((long)n_lanes + 63) / 64;
-    // (the lean instantiations solve floor contacts in registers, four slots = the incident face: quadx_fast.hpp, quad_floor_solve)
-    c->one_wave = cus > 0 && waves <= 4L * cus && getenv("PF_NO_LEAN_KERNEL") == nullptr;  // (4 SIMDs per CU)
-    c->lean = c->one_wave && P.contact_manifold_points < 8;
-  }
   pf::FwTable fsurf;
-  c->fast_fw = pf::fwk_from_params(P, c->FK, fsurf) && getenv("PF_DISABLE_FAST") == nullptr;
-  c->df_fast = P.task == PF_TASK_DOGFIGHT && pf::fw_table_from_params(P, fsurf) && getenv("PF_DISABLE_FAST") == nullptr;
+  c->ek = select_env_kernel(P, n_lanes, device, c->K, c->FK, fsurf);
+  const env_family fam = c->ek.family;
   {  // device copy of the parameter block (LDS constant tables, the out-of-line floor test)
     int cur = -1;
     (void)hipGetDevice(&cur);
@@ -1074,22 +1152,22 @@ int pf_ctx_create(const pf_params* params, int n_lanes, int device, uint64_t lan
     if (e == hipSuccess) e = hipMemcpy(c->P_dev, &c->P, sizeof(pf_params), hipMemcpyHostToDevice);
     if (e == hipSuccess) {
       float sw[pf::kQuadSolveWords] = {0};
-      if (c->fast) pf::quad_solve_words(c->P, sw);
+      if (fam == env_family::quadx) pf::quad_solve_words(c->P, sw);
       e = hipMemcpy(reinterpret_cast<char*>(c->P_dev) + pf::kQuadSolveOffset, sw, sizeof(sw), hipMemcpyHostToDevice);
     }
-    if (e == hipSuccess && c->fast) {  // (quadx_fast.hpp: launch_ctr)
+    if (e == hipSuccess && fam == env_family::quadx) {  // (quadx_fast.hpp: launch_ctr)
       const size_t words = (size_t)pf::kCtrStride * (((size_t)n_lanes + 63) / 64);
       e = hipMalloc((void**)&c->launch_ctr, sizeof(uint32_t) * words);
       if (e == hipSuccess) e = hipMemset(c->launch_ctr, 0, sizeof(uint32_t) * words);
     }
-    if (e == hipSuccess && (c->fast_fw || c->df_fast)) {
+    if (e == hipSuccess && (fam == env_family::fixedwing_wp || fam == env_family::dogfight_fast)) {
       e = hipMalloc((void**)&c->surf_dev, sizeof(fsurf));
       if (e == hipSuccess) e = hipMemcpy(c->surf_dev, &fsurf, sizeof(fsurf), hipMemcpyHostToDevice);
     }
     if (cur >= 0) (void)hipSetDevice(cur);
     if (e != hipSuccess) { if (c->P_dev) hipFree(c->P_dev); if (c->launch_ctr) hipFree(c->launch_ctr); delete c; return hip_fail(nullptr, e, "pf_ctx_create: device parameter block"); }
   }
-  if (!c->fast && (P.task == PF_TASK_HOVER || P.task == PF_TASK_WAYPOINTS) &&
+  if ((fam == env_family::fixedwing_wp || fam == env_family::generic) && (P.task == PF_TASK_HOVER || P.task == PF_TASK_WAYPOINTS) &&
       (P.vehicle == PF_FIXEDWING || P.noise_mode == PF_NOISE_OFF)) {
     // the settle phase cannot depend on the lane (fixedwing: throttle command 0 during settle, so the
     // motor noise scales nothing; or noise off): settle once here, resets copy the result
@@ -1100,8 +1178,8 @@ int pf_ctx_create(const pf_params* params, int n_lanes, int device, uint64_t lan
     hipError_t e = hipMalloc((void**)&c->tmpl, sizeof(float4) * groups);
     if (e == hipSuccess) e = hipMemset(c->tmpl, 0, sizeof(float4) * groups);
     if (e == hipSuccess) {
-      if (P.vehicle == PF_QUADX) hipLaunchKernelGGL(pf::settle_template_kernel<pf::QuadX>, dim3(1), dim3(64), 0, 0, c->P, c->tmpl, c->P_dev);
-      else hipLaunchKernelGGL(pf::settle_template_kernel<pf::Fixedwing>, dim3(1), dim3(64), 0, 0, c->P, c->tmpl, c->P_dev);
+      hipLaunchKernelGGL(vehicle_kernel(c, pf::settle_template_kernel<pf::QuadX>, pf::settle_template_kernel<pf::Fixedwing>), dim3(1), dim3(64), 0, 0, c->P,
+                         c->tmpl, c->P_dev);
       e = hipDeviceSynchronize();
     }
     if (cur >= 0) hipSetDevice(cur);
@@ -1119,11 +1197,12 @@ void pf_ctx_destroy(pf_ctx* ctx) {
   delete ctx;
 }
 int pf_state_groups(const pf_ctx* ctx) {
-  if (ctx->P.task == PF_TASK_DOGFIGHT) return pf::kDfGroups;
-  if (ctx->P.task == PF_TASK_ROCKET_LANDING) return pf::kRlGroups;
+  const env_family f = ctx->ek.family;
+  if (f == env_family::dogfight_fast || f == env_family::dogfight_generic) return pf::kDfGroups;
+  if (f == env_family::rocket_landing) return pf::kRlGroups;
   // (the specialised QuadX kernel in a cascaded flight mode, no shared world: eleven more groups, the float32 remainders of its fp64
   //  rigid-body state and PID memories -- quadx_fast.hpp: QuadStateD)
-  if (ctx->fast && ctx->K.mode != 0 && ctx->K.apw == 1) return pf::QuadX::GROUPS + 11;  // (16-19 state, 20-21 rate PID, 22-26 cascade)
+  if (f == env_family::quadx && ctx->K.mode != 0 && ctx->K.apw == 1) return pf::QuadX::GROUPS + 11;  // (16-19 state, 20-21 rate PID, 22-26 cascade)
   return ctx->P.vehicle == PF_QUADX ? pf::QuadX::GROUPS : (ctx->P.vehicle == PF_ROCKET ? pf::Rocket::GROUPS : pf::Fixedwing::GROUPS);
 }
 int pf_obs_dim(const pf_ctx* ctx) {
@@ -1134,16 +1213,12 @@ int pf_obs_dim(const pf_ctx* ctx) {
   return (P.angle_repr ? 13 : 12) + 4 + aux + (P.task == PF_TASK_WAYPOINTS ? (P.use_yaw_targets ? 4 : 3) * P.num_targets : (P.task == PF_TASK_MA_HOVER ? 3 : 0));
 }
 int pf_n_lanes(const pf_ctx* ctx) { return ctx->n; }
-int pf_ctx_is_specialised(const pf_ctx* ctx) { return ctx->fast ? 1 : (((ctx->fast_fw && ctx->tmpl) || ctx->df_fast) ? 2 : 0); }
-
-static int ensure_device(pf_ctx* ctx) {
-  int cur = -1;
-  PF_HIP(ctx, hipGetDevice(&cur));
-  if (cur != ctx->device) PF_HIP(ctx, hipSetDevice(ctx->device));
-  return PF_OK;
+int pf_ctx_is_specialised(const pf_ctx* ctx) {
+  const env_family f = ctx->ek.family;
+  return f == env_family::quadx ? 1 : ((f == env_family::fixedwing_wp || f == env_family::dogfight_fast) ? 2 : 0);
 }
 
-static int launch_env(pf_ctx* ctx, const pf_buffers* b, int op, const uint8_t* mask, void* stream) {
+static int env_reset_or_step(pf_ctx* ctx, const pf_buffers* b, int op, const uint8_t* mask, void* stream) {
   if (!ctx || !b || !b->state || !b->obs) return fail(ctx, PF_ERR_ARG, "pf_env_*: state and obs buffers are required");
   const pf_params& P = ctx->P;
   if (P.task == PF_TASK_NONE) return fail(ctx, PF_ERR_ARG, "pf_env_*: context has no env task (use the pf_aviary_* calls)");
@@ -1152,39 +1227,12 @@ static int launch_env(pf_ctx* ctx, const pf_buffers* b, int op, const uint8_t* m
   if (P.noise_mode == PF_NOISE_INJECT && ((op == pf::OP_STEP && !b->xi) || !b->xi_reset))
     if (!(op == pf::OP_STEP && P.autoreset == PF_AUTORESET_OFF && b->xi))
       return fail(ctx, PF_ERR_ARG, "PF_NOISE_INJECT needs xi (step) and xi_reset (reset/auto-reset)");
-  int rc = ensure_device(ctx);
-  if (rc) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  if (P.task == PF_TASK_DOGFIGHT) {
-    const int lpw = (64 / P.agents_per_world) * P.agents_per_world;  // whole worlds per wave
-    const dim3 grid((ctx->n + lpw - 1) / lpw);
-#define PF_DF(AA, VV) hipLaunchKernelGGL((pf::dogfight_env_kernel<AA, VV>), grid, dim3(64), 0, s, ctx->P, *b, ctx->n, ctx->lane0, op, mask, ctx->P_dev, ctx->surf_dev)
-#define PF_DFA(VV) switch (P.agents_per_world) { case 2: PF_DF(2, VV); break; case 4: PF_DF(4, VV); break; case 6: PF_DF(6, VV); break; default: PF_DF(8, VV); break; }
-    if (ctx->df_fast) { PF_DFA(pf::DfFastVeh) } else { PF_DFA(pf::DfGenericVeh) }
-#undef PF_DFA
-#undef PF_DF
-  } else if (P.task == PF_TASK_ROCKET_LANDING) {
-    launch_rocket_landing(ctx, b, op, mask, s);
-  } else if (ctx->fast) {
-    if (P.task == PF_TASK_HOVER) launch_fast<PF_TASK_HOVER>(ctx, b, op, mask, s);
-    else if (P.task == PF_TASK_MA_HOVER) launch_fast<PF_TASK_MA_HOVER>(ctx, b, op, mask, s);
-    else launch_fast<PF_TASK_WAYPOINTS>(ctx, b, op, mask, s);
-  } else if (ctx->fast_fw && ctx->tmpl) {
-    launch_fast_fw(ctx, b, op, mask, s);
-  } else if (P.vehicle == PF_QUADX) {
-    if (P.task == PF_TASK_HOVER) launch_env_t<pf::QuadX, PF_TASK_HOVER>(ctx, b, op, mask, s);
-    else if (P.task == PF_TASK_MA_HOVER) launch_env_t<pf::QuadX, PF_TASK_MA_HOVER>(ctx, b, op, mask, s);
-    else launch_env_t<pf::QuadX, PF_TASK_WAYPOINTS>(ctx, b, op, mask, s);
-  } else {
-    launch_env_t<pf::Fixedwing, PF_TASK_WAYPOINTS>(ctx, b, op, mask, s);
-  }
-  PF_HIP(ctx, hipGetLastError());
-  return PF_OK;
+  return launch_env(ctx, b, op, mask, 0, 1, 0u, stream);
 }
 int pf_env_reset(pf_ctx* ctx, const pf_buffers* b, const uint8_t* mask, void* stream) {
-  return launch_env(ctx, b, pf::OP_RESET, mask, stream);
+  return env_reset_or_step(ctx, b, pf::OP_RESET, mask, stream);
 }
-int pf_env_step(pf_ctx* ctx, const pf_buffers* b, void* stream) { return launch_env(ctx, b, pf::OP_STEP, nullptr, stream); }
+int pf_env_step(pf_ctx* ctx, const pf_buffers* b, void* stream) { return env_reset_or_step(ctx, b, pf::OP_STEP, nullptr, stream); }
 
 int pf_aviary_reset(pf_ctx* ctx, const pf_buffers* b, void* stream) {
   if (!ctx || !b || !b->state) return fail(ctx, PF_ERR_ARG, "pf_aviary_reset: state buffer required");
@@ -1193,12 +1241,8 @@ int pf_aviary_reset(pf_ctx* ctx, const pf_buffers* b, void* stream) {
   const int grid = (ctx->n + pf::kWave - 1) / pf::kWave;
   hipStream_t s = (hipStream_t)stream;
   const float* pose = b->start_pose;
-  if (ctx->P.vehicle == PF_QUADX)
-    hipLaunchKernelGGL(pf::aviary_reset_kernel<pf::QuadX>, dim3(grid), dim3(pf::kWave), 0, s, ctx->P, *b, ctx->n, pose);
-  else if (ctx->P.vehicle == PF_ROCKET)
-    hipLaunchKernelGGL(pf::aviary_reset_kernel<pf::Rocket>, dim3(grid), dim3(pf::kWave), 0, s, ctx->P, *b, ctx->n, pose);
-  else
-    hipLaunchKernelGGL(pf::aviary_reset_kernel<pf::Fixedwing>, dim3(grid), dim3(pf::kWave), 0, s, ctx->P, *b, ctx->n, pose);
+  const auto kernel = vehicle_kernel(ctx, pf::aviary_reset_kernel<pf::QuadX>, pf::aviary_reset_kernel<pf::Fixedwing>, pf::aviary_reset_kernel<pf::Rocket>);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(pf::kWave), 0, s, ctx->P, *b, ctx->n, pose);
   ctx->P.flight_mode = 0;  // drone.reset() -> set_mode(0) (quadx.py:224, fixedwing.py:196)
   PF_HIP(ctx, hipGetLastError());
   return PF_OK;
@@ -1214,12 +1258,8 @@ int pf_aviary_set_mode(pf_ctx* ctx, const pf_buffers* b, int mode, float* setpoi
   const int grid = (ctx->n + pf::kWave - 1) / pf::kWave;
   hipStream_t s = (hipStream_t)stream;
   const int sp_dim = ctx->P.vehicle == PF_ROCKET ? 7 : ((ctx->P.vehicle == PF_FIXEDWING && mode == -1) ? 6 : 4);  // fixedwing.py:221-224, rocket.py:228
-  if (ctx->P.vehicle == PF_QUADX)
-    hipLaunchKernelGGL(pf::aviary_set_mode_kernel<pf::QuadX>, dim3(grid), dim3(pf::kWave), 0, s, ctx->P, *b, ctx->n, sp_dim, mode, setpoints_out);
-  else if (ctx->P.vehicle == PF_ROCKET)
-    hipLaunchKernelGGL(pf::aviary_set_mode_kernel<pf::Rocket>, dim3(grid), dim3(pf::kWave), 0, s, ctx->P, *b, ctx->n, sp_dim, mode, setpoints_out);
-  else
-    hipLaunchKernelGGL(pf::aviary_set_mode_kernel<pf::Fixedwing>, dim3(grid), dim3(pf::kWave), 0, s, ctx->P, *b, ctx->n, sp_dim, mode, setpoints_out);
+  const auto kernel = vehicle_kernel(ctx, pf::aviary_set_mode_kernel<pf::QuadX>, pf::aviary_set_mode_kernel<pf::Fixedwing>, pf::aviary_set_mode_kernel<pf::Rocket>);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(pf::kWave), 0, s, ctx->P, *b, ctx->n, sp_dim, mode, setpoints_out);
   ctx->P.flight_mode = mode;
   PF_HIP(ctx, hipGetLastError());
   return PF_OK;
@@ -1232,17 +1272,10 @@ int pf_aviary_step(pf_ctx* ctx, const pf_buffers* b, int n_steps, void* stream) 
   if (rc) return rc;
   const int grid = (ctx->n + pf::kWave - 1) / pf::kWave;
   hipStream_t s = (hipStream_t)stream;
-  if (ctx->P.agents_per_world > 1) {  // shared worlds (pf_ctx_create admitted QuadX / Fixedwing with plain boxes only)
-    if (ctx->P.vehicle == PF_QUADX)
-      hipLaunchKernelGGL(pf::aviary_world_step_kernel<pf::QuadX>, dim3(grid), dim3(pf::kWave), 0, s, ctx->P, *b, ctx->n, ctx->lane0, n_steps, ctx->P_dev);
-    else
-      hipLaunchKernelGGL(pf::aviary_world_step_kernel<pf::Fixedwing>, dim3(grid), dim3(pf::kWave), 0, s, ctx->P, *b, ctx->n, ctx->lane0, n_steps, ctx->P_dev);
-  } else if (ctx->P.vehicle == PF_QUADX)
-    hipLaunchKernelGGL(pf::aviary_step_kernel<pf::QuadX>, dim3(grid), dim3(pf::kWave), 0, s, ctx->P, *b, ctx->n, ctx->lane0, n_steps, ctx->P_dev);
-  else if (ctx->P.vehicle == PF_ROCKET)
-    hipLaunchKernelGGL(pf::aviary_step_kernel<pf::Rocket>, dim3(grid), dim3(pf::kWave), 0, s, ctx->P, *b, ctx->n, ctx->lane0, n_steps, ctx->P_dev);
-  else
-    hipLaunchKernelGGL(pf::aviary_step_kernel<pf::Fixedwing>, dim3(grid), dim3(pf::kWave), 0, s, ctx->P, *b, ctx->n, ctx->lane0, n_steps, ctx->P_dev);
+  const auto kernel = ctx->P.agents_per_world > 1  // shared worlds (pf_ctx_create admitted QuadX / Fixedwing with plain boxes only)
+                          ? vehicle_kernel(ctx, pf::aviary_world_step_kernel<pf::QuadX>, pf::aviary_world_step_kernel<pf::Fixedwing>)
+                          : vehicle_kernel(ctx, pf::aviary_step_kernel<pf::QuadX>, pf::aviary_step_kernel<pf::Fixedwing>, pf::aviary_step_kernel<pf::Rocket>);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(pf::kWave), 0, s, ctx->P, *b, ctx->n, ctx->lane0, n_steps, ctx->P_dev);
   PF_HIP(ctx, hipGetLastError());
   return PF_OK;
 }
@@ -1255,12 +1288,8 @@ int pf_aviary_tick(pf_ctx* ctx, const pf_buffers* b, int tick_index, void* strea
   if (rc) return rc;
   const int grid = (ctx->n + pf::kWave - 1) / pf::kWave;
   hipStream_t s = (hipStream_t)stream;
-  if (ctx->P.vehicle == PF_QUADX)
-    hipLaunchKernelGGL(pf::aviary_tick_kernel<pf::QuadX>, dim3(grid), dim3(pf::kWave), 0, s, ctx->P, *b, ctx->n, ctx->lane0, tick_index, ctx->P_dev);
-  else if (ctx->P.vehicle == PF_ROCKET)
-    hipLaunchKernelGGL(pf::aviary_tick_kernel<pf::Rocket>, dim3(grid), dim3(pf::kWave), 0, s, ctx->P, *b, ctx->n, ctx->lane0, tick_index, ctx->P_dev);
-  else
-    hipLaunchKernelGGL(pf::aviary_tick_kernel<pf::Fixedwing>, dim3(grid), dim3(pf::kWave), 0, s, ctx->P, *b, ctx->n, ctx->lane0, tick_index, ctx->P_dev);
+  const auto kernel = vehicle_kernel(ctx, pf::aviary_tick_kernel<pf::QuadX>, pf::aviary_tick_kernel<pf::Fixedwing>, pf::aviary_tick_kernel<pf::Rocket>);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(pf::kWave), 0, s, ctx->P, *b, ctx->n, ctx->lane0, tick_index, ctx->P_dev);
   PF_HIP(ctx, hipGetLastError());
   return PF_OK;
 }
@@ -1284,57 +1313,17 @@ int pf_rollout(pf_ctx* ctx, const pf_buffers* b, int k_steps, uint32_t step_inde
     return fail(ctx, PF_ERR_ARG, "pf_rollout: state, obs, reward, terminated and truncated buffers are required");
   if (k_steps < 1) return fail(ctx, PF_ERR_ARG, "pf_rollout: k_steps must be >= 1");
   const pf_params& P = ctx->P;
-  const bool fw = ctx->fast_fw && ctx->tmpl;
+  const env_family f = ctx->ek.family;
   if (P.noise_mode == PF_NOISE_INJECT) return fail(ctx, PF_ERR_UNSUPPORTED, "pf_rollout: PF_NOISE_INJECT is a per-step protocol; use pf_env_step");
   if (P.task == PF_TASK_NONE) return fail(ctx, PF_ERR_UNSUPPORTED, "pf_rollout: this context has no env task");
-  if (P.task == PF_TASK_DOGFIGHT) {
-    // the dogfight, state-resident on either aircraft model: dogfight_env_kernel<.., ROLLOUT = true> (four-wide actions sampled on
-    // device, or the given sequence of either width)
-    if (!b->actions && P.df_action_dim == 6) return fail(ctx, PF_ERR_UNSUPPORTED, "pf_rollout: on-device sampling draws four-wide actions; pass the six-wide sequence in b->actions");
-    int rc = ensure_device(ctx);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    const int lpw = (64 / P.agents_per_world) * P.agents_per_world;  // whole worlds per wave
-    dim3 grid((ctx->n + lpw - 1) / lpw);
-#define PF_DFR(AA, VV) hipLaunchKernelGGL((pf::dogfight_env_kernel<AA, VV, true>), grid, dim3(64), 0, s, ctx->P, *b, ctx->n, ctx->lane0, 0, \
-                                          (const uint8_t*)nullptr, ctx->P_dev, ctx->surf_dev, k_steps, step_index0)
-#define PF_DFRA(VV) switch (P.agents_per_world) { case 2: PF_DFR(2, VV); break; case 4: PF_DFR(4, VV); break; case 6: PF_DFR(6, VV); break; default: PF_DFR(8, VV); break; }
-    if (ctx->df_fast) { PF_DFRA(pf::DfFastVeh) } else { PF_DFRA(pf::DfGenericVeh) }
-#undef PF_DFRA
-#undef PF_DFR
-    PF_HIP(ctx, hipGetLastError());
-    return PF_OK;
-  }
-  if (!fw && !ctx->fast) {
-    // Every other task (the generic env kernel: tilted multi-agent spawns, airframes and flight modes outside the specialised
-    // envelopes): state-resident as well since round 4 -- env_kernel's roll_steps, one launch for the k_steps.
-    int rc = ensure_device(ctx);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    if (P.task == PF_TASK_ROCKET_LANDING) {
-      launch_rocket_landing(ctx, b, pf::OP_STEP, nullptr, s, k_steps, step_index0);
-    } else if (P.vehicle == PF_QUADX) {
-      if (P.task == PF_TASK_HOVER) launch_env_t<pf::QuadX, PF_TASK_HOVER>(ctx, b, pf::OP_STEP, nullptr, s, k_steps, step_index0);
-      else if (P.task == PF_TASK_MA_HOVER) launch_env_t<pf::QuadX, PF_TASK_MA_HOVER>(ctx, b, pf::OP_STEP, nullptr, s, k_steps, step_index0);
-      else launch_env_t<pf::QuadX, PF_TASK_WAYPOINTS>(ctx, b, pf::OP_STEP, nullptr, s, k_steps, step_index0);
-    } else {
-      launch_env_t<pf::Fixedwing, PF_TASK_WAYPOINTS>(ctx, b, pf::OP_STEP, nullptr, s, k_steps, step_index0);
-    }
-    PF_HIP(ctx, hipGetLastError());
-    return PF_OK;
-  }
+  // Every env kernel is state-resident in a rollout: one launch for the k_steps (the dogfight on either aircraft model: four-wide
+  // actions sampled on device, or the given sequence of either width; the generic env kernel: roll_steps)
+  if ((f == env_family::dogfight_fast || f == env_family::dogfight_generic) && !b->actions && P.df_action_dim == 6)
+    return fail(ctx, PF_ERR_UNSUPPORTED, "pf_rollout: on-device sampling draws four-wide actions; pass the six-wide sequence in b->actions");
   // (the PettingZoo task has no auto-reset: finished agents are culled by the caller, their drones fly on in the shared world)
-  if (P.autoreset == PF_AUTORESET_OFF && P.task != PF_TASK_MA_HOVER)
+  if ((f == env_family::quadx || f == env_family::fixedwing_wp) && P.autoreset == PF_AUTORESET_OFF && P.task != PF_TASK_MA_HOVER)
     return fail(ctx, PF_ERR_UNSUPPORTED, "pf_rollout: needs an auto-reset mode (finished lanes would idle for the rest of the launch)");
-  int rc = ensure_device(ctx);
-  if (rc) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  if (fw) launch_rollout_fw(ctx, b, k_steps, step_index0, s);
-  else if (P.task == PF_TASK_HOVER) launch_rollout<PF_TASK_HOVER>(ctx, b, k_steps, step_index0, s);
-  else if (P.task == PF_TASK_MA_HOVER) launch_rollout<PF_TASK_MA_HOVER>(ctx, b, k_steps, step_index0, s);
-  else launch_rollout<PF_TASK_WAYPOINTS>(ctx, b, k_steps, step_index0, s);
-  PF_HIP(ctx, hipGetLastError());
-  return PF_OK;
+  return launch_env(ctx, b, pf::OP_STEP, nullptr, b->actions ? 2 : 1, k_steps, step_index0, stream);
 }
 int pf_body_tick(pf_ctx* ctx, const pf_buffers* b, int n_ticks, void* stream) {
   if (!ctx || !b || !b->state || !b->wrench) return fail(ctx, PF_ERR_ARG, "pf_body_tick: state and wrench buffers are required");
@@ -1344,10 +1333,8 @@ int pf_body_tick(pf_ctx* ctx, const pf_buffers* b, int n_ticks, void* stream) {
   if (rc) return rc;
   const int grid = (ctx->n + pf::kWave - 1) / pf::kWave;
   hipStream_t s = (hipStream_t)stream;
-  if (ctx->P.vehicle == PF_QUADX)
-    hipLaunchKernelGGL(pf::body_tick_kernel<pf::QuadX>, dim3(grid), dim3(pf::kWave), 0, s, ctx->P, *b, ctx->n, n_ticks, ctx->P_dev);
-  else
-    hipLaunchKernelGGL(pf::body_tick_kernel<pf::Fixedwing>, dim3(grid), dim3(pf::kWave), 0, s, ctx->P, *b, ctx->n, n_ticks, ctx->P_dev);
+  const auto kernel = vehicle_kernel(ctx, pf::body_tick_kernel<pf::QuadX>, pf::body_tick_kernel<pf::Fixedwing>);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(pf::kWave), 0, s, ctx->P, *b, ctx->n, n_ticks, ctx->P_dev);
   PF_HIP(ctx, hipGetLastError());
   return PF_OK;
 }

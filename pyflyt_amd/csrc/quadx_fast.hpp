@@ -162,9 +162,10 @@ inline bool quadk_from_params(const pf_params& P, QuadK& K) {
     K.calm_kt = 4.0f * K.fmaxM;
     K.calm_t2 = fmaxf(tstar * tstar, 1.0f);
     K.calm_c = fmaxf(fmaxf(__builtin_fabsf(K.dragM[0]), __builtin_fabsf(K.dragM[1])), __builtin_fabsf(K.dragM[2]));
-    // (injected noise is unbounded; mode -1 hands the action to the motors unclipped; a shared world has the pair stage in its tick)
+    // (injected noise is unbounded; mode -1 hands the action to the motors unclipped; a shared world has the pair stage in its tick;
+    //  PF_NO_CALM_PATH: the kernel selection clears it -- pyflyt_amd.hip, select_env_kernel)
     K.calm_on = (P.contact_response && P.noise_mode != PF_NOISE_INJECT && P.flight_mode != -1 && K.apw == 1 && P.motor_dt_over_tau[0] <= 1.0f &&
-                 K.calm_t2 < 1e6f && getenv("PF_NO_CALM_PATH") == nullptr) ? 1 : 0;
+                 K.calm_t2 < 1e6f) ? 1 : 0;
   }
   K.use_yaw = (P.task == PF_TASK_WAYPOINTS && P.use_yaw_targets) ? 1 : 0;
   K.goal_angle = P.goal_reach_angle;
