@@ -203,14 +203,16 @@ __global__ void __launch_bounds__(64) dogfight_env_kernel(const pf_params P, con
   }
   float4 sp_a = Sin[13 * N + li], sp_b = Sin[14 * N + li];
 
+  // (this kernel keeps its own copies of Noise::init, sampled_action4, done_flags and step_outputs: each of those calls, alone,
+  //  moved its register allocation, six more VGPRs in the rollouts)
   Noise nz;
   nz.mode = P.noise_mode; nz.n = n; nz.lane = (int)li;
   nz.k0 = (uint32_t)P.seed; nz.k1 = (uint32_t)(P.seed >> 32);
   nz.c0 = (uint32_t)(lane0 + li); nz.nmot = (float)P.n_motors; nz.cached = -1; nz.xi = nullptr;
 
   // (a mask that names some aircraft of a world resets the world)
-  const bool do_reset = widen_to_world(op == 1 && valid && ((mask == nullptr) || (mask[li] != 0)), tid, A);
-  const bool active = valid && (op == 0 || do_reset);
+  const bool do_reset = widen_to_world(op == OP_RESET && valid && ((mask == nullptr) || (mask[li] != 0)), tid, A);
+  const bool active = valid && (op == OP_STEP || do_reset);
   float sp[6] = {0, 0, 0, 0, 0, 0};
 
   // One Aviary.step of the shared world: control + ticks_per_control x (exchange, tick)
@@ -390,7 +392,7 @@ __global__ void __launch_bounds__(64) dogfight_env_kernel(const pf_params P, con
   for (int it = 0; it < KS; ++it) {
   const size_t toff = ROLLOUT ? (size_t)it * N : (size_t)0;  // this step's slot in the trajectory buffers (lanes)
   out_reward = 0.0f; out_term = false; out_trunc = false;
-  if (op == 1) {
+  if (op == OP_RESET) {
     // ---------------------------------------------------------------- reset (dogfight :215-322, base env :160-234)
     if (do_reset) {
       if (P.df_sample_spawn) {  // _get_start_pos_orn (:176-213): the world's draws, keyed by its first lane
@@ -430,7 +432,7 @@ __global__ void __launch_bounds__(64) dogfight_env_kernel(const pf_params P, con
     // ---------------------------------------------------------------- step (ma_fixedwing_base_env.py:272-334)
     float4 a;
     float a4 = 0.0f, a5 = 0.0f;
-    if (ROLLOUT && B.actions == nullptr) {  // == sample_actions_kernel(step0 + it): same Philox key, same arithmetic (four-wide)
+    if (ROLLOUT && B.actions == nullptr) {  // == sample_actions_kernel(step0 + it) (four-wide)
       const f4 u = uniform4(philox4x32((uint32_t)P.seed, (uint32_t)(P.seed >> 32), (uint32_t)(lane0 + li), step0 + (uint32_t)it, 0u, 3u));
       a = float4{fmaf(P.action_high[0] - P.action_low[0], u.a, P.action_low[0]), fmaf(P.action_high[1] - P.action_low[1], u.b, P.action_low[1]),
                  fmaf(P.action_high[2] - P.action_low[2], u.c, P.action_low[2]), fmaf(P.action_high[3] - P.action_low[3], u.d, P.action_low[3])};
@@ -472,7 +474,7 @@ __global__ void __launch_bounds__(64) dogfight_env_kernel(const pf_params P, con
       for (int k = 0; k < D; ++k) g[k] = row[k];
     }
   }
-  if (active && op == 0) {
+  if (active && op == OP_STEP) {
     B.reward[toff + li] = out_reward;
     B.terminated[toff + li] = out_term ? 1 : 0;
     B.truncated[toff + li] = out_trunc ? 1 : 0;

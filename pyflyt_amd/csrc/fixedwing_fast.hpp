@@ -876,7 +876,7 @@ __global__ void __launch_bounds__(64, WPS) fixedwing_wp_env_kernel(const FwK K, 
   {
     float4 gi = Sin[5 * N + li];
     float4 g0 = Sin[0 * N + li], g1 = Sin[1 * N + li], g2 = Sin[2 * N + li], g3 = Sin[3 * N + li], g4 = Sin[4 * N + li];
-    if (ROLL == 0 && op == 0) a_pre = reinterpret_cast<const float4*>(B.actions)[li];
+    if (ROLL == 0 && op == OP_STEP) a_pre = reinterpret_cast<const float4*>(B.actions)[li];
     // (the rare code's prefetch, uav_vehicles.hpp: only where a second wave shares the SIMD -- with one wave per SIMD every wave takes
     //  the same time and the prefetching ones were the launch's slowest: 21.1 -> 20.7 us without)
     if (WPS != 1 && blockIdx.x < kRareTextPrefetchBlocks) rare_text_prefetch((int)threadIdx.x);
@@ -891,7 +891,7 @@ __global__ void __launch_bounds__(64, WPS) fixedwing_wp_env_kernel(const FwK K, 
     rng_ctr = (uint32_t)__float_as_int(gi.z);
     PF_STAMP(1);
     if (NOISE == PF_NOISE_PHILOX) {
-      if (op == 0) zn = normal8(philox4x32(K.seed_lo, K.seed_hi, (uint32_t)(lane0 + li), rng_ctr, 0u, 0u));
+      if (op == OP_STEP) zn = normal8(philox4x32(K.seed_lo, K.seed_hi, (uint32_t)(lane0 + li), rng_ctr, 0u, 0u));
     }
     if (WPS == 1) {  // (one wave per workgroup; LDS operations of a wave complete in issue order)
       ktab[tid] = tw0;
@@ -921,7 +921,7 @@ __global__ void __launch_bounds__(64, WPS) fixedwing_wp_env_kernel(const FwK K, 
   bool term = (flags & PF_F_TERMINATED) != 0, trunc = (flags & PF_F_TRUNCATED) != 0;
 
   bool active;
-  if (op == 1) active = (mask == nullptr) || (mask[li] != 0);
+  if (op == OP_RESET) active = (mask == nullptr) || (mask[li] != 0);
   else active = true;
   active = active && valid;
 
@@ -938,11 +938,7 @@ __global__ void __launch_bounds__(64, WPS) fixedwing_wp_env_kernel(const FwK K, 
       for (int c = 0; c < 3; ++c) tgt[k][c] = tgt[k + 1][c];
     n_left -= 1;
   };
-  auto lds_sync = [&]() {  // one wave per workgroup: see quadx_fast.hpp
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-    __builtin_amdgcn_wave_barrier();
-  };
+  auto lds_sync = [&]() { lds_sync_wave(); };  // (a lambda of its own, as in quadx_fast.hpp)
   // Waypoint sampling (waypoint_handler.py:53-83), cooperatively (quadx_fast.hpp: prepare_targets): a resetting lane needs three
   // Philox calls and, per target, two sine / cosine pairs -- some 700 instructions that the one or two resetting lanes of a wave walked
   // through while the other lanes idled, in about every second wave of a launch, and a launch lasts as long as its slowest wave.
@@ -1095,7 +1091,7 @@ __global__ void __launch_bounds__(64, WPS) fixedwing_wp_env_kernel(const FwK K, 
     }
   };
   const bool wave_all = __all(active || !valid);
-  auto flush_tile = [&](float* out) {
+  auto flush_tile = [&](float* out) {  // (a copy of flush_obs_tile: that call moved this kernel's register allocation)
     lds_sync();
     if (wave_all) {
       const int rows = min(64, n - wave_base);
@@ -1117,7 +1113,7 @@ __global__ void __launch_bounds__(64, WPS) fixedwing_wp_env_kernel(const FwK K, 
   const size_t toff = ROLLOUT ? (size_t)it * N : (size_t)0;  // this step's slot in the trajectory buffers (lanes)
   // ---------------------------------------------------------------- reset (NEXT_STEP / explicit)
   bool do_reset;
-  if (op == 1) do_reset = active;
+  if (op == OP_RESET) do_reset = active;
   else do_reset = (K.autoreset == PF_AUTORESET_NEXT_STEP) && (term || trunc) && active;
   act0 = act1 = act2 = act3 = 0.f;
   reward = 0.0f;
@@ -1127,7 +1123,7 @@ __global__ void __launch_bounds__(64, WPS) fixedwing_wp_env_kernel(const FwK K, 
   PF_STAMP(4);
 
   // ---------------------------------------------------------------- the env step
-  const bool stepping = active && !was_reset && op == 0;
+  const bool stepping = active && !was_reset && op == OP_STEP;
 #pragma unroll
   for (int k = 0; k < 6; ++k) V.cmd[k] = 0.f;
   float4 a_roll = float4{0.f, 0.f, 0.f, 0.f};
@@ -1135,10 +1131,8 @@ __global__ void __launch_bounds__(64, WPS) fixedwing_wp_env_kernel(const FwK K, 
     if (GIVEN) {
       a_roll = a_nxt;
       if (it + 1 < KS) a_nxt = reinterpret_cast<const float4*>(B.actions)[toff + N + li];
-    } else {  // == sample_actions_kernel(step0 + it): same Philox key, same arithmetic
-      f4 u = uniform4(philox4x32(K.seed_lo, K.seed_hi, (uint32_t)(lane0 + li), step0 + (uint32_t)it, 0u, 3u));
-      a_roll = float4{fmaf(K.act_span[0], u.a, K.act_lo[0]), fmaf(K.act_span[1], u.b, K.act_lo[1]),
-                      fmaf(K.act_span[2], u.c, K.act_lo[2]), fmaf(K.act_span[3], u.d, K.act_lo[3])};
+    } else {  // == sample_actions_kernel(step0 + it)
+      a_roll = sampled_action4<false>(K.seed_lo, K.seed_hi, (uint32_t)(lane0 + li), step0 + (uint32_t)it, K.act_lo, K.act_span);
     }
     if (!GIVEN && B.actions_out != nullptr && active) {
       float* ao = B.actions_out + 4 * (toff + li);
@@ -1226,8 +1220,7 @@ __global__ void __launch_bounds__(64, WPS) fixedwing_wp_env_kernel(const FwK K, 
         flush_tile(B.final_obs + toff * D);
       }
       if (B.final_info != nullptr && same) {  // gymnasium's final_info: the episode's flags / targets left, pre-reset
-        B.final_info[2 * (toff + li) + 0] = (flags & ~(PF_F_TERMINATED | PF_F_TRUNCATED | PF_F_CONTACT)) | (term ? PF_F_TERMINATED : 0) |
-                                            (trunc ? PF_F_TRUNCATED : 0) | (V.contact_now ? PF_F_CONTACT : 0);
+        B.final_info[2 * (toff + li) + 0] = done_flags(flags, term, trunc, V.contact_now);
         B.final_info[2 * (toff + li) + 1] = n_left - (pop_pending ? 1 : 0);
       }
       prepare_targets(same);
@@ -1243,9 +1236,8 @@ __global__ void __launch_bounds__(64, WPS) fixedwing_wp_env_kernel(const FwK K, 
   PF_STAMP(8);
   if (active) {
     if (pop_pending) { pop_target(); pop_pending = false; }
-    flags = (flags & ~(PF_F_TERMINATED | PF_F_TRUNCATED | PF_F_CONTACT)) | (term ? PF_F_TERMINATED : 0) |
-            (trunc ? PF_F_TRUNCATED : 0) | (V.contact_now ? PF_F_CONTACT : 0);
-    if (op == 0) {
+    flags = done_flags(flags, term, trunc, V.contact_now);
+    if (op == OP_STEP) {  // (a copy of step_outputs, as in quadx_fast.hpp)
       B.reward[toff + li] = out_reward;
       B.terminated[toff + li] = out_term ? 1 : 0;
       B.truncated[toff + li] = out_trunc ? 1 : 0;

@@ -28,7 +28,6 @@ namespace pf {
 constexpr int kWave = 64;
 constexpr int kMaxObs = 40;  // 13 + 4 + 6 + 3*4 = 35 (Fixedwing), 13 + 4 + 4 + 4*4 = 37 (QuadX with yaw targets)
 
-enum { OP_STEP = 0, OP_RESET = 1 };
 // Aviary-level kernels (where bodies land and stay landed): 30 KB of LDS for the contact solve -- every lane of a wave of
 // quadrotors (the incident face's 4 vertices + the sentinel, 24 floats each) in one round, six worst-case airframes (48
 // vertices) side by side
@@ -145,9 +144,7 @@ __global__ void __launch_bounds__(kWave) env_kernel(const pf_params P, const pf_
   float old_dist = new_dist;
 
   Noise nz;
-  nz.mode = P.noise_mode; nz.n = n; nz.lane = (int)li;
-  nz.k0 = (uint32_t)P.seed; nz.k1 = (uint32_t)(P.seed >> 32);
-  nz.c0 = (uint32_t)(lane0 + li); nz.nmot = (float)P.n_motors; nz.cached = -1; nz.xi = nullptr;
+  nz.init(P, n, li, lane0);
 
   bool active = false, do_reset = false, wave_all = false;  // (per env step: set at the top of the step loop below)
 
@@ -303,26 +300,6 @@ __global__ void __launch_bounds__(kWave) env_kernel(const pf_params P, const pf_
       }
     }
   };
-  // tile -> global with full-width stores; LDS-only sync (one wave per workgroup, see quadx_fast.hpp)
-  auto lds_sync = [&]() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-    __builtin_amdgcn_wave_barrier();
-  };
-  auto flush_tile = [&](float* out) {
-    lds_sync();
-    if (wave_all) {
-      const int rows = min(kWave, n - wave_base);
-      const int total = rows * D;
-      float* g = out + (size_t)wave_base * D;
-      stream_tile(tile, g, total, tid);
-    } else if (active) {  // partial (masked reset): this lane writes its own row
-      float* g = out + (size_t)lane * D;
-      const float* row = tile + tid * D;
-      for (int k = 0; k < D; ++k) g[k] = row[k];
-    }
-    lds_sync();
-  };
 
   const int n_env_steps = roll_steps > 0 ? roll_steps : 1;
   for (int ks = 0; ks < n_env_steps; ++ks) {
@@ -355,9 +332,7 @@ __global__ void __launch_bounds__(kWave) env_kernel(const pf_params P, const pf_
   int my_its = 0;         // Aviary steps this lane still has to run in the loop below
   float4 a = float4{0.f, 0.f, 0.f, 0.f};
   if (roll_steps > 0 && B.actions == nullptr) {  // pf_sample_actions' draw for (lane, step0 + ks): every lane's, restarting or not
-    f4 u = uniform4(philox4x32((uint32_t)P.seed, (uint32_t)(P.seed >> 32), (uint32_t)(lane0 + li), step0 + (uint32_t)ks, 0u, 3u));
-    a = float4{fmaf(P.action_high[0] - P.action_low[0], u.a, P.action_low[0]), fmaf(P.action_high[1] - P.action_low[1], u.b, P.action_low[1]),
-               fmaf(P.action_high[2] - P.action_low[2], u.c, P.action_low[2]), fmaf(P.action_high[3] - P.action_low[3], u.d, P.action_low[3])};
+    a = sampled_action4<true>((uint32_t)P.seed, (uint32_t)(P.seed >> 32), (uint32_t)(lane0 + li), step0 + (uint32_t)ks, P.action_low, P.action_high);
     if (B.actions_out != nullptr && valid) reinterpret_cast<float4*>(B.actions_out)[toff + li] = a;
   } else if (active && !do_reset) {
     a = reinterpret_cast<const float4*>(B.actions)[toff + li];
@@ -434,11 +409,10 @@ __global__ void __launch_bounds__(kWave) env_kernel(const pf_params P, const pf_
     if (__any(same)) {
       if (B.final_obs != nullptr) {  // terminal observation, before the state is re-initialised
         if (active) write_obs_row();
-        flush_tile(B.final_obs + toff * D);
+        flush_obs_tile(tile, B.final_obs + toff * D, D, kWave, n, wave_base, tid, wave_all, active);
       }
       if (B.final_info != nullptr && same) {  // gymnasium's final_info: the episode's flags / targets left, pre-reset
-        B.final_info[2 * (toff + li) + 0] = (flags & ~(PF_F_TERMINATED | PF_F_TRUNCATED | PF_F_CONTACT)) | (term ? PF_F_TERMINATED : 0) |
-                                            (trunc ? PF_F_TRUNCATED : 0) | (V.b.contact_now ? PF_F_CONTACT : 0);
+        B.final_info[2 * (toff + li) + 0] = done_flags(flags, term, trunc, V.b.contact_now);
         B.final_info[2 * (toff + li) + 1] = tg.n_left - (pop_pending ? 1 : 0);
       }
       if (same) {
@@ -463,11 +437,10 @@ __global__ void __launch_bounds__(kWave) env_kernel(const pf_params P, const pf_
 
   // ---------------------------------------------------------------- outputs: obs tile first, state after
   if (active) write_obs_row();
-  flush_tile(B.obs + toff * D);
+  flush_obs_tile(tile, B.obs + toff * D, D, kWave, n, wave_base, tid, wave_all, active);
   if (active) {
     if (pop_pending) { tg.pop(); pop_pending = false; }
-    flags = (flags & ~(PF_F_TERMINATED | PF_F_TRUNCATED | PF_F_CONTACT)) | (term ? PF_F_TERMINATED : 0) |
-            (trunc ? PF_F_TRUNCATED : 0) | (V.b.contact_now ? PF_F_CONTACT : 0);
+    flags = done_flags(flags, term, trunc, V.b.contact_now);
     if (ks == n_env_steps - 1) {  // the state goes back to HBM once per launch
       V.store(Sout, N, li, mode, new_dist, int4{step_count, flags, (int)rng_ctr, tg.n_left});
       if constexpr (REKEY) {
@@ -478,11 +451,7 @@ __global__ void __launch_bounds__(kWave) env_kernel(const pf_params P, const pf_
       if (kYaw) Sout[(size_t)(VEH::G_TGT + 3) * N + li] = float4{tg.yaw[0], tg.yaw[1], tg.yaw[2], tg.yaw[3]};
       if (TASK == PF_TASK_MA_HOVER) Sout[(size_t)(VEH::G_TGT + 3) * N + li] = ma_past;
     }
-    if (op == OP_STEP) {  // a NEXT_STEP reset call reports (r=0, not done), gymnasium's convention
-      B.reward[toff + li] = out_reward;
-      B.terminated[toff + li] = out_term ? 1 : 0;
-      B.truncated[toff + li] = out_trunc ? 1 : 0;
-    }
+    step_outputs(B, op, toff, li, out_reward, out_term, out_trunc);
   }
   }  // (env steps of this launch)
 }
@@ -596,9 +565,7 @@ __global__ void __launch_bounds__(kWave) aviary_step_kernel(const pf_params P, c
   V.b.rpy = euler_from_quat_fast(V.b.q);
   uint32_t rng_ctr = (uint32_t)ints.z;
   Noise nz;
-  nz.mode = P.noise_mode; nz.n = n; nz.lane = lane;
-  nz.k0 = (uint32_t)P.seed; nz.k1 = (uint32_t)(P.seed >> 32);
-  nz.c0 = (uint32_t)(lane0 + li); nz.nmot = (float)P.n_motors; nz.cached = -1; nz.xi = nullptr;
+  nz.init(P, n, li, lane0);
   float sp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   const int spn = P.vehicle == PF_ROCKET ? 7 : ((P.vehicle == PF_FIXEDWING && mode == -1) ? 6 : 4);
 #pragma unroll
@@ -682,9 +649,7 @@ __global__ void __launch_bounds__(kWave) aviary_world_step_kernel(const pf_param
   V.b.rpy = euler_from_quat_fast(V.b.q);
   uint32_t rng_ctr = (uint32_t)ints.z;
   Noise nz;
-  nz.mode = P.noise_mode; nz.n = n; nz.lane = lane;
-  nz.k0 = (uint32_t)P.seed; nz.k1 = (uint32_t)(P.seed >> 32);
-  nz.c0 = (uint32_t)(lane0 + li); nz.nmot = (float)P.n_motors; nz.cached = -1; nz.xi = nullptr;
+  nz.init(P, n, li, lane0);
   float sp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   const int spn = (P.vehicle == PF_FIXEDWING && mode == -1) ? 6 : 4;
 #pragma unroll
@@ -766,9 +731,7 @@ __global__ void __launch_bounds__(kWave) aviary_tick_kernel(const pf_params P, c
   V.b.rpy = euler_from_quat_fast(V.b.q);
   uint32_t rng_ctr = (uint32_t)ints.z;
   Noise nz;
-  nz.mode = P.noise_mode; nz.n = n; nz.lane = lane;
-  nz.k0 = (uint32_t)P.seed; nz.k1 = (uint32_t)(P.seed >> 32);
-  nz.c0 = (uint32_t)(lane0 + li); nz.nmot = (float)P.n_motors; nz.cached = -1; nz.xi = nullptr;
+  nz.init(P, n, li, lane0);
   nz.begin_event(rng_ctr, 0u, B.xi);
   float sp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   const int spn = P.vehicle == PF_ROCKET ? 7 : ((P.vehicle == PF_FIXEDWING && mode == -1) ? 6 : 4);
@@ -856,12 +819,8 @@ __global__ void __launch_bounds__(256) sample_actions_kernel(const pf_params P, 
                                                              const uint64_t lane0, const uint32_t step_index) {
   const int lane = blockIdx.x * 256 + threadIdx.x;
   if (lane >= n) return;
-  f4 u = uniform4(philox4x32((uint32_t)P.seed, (uint32_t)(P.seed >> 32), (uint32_t)(lane0 + lane), step_index, 0u, 3u));
-  float4 a{fmaf(P.action_high[0] - P.action_low[0], u.a, P.action_low[0]),
-           fmaf(P.action_high[1] - P.action_low[1], u.b, P.action_low[1]),
-           fmaf(P.action_high[2] - P.action_low[2], u.c, P.action_low[2]),
-           fmaf(P.action_high[3] - P.action_low[3], u.d, P.action_low[3])};
-  reinterpret_cast<float4*>(actions)[lane] = a;
+  reinterpret_cast<float4*>(actions)[lane] =
+      sampled_action4<true>((uint32_t)P.seed, (uint32_t)(P.seed >> 32), (uint32_t)(lane0 + lane), step_index, P.action_low, P.action_high);
 }
 
 }  // namespace pf

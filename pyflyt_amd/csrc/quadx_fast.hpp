@@ -1379,7 +1379,7 @@ __global__ void __launch_bounds__(64 * kQuadWPB, SHARED ? 1 : WPS) quadx_m0_env_
     }
     // the action is first needed after the resets, a microsecond from here: requested where it is used (inside the stepping
     // lanes' branch) every wave sat out its whole memory latency there; requested behind the state groups it is long there
-    if (ROLL == 0 && op == 0) a_pre = reinterpret_cast<const float4*>(B.actions)[li];
+    if (ROLL == 0 && op == OP_STEP) a_pre = reinterpret_cast<const float4*>(B.actions)[li];
     float4 dl0 = float4{0.f, 0.f, 0.f, 0.f}, dl1 = dl0, dl2 = dl0, dl3 = dl0;
     float4 dl4 = dl0, dl5 = dl0;
     if (DSTATE) { dl0 = Sin[16 * N + li]; dl1 = Sin[17 * N + li]; dl2 = Sin[18 * N + li]; dl3 = Sin[19 * N + li]; dl4 = Sin[20 * N + li]; dl5 = Sin[21 * N + li]; }
@@ -1400,7 +1400,7 @@ __global__ void __launch_bounds__(64 * kQuadWPB, SHARED ? 1 : WPS) quadx_m0_env_
       // (SPARE: every lane, every launch -- 16 B a lane in Hover, 80 B in Waypoints that only the restarting lanes use. Requested
       //  by those lanes alone, once their flags are here, the words came from HBM and not from the cache the state groups of the
       //  previous launch still sit in: 2.8 us in front of the reset, as long as generating them had taken -- profiles/r05)
-      const bool need_sp = SPARE || ROLLOUT || in11 || op == 1 || K.autoreset == PF_AUTORESET_SAME_STEP ||
+      const bool need_sp = SPARE || ROLLOUT || in11 || op == OP_RESET || K.autoreset == PF_AUTORESET_SAME_STEP ||
                            (__float_as_int(gi.y) & (PF_F_TERMINATED | PF_F_TRUNCATED)) != 0;
       if (need_sp) {
         const float4 gk = SPARE ? gs7 : (in11 ? cm4 : (MODES ? cm0 : Sin[(size_t)7 * N + li]));
@@ -1408,7 +1408,7 @@ __global__ void __launch_bounds__(64 * kQuadWPB, SHARED ? 1 : WPS) quadx_m0_env_
         // pf_env_reset of EVERY lane (null mask): the spares in the state are not trusted -- a state buffer may come from another
         // context (other seed, lane offset, spawn pose, settle length, dome, number of targets) with bit 31 set; this reset generates
         // on the spot and the refill below prepares fresh ones (include/pyflyt_amd.h at pf_env_reset)
-        if (SPARE && op == 1 && mask == nullptr) rkw &= ~kSpareValid;
+        if (SPARE && op == OP_RESET && mask == nullptr) rkw &= ~kSpareValid;
         if (SPARE) {
           spv.z = gk.x; spv.vz = gk.y; spv.thr = gk.z;
           // (the targets' four groups behind the int group: in front of it, with the state groups, they cost the Waypoints launch
@@ -1423,7 +1423,7 @@ __global__ void __launch_bounds__(64 * kQuadWPB, SHARED ? 1 : WPS) quadx_m0_env_
       }
     }
     if (NOISE == PF_NOISE_PHILOX) {
-      if (op == 0) zn = normal8(philox4x32(K.seed_lo, K.seed_hi, (uint32_t)(lane0 + li), rng_ctr, 0u, 0u));
+      if (op == OP_STEP) zn = normal8(philox4x32(K.seed_lo, K.seed_hi, (uint32_t)(lane0 + li), rng_ctr, 0u, 0u));
     }
     PF_STAMP(2);  // (the step's Philox call done)
     V.p = v3{g0.x, g0.y, g0.z}; new_dist = g0.w;
@@ -1487,10 +1487,10 @@ __global__ void __launch_bounds__(64 * kQuadWPB, SHARED ? 1 : WPS) quadx_m0_env_
   bool term = (flags & PF_F_TERMINATED) != 0, trunc = (flags & PF_F_TRUNCATED) != 0;
 
   bool active;
-  if (op == 1) active = (mask == nullptr) || (mask[li] != 0);
+  if (op == OP_RESET) active = (mask == nullptr) || (mask[li] != 0);
   else active = true;
   active = active && valid;
-  if (SHARED && op == 1) active = widen_to_world(active, tid, apw) && valid;  // a mask that names some agents of a world resets the world
+  if (SHARED && op == OP_RESET) active = widen_to_world(active, tid, apw) && valid;  // a mask that names some agents of a world resets the world
 
   float act0 = 0.f, act1 = 0.f, act2 = 0.f, act3 = 0.f;
   float reward = 0.0f;
@@ -1507,14 +1507,8 @@ __global__ void __launch_bounds__(64 * kQuadWPB, SHARED ? 1 : WPS) quadx_m0_env_
     ytg[0] = ytg[1]; ytg[1] = ytg[2]; ytg[2] = ytg[3];
     n_left -= 1;
   };
-  // One wave per workgroup: LDS operations of a wave execute in issue order, so the row writes only
-  // have to be retired (lgkmcnt) and not reordered by the compiler before the tile is read back --
-  // no s_barrier and, unlike __syncthreads(), no wait on outstanding global stores.
-  auto lds_sync = [&]() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0), vmcnt/expcnt untouched
-    __builtin_amdgcn_wave_barrier();
-  };
+  // (through a lambda of its own: calling lds_sync_wave directly from the lambdas below moved the Hover kernel's register allocation)
+  auto lds_sync = [&]() { lds_sync_wave(); };
   // What a resetting lane draws, generated cooperatively: settle_ticks motor-noise normals (3 Philox calls per lane, stream 1) and,
   // in the Waypoints task, the targets (waypoint_handler.py:53-89: 3 calls, 4 with yaw targets, stream 2, and per target two sine /
   // cosine pairs). Instead of the two or three resetting lanes of a wave walking through their calls serially while the other lanes
@@ -1926,20 +1920,6 @@ __global__ void __launch_bounds__(64 * kQuadWPB, SHARED ? 1 : WPS) quadx_m0_env_
     }
   };
   const bool wave_all = __all(active || !valid);
-  auto flush_tile = [&](float* out) {
-    lds_sync();
-    if (wave_all) {
-      const int rows = min(LPW, n - wave_base);
-      const int total = rows * D;
-      float* g = out + (size_t)wave_base * D;
-      stream_tile(tile, g, total, tid);
-    } else if (active) {  // partial (masked reset): this lane writes its own row
-      float* g = out + (size_t)lane * D;
-      const float* row = tile + tid * D;
-      for (int k = 0; k < D; ++k) g[k] = row[k];
-    }
-    lds_sync();
-  };
 
   const int KS = ROLLOUT ? k_steps : 1;
   float4 a_nxt = float4{0.f, 0.f, 0.f, 0.f};
@@ -1948,7 +1928,7 @@ __global__ void __launch_bounds__(64 * kQuadWPB, SHARED ? 1 : WPS) quadx_m0_env_
   const size_t toff = ROLLOUT ? (size_t)it * N : (size_t)0;  // this step's slot in the trajectory buffers (lanes)
   // ---------------------------------------------------------------- reset (NEXT_STEP / explicit)
   bool do_reset;
-  if (op == 1) do_reset = active;
+  if (op == OP_RESET) do_reset = active;
   else do_reset = (K.autoreset == PF_AUTORESET_NEXT_STEP) && (term || trunc) && active;
   act0 = act1 = act2 = act3 = 0.f;
   reward = 0.0f;
@@ -1958,18 +1938,18 @@ __global__ void __launch_bounds__(64 * kQuadWPB, SHARED ? 1 : WPS) quadx_m0_env_
   //  the last of the prologue's, and a lone wave of a 4 096-lane batch waited 0.45 us for it. The same word in every lane: made
   //  wave-uniform for the control flow below)
   const uint32_t call0_u = SPARE ? (uint32_t)__builtin_amdgcn_readfirstlane((int)call0) : 0u;
-  refill_spares(op == 1 || ((call0_u + (uint32_t)it) % kSpareEvery) == kSpareEvery - 1u);
+  refill_spares(op == OP_RESET || ((call0_u + (uint32_t)it) % kSpareEvery) == kSpareEvery - 1u);
   PF_STAMP(4);  // (NEXT_STEP resets done)
 
   // ---------------------------------------------------------------- the env step
-  const bool stepping = active && !was_reset && op == 0;
+  const bool stepping = active && !was_reset && op == OP_STEP;
   float sp0 = 0.f, sp1 = 0.f, sp2 = 0.f, sp3 = 0.f;
   float4 a_roll = float4{0.f, 0.f, 0.f, 0.f};
   if (ROLLOUT) {  // this step's action for every lane: given sequence (prefetched one step ahead) or sampled
     if (GIVEN) {
       a_roll = a_nxt;
       if (it + 1 < KS) a_nxt = reinterpret_cast<const float4*>(B.actions)[toff + N + li];
-    } else {  // == sample_actions_kernel(step0 + it): same Philox key, same arithmetic
+    } else {  // == sample_actions_kernel(step0 + it): a copy of sampled_action4 (that call moved the code of the noise-free rollouts)
       f4 u = uniform4(philox4x32(K.seed_lo, K.seed_hi, (uint32_t)(lane0 + li), step0 + (uint32_t)it, 0u, 3u));
       a_roll = float4{fmaf(K.act_span[0], u.a, K.act_lo[0]), fmaf(K.act_span[1], u.b, K.act_lo[1]),
                       fmaf(K.act_span[2], u.c, K.act_lo[2]), fmaf(K.act_span[3], u.d, K.act_lo[3])};
@@ -2159,11 +2139,10 @@ __global__ void __launch_bounds__(64 * kQuadWPB, SHARED ? 1 : WPS) quadx_m0_env_
     if (__any(same)) {
       if (B.final_obs != nullptr) {  // terminal observation, before the state is re-initialised
         if (active) write_obs_row();
-        flush_tile(B.final_obs + toff * D);
+        flush_obs_tile(tile, B.final_obs + toff * D, D, LPW, n, wave_base, tid, wave_all, active);
       }
       if (B.final_info != nullptr && same) {  // gymnasium's final_info: the episode's flags / targets left, pre-reset
-        B.final_info[2 * (toff + li) + 0] = (flags & ~(PF_F_TERMINATED | PF_F_TRUNCATED | PF_F_CONTACT)) | (term ? PF_F_TERMINATED : 0) |
-                                            (trunc ? PF_F_TRUNCATED : 0) | (V.contact_now ? PF_F_CONTACT : 0);
+        B.final_info[2 * (toff + li) + 0] = done_flags(flags, term, trunc, V.contact_now);
         B.final_info[2 * (toff + li) + 1] = n_left - (pop_pending ? 1 : 0);
       }
       do_resets(same);
@@ -2175,13 +2154,12 @@ __global__ void __launch_bounds__(64 * kQuadWPB, SHARED ? 1 : WPS) quadx_m0_env_
   PF_STAMP(6);
   if (active) write_obs_row();
   PF_STAMP(7);  // (observation row computed and written to LDS)
-  flush_tile(B.obs + toff * D);
+  flush_obs_tile(tile, B.obs + toff * D, D, LPW, n, wave_base, tid, wave_all, active);
   PF_STAMP(8);  // (observation tile stores issued)
   if (active) {
     if (pop_pending) { pop_target(); pop_pending = false; }
-    flags = (flags & ~(PF_F_TERMINATED | PF_F_TRUNCATED | PF_F_CONTACT)) | (term ? PF_F_TERMINATED : 0) |
-            (trunc ? PF_F_TRUNCATED : 0) | (V.contact_now ? PF_F_CONTACT : 0);
-    if (op == 0) {  // a NEXT_STEP reset call reports (r=0, not done), gymnasium's convention
+    flags = done_flags(flags, term, trunc, V.contact_now);
+    if (op == OP_STEP) {  // (a copy of step_outputs: that call moved this kernel's register allocation)
       B.reward[toff + li] = out_reward;
       B.terminated[toff + li] = out_term ? 1 : 0;
       B.truncated[toff + li] = out_trunc ? 1 : 0;
@@ -2195,7 +2173,7 @@ __global__ void __launch_bounds__(64 * kQuadWPB, SHARED ? 1 : WPS) quadx_m0_env_
   if (ROLLOUT && NOISE == PF_NOISE_PHILOX && it + 1 < KS)
     zn = normal8(philox4x32(K.seed_lo, K.seed_hi, (uint32_t)(lane0 + li), rng_ctr, 0u, 0u));
   }  // for it
-  if (SPARE && op == 0 && tid == 0) launch_ctr[kCtrStride * blockIdx.x] = call0 + (uint32_t)KS;
+  if (SPARE && op == OP_STEP && tid == 0) launch_ctr[kCtrStride * blockIdx.x] = call0 + (uint32_t)KS;
   if (active) {  // the persistent state goes back to HBM once per launch
     Sout[0 * N + li] = float4{V.p.x, V.p.y, V.p.z, new_dist};
     Sout[1 * N + li] = float4{V.q.x, V.q.y, V.q.z, V.q.w};

@@ -168,7 +168,8 @@ struct PadWorld {
 constexpr int kRlGroups = Rocket::GROUPS + 2;
 constexpr int kRlActionDim = 7;
 // the action box (rocket_base_env.py:95-119): low (-1, -1, -1, 0, 0, -1, -1), high 1 -- seven wide, so not pf_params.action_low / high
-PF_DEV float rl_action_low(const int j) { return (j == 3 || j == 4) ? 0.0f : -1.0f; }
+constexpr float kRlActionLow[kRlActionDim] = {-1.0f, -1.0f, -1.0f, 0.0f, 0.0f, -1.0f, -1.0f};
+constexpr float kRlActionHigh[kRlActionDim] = {1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f};
 
 template <>
 __global__ void __launch_bounds__(kWave) env_kernel<Rocket, PF_TASK_ROCKET_LANDING, kRuntimeMode>(
@@ -207,9 +208,7 @@ __global__ void __launch_bounds__(kWave) env_kernel<Rocket, PF_TASK_ROCKET_LANDI
   float obs_pad = pad_contact;                                   // ... as the last compute_state saw it
 
   Noise nz;
-  nz.mode = P.noise_mode; nz.n = n; nz.lane = (int)li;
-  nz.k0 = (uint32_t)P.seed; nz.k1 = (uint32_t)(P.seed >> 32);
-  nz.c0 = (uint32_t)(lane0 + li); nz.nmot = (float)P.n_motors; nz.cached = -1; nz.xi = nullptr;
+  nz.init(P, n, li, lane0);
 
   bool active = false, do_reset = false, wave_all = false;
   float sp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -322,23 +321,6 @@ __global__ void __launch_bounds__(kWave) env_kernel<Rocket, PF_TASK_ROCKET_LANDI
     for (int a = 0; a < Rocket::AUX; ++a) row[k++] = aux[a];
     row[k++] = obs_pad;
   };
-  auto lds_sync = [&]() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-    __builtin_amdgcn_wave_barrier();
-  };
-  auto flush_tile = [&](float* out) {
-    lds_sync();
-    if (wave_all) {
-      const int rows = min(kWave, n - wave_base);
-      stream_tile(tile, out + (size_t)wave_base * D, rows * D, tid);
-    } else if (active) {  // partial (masked reset): this lane writes its own row
-      float* g = out + (size_t)lane * D;
-      const float* row = tile + tid * D;
-      for (int k = 0; k < D; ++k) g[k] = row[k];
-    }
-    lds_sync();
-  };
 
   const int n_env_steps = roll_steps > 0 ? roll_steps : 1;
   for (int ks = 0; ks < n_env_steps; ++ks) {
@@ -363,11 +345,7 @@ __global__ void __launch_bounds__(kWave) env_kernel<Rocket, PF_TASK_ROCKET_LANDI
 
     float a[kRlActionDim] = {0, 0, 0, 0, 0, 0, 0};
     if (roll_steps > 0 && B.actions == nullptr) {  // pf_sample_actions' draw for (lane, step0 + ks)
-      const f4 u0 = uniform4(philox4x32((uint32_t)P.seed, (uint32_t)(P.seed >> 32), (uint32_t)(lane0 + li), step0 + (uint32_t)ks, 0u, 3u));
-      const f4 u1 = uniform4(philox4x32((uint32_t)P.seed, (uint32_t)(P.seed >> 32), (uint32_t)(lane0 + li), step0 + (uint32_t)ks, 1u, 3u));
-      const float u[kRlActionDim] = {u0.a, u0.b, u0.c, u0.d, u1.a, u1.b, u1.c};
-#pragma unroll
-      for (int j = 0; j < kRlActionDim; ++j) a[j] = fmaf(1.0f - rl_action_low(j), u[j], rl_action_low(j));
+      sampled_action7<true>((uint32_t)P.seed, (uint32_t)(P.seed >> 32), (uint32_t)(lane0 + li), step0 + (uint32_t)ks, kRlActionLow, kRlActionHigh, a);
       if (B.actions_out != nullptr && valid)
 #pragma unroll
         for (int j = 0; j < kRlActionDim; ++j) B.actions_out[(toff + li) * kRlActionDim + j] = a[j];
@@ -397,8 +375,7 @@ __global__ void __launch_bounds__(kWave) env_kernel<Rocket, PF_TASK_ROCKET_LANDI
       if (V.b.nonfinite()) flags |= PF_F_NONFINITE;  // (the base state words; NaN / Inf guard as in the other env kernels)
     }
     auto flags_word = [&]() {
-      return (flags & ~(PF_F_TERMINATED | PF_F_TRUNCATED | PF_F_CONTACT | PF_F_PAD_CONTACT)) | (term ? PF_F_TERMINATED : 0) |
-             (trunc ? PF_F_TRUNCATED : 0) | (V.b.contact_now ? PF_F_CONTACT : 0) | (pad_contact != 0.0f ? PF_F_PAD_CONTACT : 0);
+      return done_flags(flags & ~PF_F_PAD_CONTACT, term, trunc, V.b.contact_now) | (pad_contact != 0.0f ? PF_F_PAD_CONTACT : 0);
     };
     // SAME_STEP auto-reset (rare path): terminal observation and info, then the reset with its settle steps in this launch
     if (P.autoreset == PF_AUTORESET_SAME_STEP) {
@@ -406,7 +383,7 @@ __global__ void __launch_bounds__(kWave) env_kernel<Rocket, PF_TASK_ROCKET_LANDI
       if (__any(same)) {
         if (B.final_obs != nullptr) {
           if (active) write_obs_row();
-          flush_tile(B.final_obs + toff * D);
+          flush_obs_tile(tile, B.final_obs + toff * D, D, kWave, n, wave_base, tid, wave_all, active);
         }
         if (B.final_info != nullptr && same) {
           B.final_info[2 * (toff + li) + 0] = flags_word();
@@ -422,7 +399,7 @@ __global__ void __launch_bounds__(kWave) env_kernel<Rocket, PF_TASK_ROCKET_LANDI
     if (active && settling) rng_ctr += 1;  // end_reset's compute_state (rocket_base_env.py:216-223)
 
     if (active) write_obs_row();
-    flush_tile(B.obs + toff * D);
+    flush_obs_tile(tile, B.obs + toff * D, D, kWave, n, wave_base, tid, wave_all, active);
     if (active) {
       flags = flags_word();
       if (ks == n_env_steps - 1) {  // the state goes back to HBM once per launch
@@ -430,11 +407,7 @@ __global__ void __launch_bounds__(kWave) env_kernel<Rocket, PF_TASK_ROCKET_LANDI
         Sout[(size_t)(Rocket::GROUPS + 0) * N + li] = float4{act[0], act[1], act[2], act[3]};
         Sout[(size_t)(Rocket::GROUPS + 1) * N + li] = float4{act[4], act[5], act[6], 0.0f};
       }
-      if (op == OP_STEP) {  // a NEXT_STEP reset call reports (r=0, not done), gymnasium's convention
-        B.reward[toff + li] = out_reward;
-        B.terminated[toff + li] = out_term ? 1 : 0;
-        B.truncated[toff + li] = out_trunc ? 1 : 0;
-      }
+      step_outputs(B, op, toff, li, out_reward, out_term, out_trunc);
     }
   }
 }
@@ -444,11 +417,10 @@ __global__ void __launch_bounds__(256) sample_actions7_kernel(const pf_params P,
                                                               const uint32_t step_index) {
   const int lane = blockIdx.x * 256 + threadIdx.x;
   if (lane >= n) return;
-  const f4 u0 = uniform4(philox4x32((uint32_t)P.seed, (uint32_t)(P.seed >> 32), (uint32_t)(lane0 + lane), step_index, 0u, 3u));
-  const f4 u1 = uniform4(philox4x32((uint32_t)P.seed, (uint32_t)(P.seed >> 32), (uint32_t)(lane0 + lane), step_index, 1u, 3u));
-  const float u[kRlActionDim] = {u0.a, u0.b, u0.c, u0.d, u1.a, u1.b, u1.c};
+  float a[kRlActionDim];
+  sampled_action7<true>((uint32_t)P.seed, (uint32_t)(P.seed >> 32), (uint32_t)(lane0 + lane), step_index, kRlActionLow, kRlActionHigh, a);
 #pragma unroll
-  for (int j = 0; j < kRlActionDim; ++j) actions[(size_t)lane * kRlActionDim + j] = fmaf(1.0f - rl_action_low(j), u[j], rl_action_low(j));
+  for (int j = 0; j < kRlActionDim; ++j) actions[(size_t)lane * kRlActionDim + j] = a[j];
 }
 
 }  // namespace pf

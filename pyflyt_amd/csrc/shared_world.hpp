@@ -12,13 +12,6 @@ namespace pf {
 PF_DEV bool slot_contact(const float x) { return (((int)x) & 1) != 0; }
 PF_DEV bool slot_at_rest(const float x) { return ((int)x) >= 2; }
 
-
-PF_DEV void lds_sync_wave() {  // one wave per workgroup: LDS traffic ordered, no s_barrier needed
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_s_waitcnt(0xc07f);
-  __builtin_amdgcn_wave_barrier();
-}
-
 // A reset mask that selects some agents of a shared world selects the world: the agents of a world are reset together (their
 // lanes exchange data inside the kernels, and the reference rebuilds the whole world: ma_quadx_base_env.py:206-241). Every lane
 // of the wave must call this (it is a ballot).

@@ -217,6 +217,36 @@ PF_DEV void stream_tile(const float* tile, float* g, int total, int tid, int lan
   for (int i = (n4 << 2) + tid; i < total; i += lanes) __builtin_nontemporal_store(tile[i], &g[i]);
 }
 
+// One wave per workgroup: LDS operations of a wave execute in issue order, so the row writes only have to be retired (lgkmcnt)
+// and not reordered by the compiler before the tile is read back -- no s_barrier and, unlike __syncthreads(), no wait on
+// outstanding global stores.
+PF_DEV void lds_sync_wave() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0), vmcnt/expcnt untouched
+  __builtin_amdgcn_wave_barrier();
+}
+
+// An env kernel's observation tile (rows written to LDS, one per lane) -> `out` [n][D]: the whole wave's rows with full-width
+// stores, or, in a partial wave (masked reset), each active lane its own row. `rows_per_wave`: the lanes a wave serves.
+// (The helpers of an env step take the caller's variables by reference: inlined, they then read them where the kernels' own
+// copies of this code did, and the kernels compile as they did -- passed by value, the same expressions came out in another
+// register allocation.)
+PF_DEV void flush_obs_tile(const float* const& tile, float* out, const int& D, const int rows_per_wave, const int& n, const int& wave_base,
+                           const int& tid, const bool& wave_all, const bool& active) {
+  lds_sync_wave();
+  if (wave_all) {
+    const int rows = min(rows_per_wave, n - wave_base);
+    const int total = rows * D;
+    float* g = out + (size_t)wave_base * D;
+    stream_tile(tile, g, total, tid);
+  } else if (active) {
+    float* g = out + (size_t)(wave_base + tid) * D;
+    const float* row = tile + tid * D;
+    for (int k = 0; k < D; ++k) g[k] = row[k];
+  }
+  lds_sync_wave();
+}
+
 // (r05, measured and dropped: every LDS read of the tile issued ahead of the first store -- an unrolled, predicated copy of up to ten
 //  rounds -- instead of this loop's read / wait / store per round: Hover 9.65 -> 9.91 us, QuadX-Waypoints 16.65 -> 17.3, Fixedwing-
 //  Waypoints 20.63 -> 21.59 on one box, profiles/tools/r05/g21.sh. The phase traces' 0.36-0.6 us "obs stores issued" is the issue of

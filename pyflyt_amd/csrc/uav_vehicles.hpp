@@ -20,6 +20,12 @@ struct Noise {
   float nmot;
   int cached;
   f8 z;
+  // a lane's source: pf_params' mode and seed, keyed by the lane's global index (by reference: see flush_obs_tile)
+  PF_DEV void init(const pf_params& P, const int& n_, const size_t& li, const uint64_t& lane0) {
+    mode = P.noise_mode; n = n_; lane = (int)li;
+    k0 = (uint32_t)P.seed; k1 = (uint32_t)(P.seed >> 32);
+    c0 = (uint32_t)(lane0 + li); nmot = (float)P.n_motors; cached = -1; xi = nullptr;
+  }
   PF_DEV void begin_event(uint32_t ctr, uint32_t strm, const float* inj) {
     c1 = ctr; stream = strm; xi = inj; cached = -1;
   }
@@ -38,6 +44,51 @@ struct Noise {
     return pick4(u, (uint32_t)flat & 3u);
   }
 };
+
+// ------------------------------------------------------------------------------------------
+// The gymnasium step protocol that every env kernel follows. (The caller's variables go in by reference: see flush_obs_tile.)
+enum { OP_STEP = 0, OP_RESET = 1 };
+
+// The flags word's done bits as the step left them: terminated, truncated, contact after the last tick. The same word is the
+// state's and gymnasium's final_info; a task with bits of its own clears them in `flags` and ORs them in at the call site.
+PF_DEV int done_flags(const int& flags, const bool& term, const bool& trunc, const bool& contact) {
+  return (flags & ~(PF_F_TERMINATED | PF_F_TRUNCATED | PF_F_CONTACT)) | (term ? PF_F_TERMINATED : 0) | (trunc ? PF_F_TRUNCATED : 0) |
+         (contact ? PF_F_CONTACT : 0);
+}
+
+// A step call's reward / terminated / truncated at trajectory slot toff + li. A reset call writes none of them, and a lane that a
+// NEXT_STEP step call resets reports (r = 0, not done): gymnasium's convention.
+PF_DEV void step_outputs(const pf_buffers& B, const int& op, const size_t& toff, const size_t& li, const float& reward, const bool& term,
+                         const bool& trunc) {
+  if (op == OP_STEP) {
+    B.reward[toff + li] = reward;
+    B.terminated[toff + li] = term ? 1 : 0;
+    B.truncated[toff + li] = trunc ? 1 : 0;
+  }
+}
+
+// pf_sample_actions' draw for (global lane, step): Philox stream 3 scaled into the action box, lo + width * u. A rollout that samples
+// its actions on the device draws through these (or, in the QuadX fast and dogfight kernels, through a marked copy), so that its
+// actions are pf_sample_actions'. `box` is the box's width (the fast kernels keep high - low in their constants) or, HIGH, its
+// high end (pf_params.action_high).
+template <bool HIGH>
+PF_DEV float box_point(const float* lo, const float* box, const int j, const float u) { return fmaf(HIGH ? box[j] - lo[j] : box[j], u, lo[j]); }
+template <bool HIGH>
+PF_DEV float4 sampled_action4(const uint32_t k0, const uint32_t k1, const uint32_t lane, const uint32_t step, const float* lo, const float* box) {
+  const f4 u = uniform4(philox4x32(k0, k1, lane, step, 0u, 3u));
+  return float4{box_point<HIGH>(lo, box, 0, u.a), box_point<HIGH>(lo, box, 1, u.b), box_point<HIGH>(lo, box, 2, u.c),
+                box_point<HIGH>(lo, box, 3, u.d)};
+}
+// seven wide (Rocket-Landing): call 0's four uniforms, then call 1's first three
+template <bool HIGH>
+PF_DEV void sampled_action7(const uint32_t k0, const uint32_t k1, const uint32_t lane, const uint32_t step, const float* lo, const float* box,
+                            float a[7]) {
+  const f4 u0 = uniform4(philox4x32(k0, k1, lane, step, 0u, 3u));
+  const f4 u1 = uniform4(philox4x32(k0, k1, lane, step, 1u, 3u));
+  const float u[7] = {u0.a, u0.b, u0.c, u0.d, u1.a, u1.b, u1.c};
+#pragma unroll
+  for (int j = 0; j < 7; ++j) a[j] = box_point<HIGH>(lo, box, j, u[j]);
+}
 
 // abstractions/pid.py:70-94 for one component
 PF_DEV float pid1(float kp, float ki, float kd, float lim, float T, float invT, float& I, float& E, float st, float sp) {
