@@ -170,7 +170,7 @@ class Aviary:
         self.start_pos, self.start_orn = start_pos, start_orn
         self.updates_per_step = P.ticks_per_control  # core/aviary.py:288-289
         self.step_period = 1.0 / (self.physics_hz / P.ticks_per_control)
-        self._sp_dim = 7 if drone_type == "rocket" else 4  # rocket.py:228
+        self._sp_dim = self.engine._sp_dim(0)
         self.setpoints = torch.zeros(self.num_drones, self._sp_dim, dtype=torch.float32, device=self.device)
         self.reset()
 
@@ -184,7 +184,7 @@ class Aviary:
         self.engine.modes = None   # drone.reset() -> set_mode(0) on every drone
         self.engine.aviary_reset(self._start_pose)
         self.mode = 0
-        self._set_sp_dim(7 if self.drone_type == "rocket" else 4)
+        self._set_sp_dim(self.engine._sp_dim(0))
         self.setpoints.zero_()
         self._contact_acc = None
         self._controller = None
@@ -265,7 +265,7 @@ class Aviary:
         lo, hi = {"quadx": (-1, 7), "fixedwing": (-1, 0), "rocket": (0, 0)}[self.drone_type]
         if mode < lo or mode > hi:
             raise ValueError(f"`mode` must be between {lo} and {hi}, got {mode}.")  # quadx.py:260-263
-        self._set_sp_dim(7 if self.drone_type == "rocket" else (6 if (self.drone_type == "fixedwing" and mode == -1) else 4))
+        self._set_sp_dim(self.engine._sp_dim(mode))
         self.engine.aviary_set_mode(mode, self.setpoints)
         self.mode = mode
         self._base_sp_dim = self._sp_dim

@@ -109,9 +109,7 @@ __global__ void __launch_bounds__(kWave) env_kernel(const pf_params P, const pf_
 
   static_assert(kWave * kMaxObs >= kContactSlotFloats, "the contact solver's LDS regions alias the observation tile: at least one worst-case region");
   VEH V;
-  V.b.pdev = Pdev;
-  V.b.cws = (lds_fptr)tile;  // (idle during the physics ticks)
-  V.b.contact_regions(P, kWave * kMaxObs);
+  bind_contact(V, P, Pdev, tile, kWave * kMaxObs);  // (the tile is idle during the physics ticks)
   V.bind(ktab);
   if (TASK == PF_TASK_MA_HOVER && P.agents_per_world > 1) { V.b.wpose_ = wpose; V.b.wvel_ = wvel; V.b.wtid = tid; V.b.wA = P.agents_per_world; }
   SideBlock tg;
@@ -465,15 +463,10 @@ namespace pf {
 template <class VEH>
 __global__ void settle_template_kernel(const pf_params P, float4* tmpl, const pf_params* __restrict__ Pdev) {
   __shared__ __attribute__((aligned(16))) float ktab[VEH::TABLE_FLOATS];
-  VEH::fill_table(ktab, Pdev, threadIdx.x);
-  __syncthreads();
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
   __shared__ __attribute__((aligned(16))) float cws[kAviaryContactFloats];
   VEH V;
-  V.b.pdev = Pdev;
-  V.b.cws = (lds_fptr)cws;
-  V.b.contact_regions(P, kAviaryContactFloats);
-  V.bind(ktab);
+  bind_vehicle(V, P, Pdev, ktab, cws, kAviaryContactFloats);
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
   float sp[6] = {0, 0, 0, 0, 0, 0};
   V.reset(P, nullptr, sp);
   V.set_mode(P.flight_mode, sp);
@@ -485,36 +478,21 @@ __global__ void settle_template_kernel(const pf_params P, float4* tmpl, const pf
 }
 
 // ------------------------------------------------------------------ Aviary-level kernels
+// Each one: bind the vehicle to its LDS, load the lane, its own loop, store the lane, write the outputs (helpers: uav_vehicles.hpp).
 template <class VEH>
 __global__ void __launch_bounds__(kWave) aviary_reset_kernel(const pf_params P, const pf_buffers B, const int n,
                                                              const float* pose) {
   const int lane = blockIdx.x * kWave + threadIdx.x;
   if (lane >= n) return;
+  const size_t li = lane;
   VEH V;
-  V.b.pdev = nullptr;  // (no tick in this kernel)
-  V.b.cws = nullptr;
+  bind_no_tick(V);
   float sp[8];
-  V.reset(P, pose ? pose + (size_t)lane * 7 : nullptr, sp, B.start_vel ? B.start_vel + (size_t)lane * 3 : nullptr);
-  float4* S = reinterpret_cast<float4*>(B.state);
-  V.store(S, (size_t)n, (size_t)lane, /*mode=*/7, INFINITY, int4{0, 0, 0, 0});
-  if (B.out_state) {
-    float* o = B.out_state + (size_t)lane * 12;
-    o[0] = V.b.wb.x; o[1] = V.b.wb.y; o[2] = V.b.wb.z; o[3] = V.b.rpy.x; o[4] = V.b.rpy.y; o[5] = V.b.rpy.z;
-    o[6] = V.b.vb.x; o[7] = V.b.vb.y; o[8] = V.b.vb.z; o[9] = V.b.p.x; o[10] = V.b.p.y; o[11] = V.b.p.z;
-  }
-  if (B.out_link_pos) {
-#pragma unroll
-    for (int k = 0; k < VEH::WIND_LINKS; ++k) {
-      v3 lp = V.link_pos(P, k);
-      float* o = B.out_link_pos + ((size_t)lane * VEH::WIND_LINKS + k) * 3;
-      o[0] = lp.x; o[1] = lp.y; o[2] = lp.z;
-    }
-  }
-  if (B.out_aux) {
-    float aux[VEH::AUX];
-    V.aux(aux);
-    for (int k = 0; k < VEH::AUX; ++k) B.out_aux[(size_t)lane * VEH::AUX + k] = aux[k];
-  }
+  V.reset(P, pose ? pose + li * 7 : nullptr, sp, B.start_vel ? B.start_vel + li * 3 : nullptr);
+  V.store(reinterpret_cast<float4*>(B.state), (size_t)n, li, /*mode=*/7, INFINITY, int4{0, 0, 0, 0});
+  if (B.out_state) write_out_state(V, B, li);
+  if (B.out_link_pos) write_out_link_pos(V, P, B, li);
+  if (B.out_aux) write_out_aux(V, B, li);
 }
 
 template <class VEH>
@@ -523,8 +501,7 @@ __global__ void __launch_bounds__(kWave) aviary_set_mode_kernel(const pf_params 
   const int lane = blockIdx.x * kWave + threadIdx.x;
   if (lane >= n) return;
   VEH V;
-  V.b.pdev = nullptr;  // (no tick in this kernel)
-  V.b.cws = nullptr;
+  bind_no_tick(V);
   float nd;
   int4 ints;
   // load everything (old mode 7 == all groups), re-initialise the controllers, store everything
@@ -547,33 +524,22 @@ __global__ void __launch_bounds__(kWave) aviary_step_kernel(const pf_params P, c
                                                             const uint64_t lane0, const int n_steps,
                                                             const pf_params* __restrict__ Pdev) {
   __shared__ __attribute__((aligned(16))) float ktab[VEH::TABLE_FLOATS];
-  VEH::fill_table(ktab, Pdev, threadIdx.x);
-  __syncthreads();
+  __shared__ __attribute__((aligned(16))) float cws[kAviaryContactFloats];  // the contact solver's LDS regions (uav_vehicles.hpp)
+  VEH V;
+  bind_vehicle(V, P, Pdev, ktab, cws, kAviaryContactFloats);
   const int lane = blockIdx.x * kWave + threadIdx.x;
   if (lane >= n) return;
   const size_t li = lane, N = n;
-  __shared__ __attribute__((aligned(16))) float cws[kAviaryContactFloats];  // the contact solver's LDS regions (uav_vehicles.hpp)
-  VEH V;
-  V.b.pdev = Pdev;
-  V.b.cws = (lds_fptr)cws;
-  V.b.contact_regions(P, kAviaryContactFloats);
-  V.bind(ktab);
-  float nd;
+  int mode;
+  float nd, sp[8];
   int4 ints;
-  const int mode = B.modes ? B.modes[li] : P.flight_mode;
-  V.load(reinterpret_cast<const float4*>(B.state), N, li, mode, nd, ints);
-  V.b.rpy = euler_from_quat_fast(V.b.q);
-  uint32_t rng_ctr = (uint32_t)ints.z;
+  uint32_t rng_ctr;
   Noise nz;
-  nz.init(P, n, li, lane0);
-  float sp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  const int spn = P.vehicle == PF_ROCKET ? 7 : ((P.vehicle == PF_FIXEDWING && mode == -1) ? 6 : 4);
-#pragma unroll
-  for (int k = 0; k < 8; ++k)
-    if (k < spn) sp[k] = B.setpoints[li * spn + k];
+  load_lane(V, P, B, n, li, lane0, mode, nd, ints, rng_ctr, nz);
+  read_setpoints(P, B, li, mode, sp);
+  const int ratio = lane_ctrl_ratio(B, li, 0);
+  const bool armed = lane_armed(B, li);
   bool contact = false;
-  const int ratio = B.ctrl_ratio ? B.ctrl_ratio[li] : 0;
-  const bool armed = !B.armed || B.armed[li] != 0;  // aviary.py:423-438
   for (int s = 0; s < n_steps; ++s) {
     nz.begin_event(rng_ctr, 0u, B.xi ? B.xi + (size_t)s * P.ticks_per_control * N : nullptr);
     if (!armed) {  // no control, no forces, no state read-back: gravity only (aviary.py:510-521 skip it, Bullet does not)
@@ -596,19 +562,9 @@ __global__ void __launch_bounds__(kWave) aviary_step_kernel(const pf_params P, c
     rng_ctr += 1;
     contact = V.b.contact_step;
   }
-  int flags = (ints.y & ~PF_F_CONTACT) | (V.b.contact_now ? PF_F_CONTACT : 0);
-  V.store(reinterpret_cast<float4*>(B.state), N, li, mode, nd, int4{ints.x, flags, (int)rng_ctr, ints.w});
-  if (B.out_state && armed) {
-    float4* o = reinterpret_cast<float4*>(B.out_state + li * 12);
-    o[0] = float4{V.b.wb.x, V.b.wb.y, V.b.wb.z, V.b.rpy.x};
-    o[1] = float4{V.b.rpy.y, V.b.rpy.z, V.b.vb.x, V.b.vb.y};
-    o[2] = float4{V.b.vb.z, V.b.p.x, V.b.p.y, V.b.p.z};
-  }
-  if (B.out_aux && armed) {
-    float aux[VEH::AUX];
-    V.aux(aux);
-    for (int k = 0; k < VEH::AUX; ++k) B.out_aux[li * VEH::AUX + k] = aux[k];
-  }
+  store_lane(V, B, n, li, mode, nd, ints, rng_ctr);
+  if (B.out_state && armed) write_out_state(V, B, li);
+  if (B.out_aux && armed) write_out_aux(V, B, li);
   if (B.out_contact) B.out_contact[li] = contact ? 1 : 0;
 }
 
@@ -626,38 +582,27 @@ __global__ void __launch_bounds__(kWave) aviary_world_step_kernel(const pf_param
                                                                   const uint64_t lane0, const int n_steps,
                                                                   const pf_params* __restrict__ Pdev) {
   __shared__ __attribute__((aligned(16))) float ktab[VEH::TABLE_FLOATS];
-  VEH::fill_table(ktab, Pdev, threadIdx.x);
-  __syncthreads();
+  __shared__ __attribute__((aligned(16))) float cws[kAviaryContactFloats];  // the contact solvers' LDS regions (floor and pair stage)
+  __shared__ float wpose[kWave * 8];                                         // each lane's pose and contact bit, once per tick
+  __shared__ float wvel[kWave * kPairVelStride];                             // ... and its new velocities for the pair stage
+  VEH V;
+  bind_vehicle(V, P, Pdev, ktab, cws, kAviaryContactFloats);
   const int tid = threadIdx.x;
   const int lane = blockIdx.x * kWave + tid;
   if (lane >= n) return;  // (whole worlds: the lanes that stay are every lane of their worlds)
   const size_t li = lane, N = n;
   const int K = P.agents_per_world;
-  __shared__ __attribute__((aligned(16))) float cws[kAviaryContactFloats];  // the contact solvers' LDS regions (floor and pair stage)
-  __shared__ float wpose[kWave * 8];                                         // each lane's pose and contact bit, once per tick
-  __shared__ float wvel[kWave * kPairVelStride];                             // ... and its new velocities for the pair stage
-  VEH V;
-  V.b.pdev = Pdev;
-  V.b.cws = (lds_fptr)cws;
-  V.b.contact_regions(P, kAviaryContactFloats);
-  V.bind(ktab);
   V.b.wpose_ = wpose; V.b.wvel_ = wvel; V.b.wtid = tid; V.b.wA = K;
-  float nd;
+  int mode;
+  float nd, sp[8];
   int4 ints;
-  const int mode = B.modes ? B.modes[li] : P.flight_mode;
-  V.load(reinterpret_cast<const float4*>(B.state), N, li, mode, nd, ints);
-  V.b.rpy = euler_from_quat_fast(V.b.q);
-  uint32_t rng_ctr = (uint32_t)ints.z;
+  uint32_t rng_ctr;
   Noise nz;
-  nz.init(P, n, li, lane0);
-  float sp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  const int spn = (P.vehicle == PF_FIXEDWING && mode == -1) ? 6 : 4;
-#pragma unroll
-  for (int k = 0; k < 8; ++k)
-    if (k < spn) sp[k] = B.setpoints[li * spn + k];
-  const int ratio = B.ctrl_ratio ? B.ctrl_ratio[li] : 0;
+  load_lane(V, P, B, n, li, lane0, mode, nd, ints, rng_ctr, nz);
+  read_setpoints(P, B, li, mode, sp);
+  const int ratio = lane_ctrl_ratio(B, li, 0);
   const int rr = ratio > 0 ? ratio : P.ticks_per_control;  // this drone's own control rate, or once per Aviary step
-  const bool armed = !B.armed || B.armed[li] != 0;         // aviary.py:423-438
+  const bool armed = lane_armed(B, li);
   // The QuadX controller reads its constants from the device copy of the parameter block: taken from the kernel argument, the
   // compiler keeps them in registers across the tick loop, whose pair-stage call leaves half the register file to the values that
   // live across it, and the instantiation spilled to scratch memory. The copy's flight_mode is the one of pf_ctx_create: the lane's
@@ -686,19 +631,9 @@ __global__ void __launch_bounds__(kWave) aviary_world_step_kernel(const pf_param
     if (armed) V.b.rpy = euler_from_quat_fast(V.b.q);
     rng_ctr += 1;
   }
-  int flags = (ints.y & ~PF_F_CONTACT) | (V.b.contact_now ? PF_F_CONTACT : 0);
-  V.store(reinterpret_cast<float4*>(B.state), N, li, mode, nd, int4{ints.x, flags, (int)rng_ctr, ints.w});
-  if (B.out_state && armed) {
-    float4* o = reinterpret_cast<float4*>(B.out_state + li * 12);
-    o[0] = float4{V.b.wb.x, V.b.wb.y, V.b.wb.z, V.b.rpy.x};
-    o[1] = float4{V.b.rpy.y, V.b.rpy.z, V.b.vb.x, V.b.vb.y};
-    o[2] = float4{V.b.vb.z, V.b.p.x, V.b.p.y, V.b.p.z};
-  }
-  if (B.out_aux && armed) {
-    float aux[VEH::AUX];
-    V.aux(aux);
-    for (int k = 0; k < VEH::AUX; ++k) B.out_aux[li * VEH::AUX + k] = aux[k];
-  }
+  store_lane(V, B, n, li, mode, nd, ints, rng_ctr);
+  if (B.out_state && armed) write_out_state(V, B, li);
+  if (B.out_aux && armed) write_out_aux(V, B, li);
   if (B.out_contact) B.out_contact[li] = floor ? 1 : 0;
   if (B.out_contact_peers) B.out_contact_peers[li] = (uint8_t)peers;
 }
@@ -710,36 +645,25 @@ __global__ void __launch_bounds__(kWave) aviary_tick_kernel(const pf_params P, c
                                                             const uint64_t lane0, const int tick_index,
                                                             const pf_params* __restrict__ Pdev) {
   __shared__ __attribute__((aligned(16))) float ktab[VEH::TABLE_FLOATS];
-  VEH::fill_table(ktab, Pdev, threadIdx.x);
-  __syncthreads();
+  __shared__ __attribute__((aligned(16))) float cws[kAviaryContactFloats];  // the contact solver's LDS regions (uav_vehicles.hpp)
+  VEH V;
+  bind_vehicle(V, P, Pdev, ktab, cws, kAviaryContactFloats);
   const int lane = blockIdx.x * kWave + threadIdx.x;
   if (lane >= n) return;
   const size_t li = lane, N = n;
   constexpr bool kQuad = VEH::AUX == 4;
   constexpr int kCmdGroup = 12;
-  __shared__ __attribute__((aligned(16))) float cws[kAviaryContactFloats];  // the contact solver's LDS regions (uav_vehicles.hpp)
-  VEH V;
-  V.b.pdev = Pdev;
-  V.b.cws = (lds_fptr)cws;
-  V.b.contact_regions(P, kAviaryContactFloats);
-  V.bind(ktab);
-  float nd;
-  int4 ints;
-  const int mode = B.modes ? B.modes[li] : P.flight_mode;
   float4* S = reinterpret_cast<float4*>(B.state);
-  V.load(S, N, li, mode, nd, ints);
-  V.b.rpy = euler_from_quat_fast(V.b.q);
-  uint32_t rng_ctr = (uint32_t)ints.z;
+  int mode;
+  float nd, sp[8];
+  int4 ints;
+  uint32_t rng_ctr;
   Noise nz;
-  nz.init(P, n, li, lane0);
+  load_lane(V, P, B, n, li, lane0, mode, nd, ints, rng_ctr, nz);
   nz.begin_event(rng_ctr, 0u, B.xi);
-  float sp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  const int spn = P.vehicle == PF_ROCKET ? 7 : ((P.vehicle == PF_FIXEDWING && mode == -1) ? 6 : 4);
-#pragma unroll
-  for (int k = 0; k < 8; ++k)
-    if (k < spn) sp[k] = B.setpoints[li * spn + k];
-  const int ratio = B.ctrl_ratio ? B.ctrl_ratio[li] : P.ticks_per_control;
-  const bool armed = !B.armed || B.armed[li] != 0;
+  read_setpoints(P, B, li, mode, sp);
+  const int ratio = lane_ctrl_ratio(B, li, P.ticks_per_control);
+  const bool armed = lane_armed(B, li);
   if (!armed) {
     V.tick_unarmed(P);
   } else {
@@ -754,29 +678,12 @@ __global__ void __launch_bounds__(kWave) aviary_tick_kernel(const pf_params P, c
   }
   V.b.rpy = euler_from_quat_fast(V.b.q);
   if (tick_index == P.ticks_per_control - 1) rng_ctr += 1;
-  int flags = (ints.y & ~PF_F_CONTACT) | (V.b.contact_now ? PF_F_CONTACT : 0);
-  V.store(S, N, li, mode, nd, int4{ints.x, flags, (int)rng_ctr, ints.w});
+  store_lane(V, B, n, li, mode, nd, ints, rng_ctr);
   if (kQuad) S[(size_t)kCmdGroup * N + li] = V.get_cmd();
-  if (B.out_state && armed) {
-    float4* o = reinterpret_cast<float4*>(B.out_state + li * 12);
-    o[0] = float4{V.b.wb.x, V.b.wb.y, V.b.wb.z, V.b.rpy.x};
-    o[1] = float4{V.b.rpy.y, V.b.rpy.z, V.b.vb.x, V.b.vb.y};
-    o[2] = float4{V.b.vb.z, V.b.p.x, V.b.p.y, V.b.p.z};
-  }
-  if (B.out_aux && armed) {
-    float aux[VEH::AUX];
-    V.aux(aux);
-    for (int k = 0; k < VEH::AUX; ++k) B.out_aux[li * VEH::AUX + k] = aux[k];
-  }
+  if (B.out_state && armed) write_out_state(V, B, li);
+  if (B.out_aux && armed) write_out_aux(V, B, li);
   if (B.out_contact) B.out_contact[li] = V.b.contact_now ? 1 : 0;
-  if (B.out_link_pos) {
-#pragma unroll
-    for (int k = 0; k < VEH::WIND_LINKS; ++k) {
-      v3 lp = V.link_pos(P, k);
-      float* o = B.out_link_pos + (li * VEH::WIND_LINKS + k) * 3;
-      o[0] = lp.x; o[1] = lp.y; o[2] = lp.z;
-    }
-  }
+  if (B.out_link_pos) write_out_link_pos(V, P, B, li);
 }
 
 // applyExternalForce / applyExternalTorque on the base link (LINK_FRAME) + stepSimulation, n_ticks times
@@ -786,16 +693,13 @@ __global__ void __launch_bounds__(kWave) body_tick_kernel(const pf_params P, con
                                                           const pf_params* __restrict__ Pdev) {
   const int lane = blockIdx.x * kWave + threadIdx.x;
   if (lane >= n) return;
-  const size_t li = lane, N = n;
+  const size_t li = lane;
   __shared__ __attribute__((aligned(16))) float cws[kAviaryContactFloats];
   VEH V;
-  V.b.pdev = Pdev;
-  V.b.cws = (lds_fptr)cws;
-  V.b.contact_regions(P, kAviaryContactFloats);
+  bind_contact(V, P, Pdev, cws, kAviaryContactFloats);  // (no constant table: the vehicle's forces are not run)
   float nd;
   int4 ints;
-  float4* S = reinterpret_cast<float4*>(B.state);
-  V.load(S, N, li, 7, nd, ints);
+  V.load(reinterpret_cast<const float4*>(B.state), (size_t)n, li, 7, nd, ints);
   const float* wr = B.wrench + li * 6;
   const v3 F{wr[0], wr[1], wr[2]}, tau{wr[3], wr[4], wr[5]};
   bool contact = false;
@@ -804,14 +708,8 @@ __global__ void __launch_bounds__(kWave) body_tick_kernel(const pf_params P, con
     contact |= V.b.contact_now;
   }
   V.b.rpy = euler_from_quat_fast(V.b.q);
-  int flags = (ints.y & ~PF_F_CONTACT) | (V.b.contact_now ? PF_F_CONTACT : 0);
-  V.store(S, N, li, 7, nd, int4{ints.x, flags, ints.z, ints.w});
-  if (B.out_state) {
-    float4* o = reinterpret_cast<float4*>(B.out_state + li * 12);
-    o[0] = float4{V.b.wb.x, V.b.wb.y, V.b.wb.z, V.b.rpy.x};
-    o[1] = float4{V.b.rpy.y, V.b.rpy.z, V.b.vb.x, V.b.vb.y};
-    o[2] = float4{V.b.vb.z, V.b.p.x, V.b.p.y, V.b.p.z};
-  }
+  store_lane(V, B, n, li, 7, nd, ints, (uint32_t)ints.z);
+  if (B.out_state) write_out_state(V, B, li);
   if (B.out_contact) B.out_contact[li] = contact ? 1 : 0;
 }
 
@@ -1216,7 +1114,7 @@ int pf_aviary_set_mode(pf_ctx* ctx, const pf_buffers* b, int mode, float* setpoi
   if (rc) return rc;
   const int grid = (ctx->n + pf::kWave - 1) / pf::kWave;
   hipStream_t s = (hipStream_t)stream;
-  const int sp_dim = ctx->P.vehicle == PF_ROCKET ? 7 : ((ctx->P.vehicle == PF_FIXEDWING && mode == -1) ? 6 : 4);  // fixedwing.py:221-224, rocket.py:228
+  const int sp_dim = pf::setpoint_width(ctx->P.vehicle, mode);
   const auto kernel = vehicle_kernel(ctx, pf::aviary_set_mode_kernel<pf::QuadX>, pf::aviary_set_mode_kernel<pf::Fixedwing>, pf::aviary_set_mode_kernel<pf::Rocket>);
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(pf::kWave), 0, s, ctx->P, *b, ctx->n, sp_dim, mode, setpoints_out);
   ctx->P.flight_mode = mode;

@@ -187,9 +187,7 @@ __global__ void __launch_bounds__(kWave) env_kernel<Rocket, PF_TASK_ROCKET_LANDI
   float4* Sout = reinterpret_cast<float4*>(B.state);
 
   Rocket V;
-  V.b.pdev = Pdev;
-  V.b.cws = (lds_fptr)tile;  // (idle during the physics ticks)
-  V.b.contact_regions(P, kWave * kMaxObs);
+  bind_contact(V, P, Pdev, tile, kWave * kMaxObs);  // (the tile is idle during the physics ticks)
   PadWorld W;
   W.pdev = Pdev;
   W.pad_step = false;

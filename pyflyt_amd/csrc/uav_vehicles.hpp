@@ -1225,4 +1225,84 @@ struct Fixedwing {
   PF_DEV void set_cmd(float4) {}
 };
 
+// ------------------------------------------------------------------------------------------
+// What every Aviary-level kernel (pyflyt_amd.hip) does around its own loop: bind, load, ..., store, outputs.
+// (The caller's variables go in by reference: see flush_obs_tile.)
+
+// Floats per drone in the setpoint buffer: fixedwing.py:221-224, rocket.py:228 (host and device)
+constexpr int setpoint_width(int vehicle, int mode) { return vehicle == PF_ROCKET ? 7 : ((vehicle == PF_FIXEDWING && mode == -1) ? 6 : 4); }
+
+// The vehicle's view of the wave's LDS: the contact solver's regions (`floats` of them at `cws`) and the device copy of the
+// parameter block it reads its colliders from.
+template <class VEH>
+PF_DEV void bind_contact(VEH& V, const pf_params& P, const pf_params* __restrict const& Pdev, float* cws, const int& floats) {
+  V.b.pdev = Pdev;
+  V.b.cws = (lds_fptr)cws;
+  V.b.contact_regions(P, floats);
+}
+// ... and the vehicle's constant table, filled here. EVERY thread of the workgroup calls this, before the lanes past n return:
+// it holds the barrier behind the fill.
+template <class VEH>
+PF_DEV void bind_vehicle(VEH& V, const pf_params& P, const pf_params* __restrict const& Pdev, float* ktab, float* cws, const int& floats) {
+  VEH::fill_table(ktab, Pdev, threadIdx.x);
+  __syncthreads();
+  bind_contact(V, P, Pdev, cws, floats);
+  V.bind(ktab);
+}
+template <class VEH>
+PF_DEV void bind_no_tick(VEH& V) { V.b.pdev = nullptr; V.b.cws = nullptr; }  // (a kernel that runs no physics tick)
+
+// The lane as the last call left it: its flight mode (per-drone modes: QuadX only), state, Euler angles, event counter, noise source.
+template <class VEH>
+PF_DEV void load_lane(VEH& V, const pf_params& P, const pf_buffers& B, const int& n, const size_t& li, const uint64_t& lane0, int& mode,
+                      float& nd, int4& ints, uint32_t& rng_ctr, Noise& nz) {
+  mode = B.modes ? B.modes[li] : P.flight_mode;
+  V.load(reinterpret_cast<const float4*>(B.state), (size_t)n, li, mode, nd, ints);
+  V.b.rpy = euler_from_quat_fast(V.b.q);
+  rng_ctr = (uint32_t)ints.z;
+  nz.init(P, n, li, lane0);
+}
+PF_DEV void read_setpoints(const pf_params& P, const pf_buffers& B, const size_t& li, const int& mode, float (&sp)[8]) {
+  const int spn = setpoint_width(P.vehicle, mode);
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    sp[k] = 0.0f;
+    if (k < spn) sp[k] = B.setpoints[li * spn + k];
+  }
+}
+// This drone's own control period in ticks (`unset`: the caller's value for "none given") and whether it is armed (aviary.py:423-438)
+PF_DEV int lane_ctrl_ratio(const pf_buffers& B, const size_t& li, const int& unset) { return B.ctrl_ratio ? B.ctrl_ratio[li] : unset; }
+PF_DEV bool lane_armed(const pf_buffers& B, const size_t& li) { return !B.armed || B.armed[li] != 0; }
+
+// The state back to HBM, the flags word's contact bit as the last tick left it.
+template <class VEH>
+PF_DEV void store_lane(const VEH& V, const pf_buffers& B, const int& n, const size_t& li, const int& mode, const float& nd, const int4& ints,
+                       const uint32_t& rng_ctr) {
+  const int flags = (ints.y & ~PF_F_CONTACT) | (V.b.contact_now ? PF_F_CONTACT : 0);
+  V.store(reinterpret_cast<float4*>(B.state), (size_t)n, li, mode, nd, int4{ints.x, flags, (int)rng_ctr, ints.w});
+}
+// One row of each optional output (the caller has checked the pointer, and `armed` where a disarmed drone keeps its last row).
+template <class VEH>
+PF_DEV void write_out_state(const VEH& V, const pf_buffers& B, const size_t& li) {  // w_b, rpy, v_b, p: 48 B rows
+  float4* o = reinterpret_cast<float4*>(B.out_state + li * 12);
+  o[0] = float4{V.b.wb.x, V.b.wb.y, V.b.wb.z, V.b.rpy.x};
+  o[1] = float4{V.b.rpy.y, V.b.rpy.z, V.b.vb.x, V.b.vb.y};
+  o[2] = float4{V.b.vb.z, V.b.p.x, V.b.p.y, V.b.p.z};
+}
+template <class VEH>
+PF_DEV void write_out_aux(const VEH& V, const pf_buffers& B, const size_t& li) {
+  float aux[VEH::AUX];
+  V.aux(aux);
+  for (int k = 0; k < VEH::AUX; ++k) B.out_aux[li * VEH::AUX + k] = aux[k];
+}
+template <class VEH>
+PF_DEV void write_out_link_pos(const VEH& V, const pf_params& P, const pf_buffers& B, const size_t& li) {
+#pragma unroll
+  for (int k = 0; k < VEH::WIND_LINKS; ++k) {
+    v3 lp = V.link_pos(P, k);
+    float* o = B.out_link_pos + (li * VEH::WIND_LINKS + k) * 3;
+    o[0] = lp.x; o[1] = lp.y; o[2] = lp.z;
+  }
+}
+
 }  // namespace pf

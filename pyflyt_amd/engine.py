@@ -140,6 +140,7 @@ class BatchEngine:
         return t
 
     def _sp_dim(self, mode=None):
+        """Floats per drone in the setpoint buffer (fixedwing.py:221-224, rocket.py:228): csrc's setpoint_width."""
         mode = self.params.flight_mode if mode is None else mode
         return 7 if self.params.vehicle == L.ROCKET else (6 if (self.params.vehicle == L.FIXEDWING and mode == -1) else 4)
 
