@@ -389,6 +389,49 @@ int pf_sample_actions(pf_ctx* ctx, float* actions, uint32_t step_index, void* st
  * an env task, for an auto-reset mode of OFF on the specialised single-agent kernels, and for sampling six-wide dogfight actions. */
 int pf_rollout(pf_ctx* ctx, const pf_buffers* b, int k_steps, uint32_t step_index0, void* stream);
 
+/* Closed-loop rollouts: pf_rollout with every action computed ON THE DEVICE, inside the same launch, by a small MLP policy from the
+ * observation the env has just written -- the loop an on-policy learner runs (obs -> policy -> action -> env.step), without a launch
+ * or a trip through HBM between the env step and the policy. (Added without a new PF_ABI_VERSION: pf_params and pf_buffers are as
+ * they were, and a new function breaks no existing binding.)
+ *   - WHICH OBSERVATION. Step s of lane i consumes a = mean + exp(log_std) * eps with mean = MLP(o): for s = 0, o is the lane's row
+ *     of obs0; for s >= 1 the observation the env wrote for step s - 1, i.e. the row of b->obs[s - 1] (under SAME_STEP the reset
+ *     observation of a lane that finished in step s - 1).
+ *   - NO CLIPPING: the action is used as sampled, as the reference env uses what it is given (quadx_base_env.py:280).
+ *   - RESET STEPS: a lane that NEXT_STEP resets at step s ignores its action, as in pf_env_step; actions_out still holds the sample.
+ *   - NOISE: eps is standard normal, ONE Philox call per lane and step keyed by (seed, global lane, step_index0 + s, 0), stream
+ *     constant 4, which no other draw uses (DESIGN.md lists them); the first four of the call's eight Box-Muller normals (16-bit
+ *     uniforms: |eps| <= 4.86, resolution 2^-16 in the radius and angle draws). log_std == NULL: no call, a = mean exactly.
+ *   - THE MLP: n_layers affine layers with `activation` between them, torch.nn.Linear's layout. Every sum runs bias first, then
+ *     the inputs in ascending index, one fused multiply-add each, in float32; hidden widths are padded with zero weights to
+ *     PF_POLICY_MAX_HIDDEN (exact). The order is fixed: results do not depend on the launch shape, and k steps in one call give
+ *     the same bits as two calls of k / 2 with step_index0 advanced and obs0 pointing at the first call's last observation row.
+ *     tanh is evaluated in float32 (absolute error below 2e-7).
+ *   - OUTPUTS: b->actions_out [k_steps][n][4] the consumed actions, mean_out the means; every trajectory buffer as for pf_rollout.
+ *     b->actions must be NULL (PF_ERR_ARG). The weights are read at every call: an optimiser step in place is seen by the next one.
+ *   - ALIASING: obs0 may point INTO b->obs -- continuing a rollout in the same trajectory buffer makes it row k_steps - 1 of the very
+ *     buffer the call overwrites. That is safe because each wavefront reads the obs0 rows of its own 64 lanes in its prologue, before
+ *     its first step, and is the only writer of those lanes' rows of b->obs (at step k_steps - 1, last). A change that lets another
+ *     wave write a lane's rows, or moves the obs0 read behind the first flush, breaks the splitting contract.
+ *   - SUPPORTED: QuadX-Hover and QuadX-Waypoints on the specialised kernel (pf_ctx_is_specialised() == 1), flight mode 0, PF_NOISE_OFF
+ *     or PF_NOISE_PHILOX, NEXT_STEP or SAME_STEP auto-reset, contact response on (4-point manifold) or off. Everything else -- other
+ *     tasks and vehicles (shared worlds among them), the generic kernel, cascaded flight modes, PF_NOISE_INJECT, auto-reset OFF, widths
+ *     over PF_POLICY_MAX_HIDDEN, and contact_response with contact_manifold_points = 8 (its solve runs out of line with a stack
+ *     argument block) -- is PF_ERR_UNSUPPORTED with a message that names what is missing. */
+#define PF_POLICY_MAX_HIDDEN 64
+enum pf_activation { PF_ACT_TANH = 0, PF_ACT_RELU = 1 };
+typedef struct pf_policy {
+  int32_t n_layers;            /* 2 or 3 affine layers = 1 or 2 hidden layers */
+  int32_t width[2];            /* hidden widths, 1..PF_POLICY_MAX_HIDDEN */
+  int32_t activation;          /* pf_activation, on the hidden layers; the output layer is affine */
+  const float* w[3];           /* device, row-major [out][in] = torch.nn.Linear.weight; in of layer 0 = pf_obs_dim(), out of the last = action width */
+  const float* b[3];           /* device, [out] */
+  const float* log_std;        /* device, [action width], or NULL = deterministic (action = mean) */
+  const float* obs0;           /* device, [n][pf_obs_dim()]: the observation the previous call left (reset, step, or the last row of a rollout) */
+  float* mean_out;             /* device, [k_steps][n][action width], or NULL */
+} pf_policy;
+size_t pf_sizeof_policy(void);
+int pf_rollout_policy(pf_ctx* ctx, const pf_buffers* b, const pf_policy* policy, int k_steps, uint32_t step_index0, void* stream);
+
 /* The reference's LOWER boundary for one drone: applyExternalForce / applyExternalTorque on the base link in
  * LINK_FRAME followed by stepSimulation (core/drones/quadx.py:502-510, core/aviary.py:516), n_ticks times with
  * the wrench b->wrench held: the free-body tick alone (collision detection, gyroscopic term, +-max_coord_vel

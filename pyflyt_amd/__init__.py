@@ -7,6 +7,7 @@ gfx950 called through a C ABI (include/pyflyt_amd.h). There is no CPU fallback.
 from . import _lib
 from ._lib import PyFlytAmdError
 from .params import build_params
+from .policy import MLPPolicy
 
-__all__ = ["_lib", "PyFlytAmdError", "build_params"]
+__all__ = ["_lib", "PyFlytAmdError", "build_params", "MLPPolicy"]
 __version__ = "0.1.0"

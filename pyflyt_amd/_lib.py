@@ -64,12 +64,9 @@ def _parse_header(path):
                 if not nm:
                     raise ValueError(f"cannot parse field {item!r} of {m.group(3)} in {path}")
                 dims = [defines[d] if d in defines else int(d) for d in re.findall(r"\[\s*(\w+)\s*\]", nm.group(2))]
-                if is_ptr:
-                    ct = C.c_void_p
-                else:
-                    ct = _SCALARS.get(base) or structs[base]
-                    for d in reversed(dims):
-                        ct = ct * d
+                ct = C.c_void_p if is_ptr else (_SCALARS.get(base) or structs[base])
+                for d in reversed(dims):  # (an array of pointers as well: pf_policy.w[3])
+                    ct = ct * d
                 fields.append((nm.group(1), ct))
         structs[m.group(3)] = type(m.group(3), (C.Structure,), {"_fields_": fields})
     protos = sorted(set(re.findall(r"\b(pf_[a-z_0-9]+)\s*\(", text)))
@@ -79,7 +76,7 @@ def _parse_header(path):
 _DEFINES, _ENUMS, _STRUCTS, _PROTOS = _parse_header(HEADER_PATH)
 PF_ABI_VERSION = _DEFINES["PF_ABI_VERSION"]
 PfPid, PfBox, PfSurface, PfRocket = _STRUCTS["pf_pid"], _STRUCTS["pf_box"], _STRUCTS["pf_surface"], _STRUCTS["pf_rocket"]
-PfParams, PfBuffers = _STRUCTS["pf_params"], _STRUCTS["pf_buffers"]
+PfParams, PfBuffers, PfPolicy = _STRUCTS["pf_params"], _STRUCTS["pf_buffers"], _STRUCTS["pf_policy"]
 for _k, _v in _ENUMS.items():  # PF_F_TERMINATED -> F_TERMINATED etc. stay spelled out above; expose the rest as PF_*
     globals().setdefault(_k, _v)
 
@@ -134,9 +131,11 @@ def lib():
     L.pf_wind_links.argtypes = [C.c_void_p]
     L.pf_rollout.argtypes = [C.c_void_p, C.POINTER(PfBuffers), C.c_int, C.c_uint32, C.c_void_p]
     L.pf_body_tick.argtypes = [C.c_void_p, C.POINTER(PfBuffers), C.c_int, C.c_void_p]
+    L.pf_rollout_policy.argtypes = [C.c_void_p, C.POINTER(PfBuffers), C.POINTER(PfPolicy), C.c_int, C.c_uint32, C.c_void_p]
+    L.pf_sizeof_policy.restype = C.c_size_t
     L.pf_sizeof_params.restype = C.c_size_t
     L.pf_sizeof_buffers.restype = C.c_size_t
-    if L.pf_sizeof_params() != C.sizeof(PfParams) or L.pf_sizeof_buffers() != C.sizeof(PfBuffers):
+    if L.pf_sizeof_params() != C.sizeof(PfParams) or L.pf_sizeof_buffers() != C.sizeof(PfBuffers) or L.pf_sizeof_policy() != C.sizeof(PfPolicy):
         raise PyFlytAmdError("struct layout mismatch between pyflyt_amd/_lib.py and include/pyflyt_amd.h")
     if L.pf_abi_version() != PF_ABI_VERSION:
         raise PyFlytAmdError("ABI version mismatch between pyflyt_amd/_lib.py and libpyflyt_amd.so")

@@ -753,6 +753,7 @@ struct pf_ctx {
   float4* tmpl;      // settled spawn state for lane-independent resets (env_kernel), or null
   pf::FwK FK;
   pf::FwTable* surf_dev;  // pre-combined surface + body constants (scalar-loaded per tick)
+  float* policy_dev;      // the specialised QuadX kernel: pf_rollout_policy's packed weights (policy_mlp.hpp), rewritten by every call
 };
 static thread_local char g_err[256] = "";
 
@@ -890,7 +891,7 @@ static int launch_env(pf_ctx* ctx, const pf_buffers* b, int op, const uint8_t* m
       });
       const int grid = (ctx->n + 64 * pf::kQuadWPB - 1) / (64 * pf::kQuadWPB);
       hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * pf::kQuadWPB), 0, s, ctx->K, *b, ctx->P_dev, ctx->n, ctx->lane0, op, mask, k_steps, step0,
-                         ctx->launch_ctr);
+                         ctx->launch_ctr, pf::PolicyK{});
       break;
     }
     case env_family::fixedwing_wp: {
@@ -923,11 +924,23 @@ static int launch_env(pf_ctx* ctx, const pf_buffers* b, int op, const uint8_t* m
   return PF_OK;
 }
 
+// pf_rollout_policy's instantiations: the one-wave-per-SIMD register budget at every batch size (the evaluation's 64 accumulators on top
+// of the env step leave no room under two waves' 256 registers without scratch, and its LDS -- 21 KB of the rollout + 16 KB of activations --
+// admits four waves per CU whatever the budget), with the contact response compiled in or not as the context has it. Zero scratch, all eight.
+template <int TASK>
+static auto quadx_policy_kernel(bool philox, bool cr) {
+  using namespace pf;
+  if (cr)
+    return philox ? quadx_m0_env_kernel<TASK, PF_NOISE_PHILOX, 64, 3, true, false, false, 1> : quadx_m0_env_kernel<TASK, PF_NOISE_OFF, 64, 3, true, false, false, 1>;
+  return philox ? quadx_m0_env_kernel<TASK, PF_NOISE_PHILOX, 64, 3, false, false, false, 1> : quadx_m0_env_kernel<TASK, PF_NOISE_OFF, 64, 3, false, false, false, 1>;
+}
+
 extern "C" {
 
 int pf_abi_version(void) { return PF_ABI_VERSION; }
 size_t pf_sizeof_params(void) { return sizeof(pf_params); }
 size_t pf_sizeof_buffers(void) { return sizeof(pf_buffers); }
+size_t pf_sizeof_policy(void) { return sizeof(pf_policy); }
 const char* pf_last_error(const pf_ctx* ctx) { return ctx ? ctx->err : g_err; }
 
 int pf_ctx_create(const pf_params* params, int n_lanes, int device, uint64_t lane_offset, pf_ctx** out) {
@@ -990,7 +1003,7 @@ int pf_ctx_create(const pf_params* params, int n_lanes, int device, uint64_t lan
     return fail(nullptr, PF_ERR_ARG, "the contact model's distances, threshold, erp, friction and restitution must be >= 0");
   pf_ctx* c = new (std::nothrow) pf_ctx;
   if (!c) return fail(nullptr, PF_ERR_ARG, "out of host memory");
-  c->P = P; c->n = n_lanes; c->device = device; c->lane0 = lane_offset; c->err[0] = 0; c->launch_ctr = nullptr;
+  c->P = P; c->n = n_lanes; c->device = device; c->lane0 = lane_offset; c->err[0] = 0; c->launch_ctr = nullptr; c->policy_dev = nullptr;
   {  // the airframe's worst-case contact count (collider vertices), see pf_params.contact_max_points
     int pts = 0;
     for (int k = 0; k < P.n_boxes; ++k) pts += P.boxes[k].kind == 1 ? 16 : (P.contact_manifold_points >= 8 ? 8 : 4);
@@ -1016,13 +1029,14 @@ int pf_ctx_create(const pf_params* params, int n_lanes, int device, uint64_t lan
       const size_t words = (size_t)pf::kCtrStride * (((size_t)n_lanes + 63) / 64);
       e = hipMalloc((void**)&c->launch_ctr, sizeof(uint32_t) * words);
       if (e == hipSuccess) e = hipMemset(c->launch_ctr, 0, sizeof(uint32_t) * words);
+      if (e == hipSuccess) e = hipMalloc((void**)&c->policy_dev, sizeof(float) * pf::kPolWords);
     }
     if (e == hipSuccess && (fam == env_family::fixedwing_wp || fam == env_family::dogfight_fast)) {
       e = hipMalloc((void**)&c->surf_dev, sizeof(fsurf));
       if (e == hipSuccess) e = hipMemcpy(c->surf_dev, &fsurf, sizeof(fsurf), hipMemcpyHostToDevice);
     }
     if (cur >= 0) (void)hipSetDevice(cur);
-    if (e != hipSuccess) { if (c->P_dev) hipFree(c->P_dev); if (c->launch_ctr) hipFree(c->launch_ctr); delete c; return hip_fail(nullptr, e, "pf_ctx_create: device parameter block"); }
+    if (e != hipSuccess) { if (c->P_dev) hipFree(c->P_dev); if (c->launch_ctr) hipFree(c->launch_ctr); if (c->policy_dev) hipFree(c->policy_dev); delete c; return hip_fail(nullptr, e, "pf_ctx_create: device parameter block"); }
   }
   if ((fam == env_family::fixedwing_wp || fam == env_family::generic) && (P.task == PF_TASK_HOVER || P.task == PF_TASK_WAYPOINTS) &&
       (P.vehicle == PF_FIXEDWING || P.noise_mode == PF_NOISE_OFF)) {
@@ -1049,6 +1063,7 @@ void pf_ctx_destroy(pf_ctx* ctx) {
   if (!ctx) return;
   if (ctx->P_dev) hipFree(ctx->P_dev);
   if (ctx->launch_ctr) hipFree(ctx->launch_ctr);
+  if (ctx->policy_dev) hipFree(ctx->policy_dev);
   if (ctx->tmpl) hipFree(ctx->tmpl);
   if (ctx->surf_dev) hipFree(ctx->surf_dev);
   delete ctx;
@@ -1181,6 +1196,49 @@ int pf_rollout(pf_ctx* ctx, const pf_buffers* b, int k_steps, uint32_t step_inde
   if ((f == env_family::quadx || f == env_family::fixedwing_wp) && P.autoreset == PF_AUTORESET_OFF && P.task != PF_TASK_MA_HOVER)
     return fail(ctx, PF_ERR_UNSUPPORTED, "pf_rollout: needs an auto-reset mode (finished lanes would idle for the rest of the launch)");
   return launch_env(ctx, b, pf::OP_STEP, nullptr, b->actions ? 2 : 1, k_steps, step_index0, stream);
+}
+int pf_rollout_policy(pf_ctx* ctx, const pf_buffers* b, const pf_policy* q, int k_steps, uint32_t step_index0, void* stream) {
+  if (!ctx || !b || !q || !b->state || !b->obs || !b->reward || !b->terminated || !b->truncated)
+    return fail(ctx, PF_ERR_ARG, "pf_rollout_policy: policy, state, obs, reward, terminated and truncated buffers are required");
+  if (k_steps < 1) return fail(ctx, PF_ERR_ARG, "pf_rollout_policy: k_steps must be >= 1");
+  if (b->actions) return fail(ctx, PF_ERR_ARG, "pf_rollout_policy: b->actions must be NULL (the policy computes the actions; b->actions_out receives them)");
+  const pf_params& P = ctx->P;
+  const env_choice& c = ctx->ek;
+  if (P.vehicle != PF_QUADX || (P.task != PF_TASK_HOVER && P.task != PF_TASK_WAYPOINTS))
+    return fail(ctx, PF_ERR_UNSUPPORTED, "pf_rollout_policy: QuadX-Hover and QuadX-Waypoints only (no on-device policy for this task / vehicle)");
+  if (c.family != env_family::quadx)
+    return fail(ctx, PF_ERR_UNSUPPORTED, "pf_rollout_policy: needs the specialised QuadX kernel (pf_ctx_is_specialised() == 1); this context runs the generic one");
+  if (c.md) return fail(ctx, PF_ERR_UNSUPPORTED, "pf_rollout_policy: flight mode 0 only (no instantiation with the cascaded flight modes)");
+  // (shared worlds exist for PF_TASK_MA_HOVER and the dogfight only: refused by the task check above)
+  if (P.noise_mode == PF_NOISE_INJECT) return fail(ctx, PF_ERR_UNSUPPORTED, "pf_rollout_policy: PF_NOISE_INJECT is a per-step protocol; use pf_env_step");
+  if (P.autoreset == PF_AUTORESET_OFF)
+    return fail(ctx, PF_ERR_UNSUPPORTED, "pf_rollout_policy: needs an auto-reset mode (auto-reset OFF: finished lanes would idle for the rest of the launch)");
+  // (the contact response with every vertex in the manifold runs the out-of-line solve, whose argument block is stack: no zero-scratch instantiation)
+  if (c.cr && P.contact_manifold_points >= 8)
+    return fail(ctx, PF_ERR_UNSUPPORTED, "pf_rollout_policy: contact_response with contact_manifold_points = 8 is not supported (the in-register floor solve holds the 4-point manifold)");
+  if (q->n_layers != 2 && q->n_layers != 3) return fail(ctx, PF_ERR_ARG, "pf_rollout_policy: n_layers must be 2 or 3");
+  for (int l = 0; l + 1 < q->n_layers; ++l) {
+    if (q->width[l] > PF_POLICY_MAX_HIDDEN) return fail(ctx, PF_ERR_UNSUPPORTED, "pf_rollout_policy: hidden widths over PF_POLICY_MAX_HIDDEN (64) are not supported");
+    if (q->width[l] < 1) return fail(ctx, PF_ERR_ARG, "pf_rollout_policy: hidden widths must be >= 1");
+  }
+  if (q->activation != PF_ACT_TANH && q->activation != PF_ACT_RELU) return fail(ctx, PF_ERR_ARG, "pf_rollout_policy: activation must be PF_ACT_TANH or PF_ACT_RELU");
+  for (int l = 0; l < q->n_layers; ++l)
+    if (!q->w[l] || !q->b[l]) return fail(ctx, PF_ERR_ARG, "pf_rollout_policy: every layer needs w and b");
+  if (!q->obs0) return fail(ctx, PF_ERR_ARG, "pf_rollout_policy: obs0 (the observation the previous call left) is required");
+  const int D = pf_obs_dim(ctx);
+  if (D > pf::kPolMaxIn) return fail(ctx, PF_ERR_UNSUPPORTED, "pf_rollout_policy: observation wider than the first layer's block");
+  int rc = ensure_device(ctx);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(pf::policy_pack_kernel, dim3(1), dim3(256), 0, s, *q, D, ctx->policy_dev);
+  const pf::PolicyK PK{ctx->policy_dev, q->obs0, q->mean_out, q->n_layers, q->activation, q->log_std != nullptr ? 1 : 0};
+  const bool philox = P.noise_mode == PF_NOISE_PHILOX;
+  const auto kernel = P.task == PF_TASK_HOVER ? quadx_policy_kernel<PF_TASK_HOVER>(philox, c.cr) : quadx_policy_kernel<PF_TASK_WAYPOINTS>(philox, c.cr);
+  const int grid = (ctx->n + 64 * pf::kQuadWPB - 1) / (64 * pf::kQuadWPB);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * pf::kQuadWPB), 0, s, ctx->K, *b, ctx->P_dev, ctx->n, ctx->lane0, (int)pf::OP_STEP, (const uint8_t*)nullptr,
+                     k_steps, step_index0, ctx->launch_ctr, PK);
+  PF_HIP(ctx, hipGetLastError());
+  return PF_OK;
 }
 int pf_body_tick(pf_ctx* ctx, const pf_buffers* b, int n_ticks, void* stream) {
   if (!ctx || !b || !b->state || !b->wrench) return fail(ctx, PF_ERR_ARG, "pf_body_tick: state and wrench buffers are required");

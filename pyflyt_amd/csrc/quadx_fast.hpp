@@ -25,6 +25,7 @@
 #include "uav_vehicles.hpp"  // contact_solve_dev
 #include "quadx_control_d.hpp"
 #include "shared_world.hpp"
+#include "policy_mlp.hpp"
 
 namespace pf {
 
@@ -1271,7 +1272,9 @@ struct QuadSpare {
 // ROLL: 0 = one env step per launch (pf_env_step / pf_env_reset); 1 = pf_rollout with on-device action sampling -- the
 // loop then contains NO vector-memory load, so nothing in it ever waits on vmcnt (on gfx9 stores count in vmcnt too: a
 // load in the loop would make every step wait for the previous step's observation stores to be acknowledged);
-// 2 = pf_rollout over a given action sequence (prefetched one step ahead; pays that wait).
+// 2 = pf_rollout over a given action sequence (prefetched one step ahead; pays that wait);
+// 3 = pf_rollout_policy: the action of step s + 1 is computed at the end of step s by the per-lane MLP (policy_mlp.hpp) from the
+// observation row the step has just left in the LDS tile -- weights through the scalar cache: still no vector-memory load in the loop.
 // One wavefront per workgroup: no barrier, no inter-wave traffic. (Multi-wave workgroups were measured in round 3 and dropped --
 // profiles/r06/experiments/ab_switches.patch has the switch; the index arithmetic below keeps the general form.)
 constexpr int kQuadWPB = 1;
@@ -1287,7 +1290,7 @@ template <int TASK, int NOISE, int LPW, int ROLL, bool CR, bool MODES = false, b
 __global__ void __launch_bounds__(64 * kQuadWPB, SHARED ? 1 : WPS) quadx_m0_env_kernel(const QuadK K, const pf_buffers B, const pf_params* __restrict__ Pfull,
                                                              const int n, const uint64_t lane0, const int op,
                                                              const uint8_t* __restrict__ mask, const int k_steps, const uint32_t step0,
-                                                             uint32_t* launch_ctr) {
+                                                             uint32_t* launch_ctr, const PolicyK PK) {
   constexpr bool ROLLOUT = ROLL != 0;
   // (see QuadSpare) REKEY: a reset's draws are keyed by the counter at the previous reset; SPARE: ... and prepared ahead. launch_ctr: one
   // word per workgroup (kCtrStride apart) in device memory, the env steps this context has taken -- the refill cadence is a function of that count alone.
@@ -1413,11 +1416,19 @@ __global__ void __launch_bounds__(64 * kQuadWPB, SHARED ? 1 : WPS) quadx_m0_env_
           spv.z = gk.x; spv.vz = gk.y; spv.thr = gk.z;
           // (the targets' four groups behind the int group: in front of it, with the state groups, they cost the Waypoints launch
           //  0.2 us -- 16.9 against 16.7 us --, the settled state's one group gained the Hover launch 0.13)
+          if constexpr (ROLL == 3) {
+            // (the policy rollout: the targets straight to the lane's LDS row, not through spv -- through it the Waypoints noise-off
+            //  instantiation kept one dead 16-byte store of spv.t[0] on the stack, its only scratch)
+            float4* r4 = reinterpret_cast<float4*>(splds);
+            r4[0] = float4{spv.z, spv.vz, spv.thr, 0.0f};
+            if (TASK == PF_TASK_WAYPOINTS) { r4[1] = Sin[8 * N + li]; r4[2] = Sin[9 * N + li]; r4[3] = Sin[10 * N + li]; r4[4] = Sin[11 * N + li]; }
+          } else {
           if (TASK == PF_TASK_WAYPOINTS) { spv.t[0] = Sin[8 * N + li]; spv.t[1] = Sin[9 * N + li]; spv.t[2] = Sin[10 * N + li]; spv.t[3] = Sin[11 * N + li]; }
           if (ROLLOUT) {
             float4* r4 = reinterpret_cast<float4*>(splds);
             r4[0] = float4{spv.z, spv.vz, spv.thr, 0.0f};
             if (TASK == PF_TASK_WAYPOINTS) { r4[1] = spv.t[0]; r4[2] = spv.t[1]; r4[3] = spv.t[2]; r4[4] = spv.t[3]; }
+          }
           }
         }
       }
@@ -1924,6 +1935,49 @@ __global__ void __launch_bounds__(64 * kQuadWPB, SHARED ? 1 : WPS) quadx_m0_env_
   const int KS = ROLLOUT ? k_steps : 1;
   float4 a_nxt = float4{0.f, 0.f, 0.f, 0.f};
   if (GIVEN) a_nxt = reinterpret_cast<const float4*>(B.actions)[li];
+  // (ROLL == 3) the action this lane consumes in step `slot`, from its observation row in the tile: mean = MLP(row), a = mean + std * eps
+  // with eps the first four normals of ONE Philox call of a stream of its own, 4 (0 motor noise, 1 settle noise, 2 reset draws, 3 the
+  // sampled rollout's uniforms). Stored where it is computed, one step ahead of its use.
+  lds_fptr polh = nullptr;
+  pol_cptr polP = nullptr;
+  if constexpr (ROLL == 3) {
+    __shared__ __attribute__((aligned(16))) float polh_all[kQuadWPB * kPolH * 64];
+    polh = (lds_fptr)(polh_all + wid * (kPolH * 64) + tid);
+    polP = pol_uniform(PK.packed);
+  }
+  auto policy_action = [&](const int slot) -> float4 {
+    const float4 m = policy_mean(PK, polP, (lds_fptr)(tile + tid * D), D, polh);
+    float4 a = m;
+    if (PK.has_std) {
+      const f8 e = normal8(philox4x32(K.seed_lo, K.seed_hi, (uint32_t)(lane0 + li), step0 + (uint32_t)slot, 0u, 4u));
+      a = float4{fmaf(polP[kPolStd + 0], e.v[0], m.x), fmaf(polP[kPolStd + 1], e.v[1], m.y), fmaf(polP[kPolStd + 2], e.v[2], m.z),
+                 fmaf(polP[kPolStd + 3], e.v[3], m.w)};
+    }
+    if (active) {
+      const size_t o = 4 * ((size_t)slot * N + li);
+      if (PK.mean_out != nullptr) {
+        float* mo = PK.mean_out + o;
+        __builtin_nontemporal_store(m.x, mo + 0); __builtin_nontemporal_store(m.y, mo + 1);
+        __builtin_nontemporal_store(m.z, mo + 2); __builtin_nontemporal_store(m.w, mo + 3);
+      }
+      if (B.actions_out != nullptr) {
+        float* ao = B.actions_out + o;
+        __builtin_nontemporal_store(a.x, ao + 0); __builtin_nontemporal_store(a.y, ao + 1);
+        __builtin_nontemporal_store(a.z, ao + 2); __builtin_nontemporal_store(a.w, ao + 3);
+      }
+    }
+    return a;
+  };
+  if constexpr (ROLL == 3) {  // step 0 acts on obs0: the lane's row staged in the tile (the only vector-memory loads of the policy, in the prologue)
+    if (active) {
+      const float* o0 = PK.obs0 + li * (size_t)D;
+      float* row = tile + tid * D;
+      for (int k = 0; k < D; ++k) row[k] = o0[k];
+    }
+    lds_sync_wave();
+    a_nxt = policy_action(0);
+    lds_sync_wave();
+  }
   for (int it = 0; it < KS; ++it) {
   const size_t toff = ROLLOUT ? (size_t)it * N : (size_t)0;  // this step's slot in the trajectory buffers (lanes)
   // ---------------------------------------------------------------- reset (NEXT_STEP / explicit)
@@ -1949,12 +2003,14 @@ __global__ void __launch_bounds__(64 * kQuadWPB, SHARED ? 1 : WPS) quadx_m0_env_
     if (GIVEN) {
       a_roll = a_nxt;
       if (it + 1 < KS) a_nxt = reinterpret_cast<const float4*>(B.actions)[toff + N + li];
+    } else if constexpr (ROLL == 3) {
+      a_roll = a_nxt;  // (computed, and stored, at the end of the previous step / in the prologue)
     } else {  // == sample_actions_kernel(step0 + it): a copy of sampled_action4 (that call moved the code of the noise-free rollouts)
       f4 u = uniform4(philox4x32(K.seed_lo, K.seed_hi, (uint32_t)(lane0 + li), step0 + (uint32_t)it, 0u, 3u));
       a_roll = float4{fmaf(K.act_span[0], u.a, K.act_lo[0]), fmaf(K.act_span[1], u.b, K.act_lo[1]),
                       fmaf(K.act_span[2], u.c, K.act_lo[2]), fmaf(K.act_span[3], u.d, K.act_lo[3])};
     }
-    if (!GIVEN && B.actions_out != nullptr && active) {
+    if (!GIVEN && ROLL != 3 && B.actions_out != nullptr && active) {
       float* ao = B.actions_out + 4 * (toff + li);
       __builtin_nontemporal_store(a_roll.x, ao + 0); __builtin_nontemporal_store(a_roll.y, ao + 1);
       __builtin_nontemporal_store(a_roll.z, ao + 2); __builtin_nontemporal_store(a_roll.w, ao + 3);
@@ -2172,6 +2228,9 @@ __global__ void __launch_bounds__(64 * kQuadWPB, SHARED ? 1 : WPS) quadx_m0_env_
   // the next step's motor-noise normals (keyed by the event counter this step left behind)
   if (ROLLOUT && NOISE == PF_NOISE_PHILOX && it + 1 < KS)
     zn = normal8(philox4x32(K.seed_lo, K.seed_hi, (uint32_t)(lane0 + li), rng_ctr, 0u, 0u));
+  if constexpr (ROLL == 3) {  // the next step's action, from the row this step's observation has just left in the tile (flushed above)
+    if (it + 1 < KS) a_nxt = policy_action(it + 1);
+  }
   }  // for it
   if (SPARE && op == OP_STEP && tid == 0) launch_ctr[kCtrStride * blockIdx.x] = call0 + (uint32_t)KS;
   if (active) {  // the persistent state goes back to HBM once per launch
@@ -2197,6 +2256,12 @@ __global__ void __launch_bounds__(64 * kQuadWPB, SHARED ? 1 : WPS) quadx_m0_env_
       Sout[21 * N + li] = float4{(float)(SD.rE[1] - (double)V.E[1]), (float)(SD.rE[2] - (double)V.E[2]), (float)(SD.thr[3] - (double)V.t23.y), 0.0f};
       if constexpr (DSTATE) { if (K.mode > 0) C.store_lo(Sout, N, li, 22); }
     }
+    if constexpr (ROLL == 3) {  // (the same words, LDS row -> state without a QuadSpare in between: that copy kept a stack slot alive)
+      const float4* r4 = reinterpret_cast<const float4*>(splds);
+      const float4 a0 = r4[0];
+      Sout[7 * N + li] = float4{a0.x, a0.y, a0.z, __int_as_float((int)rkw)};
+      if (TASK == PF_TASK_WAYPOINTS) { Sout[8 * N + li] = r4[1]; Sout[9 * N + li] = r4[2]; Sout[10 * N + li] = r4[3]; Sout[11 * N + li] = r4[4]; }
+    } else
     if (REKEY && !(MODES && K.mode > 0) && (sp_dirty || ROLLOUT)) {  // group 7: the spare's settled state + the key word; 8-11: its targets
       const Sp x = SPARE ? spare_get() : Sp{};
       Sout[7 * N + li] = float4{x.z, x.vz, x.thr, __int_as_float((int)(SPARE ? rkw : (rkw & ~kSpareValid)))};

@@ -74,6 +74,9 @@ class BatchEngine:
         # env_step's hot path: {id(action tensor): (the tensor, its filled pf_buffers block)} -- see env_step
         self._prepared: dict[int, tuple] = {}
         self._step_fn = self.lib.pf_env_step
+        # the tensor that holds every lane's CURRENT observation: self.obs after a reset or a step, the last trajectory row after a
+        # rollout of either kind -- what rollout_policy's first step acts on (pf_policy.obs0)
+        self._cur_obs = self.obs
 
     def close(self):
         if self._ctx:
@@ -172,6 +175,7 @@ class BatchEngine:
         b = self._buffers(xi_reset=xi_reset, u_targets=u_targets)
         with torch.cuda.device(self.device):
             L.check(self.lib.pf_env_reset(self._ctx, C.byref(b), _ptr(mask), self._stream()), self._ctx)
+        self._cur_obs = self.obs
         return self.obs
 
     @property
@@ -195,6 +199,7 @@ class BatchEngine:
             rc = self._step_fn(self._ctx, hit[1], _raw_stream(self._index))  # (the library selects the context's device itself)
             if rc:
                 L.check(rc, self._ctx)
+            self._cur_obs = self.obs
             return self.obs, self.reward, self.terminated, self.truncated
         self._check_f32(actions, (self.n, self.action_dim), "actions")
         self._check_f32(xi, (self.ticks_per_step, self.n), "xi")
@@ -203,6 +208,7 @@ class BatchEngine:
         b = self._buffers(actions=actions, xi=xi, xi_reset=xi_reset, u_targets=u_targets)
         with torch.cuda.device(self.device):
             L.check(self.lib.pf_env_step(self._ctx, C.byref(b), self._stream()), self._ctx)
+        self._cur_obs = self.obs
         return self.obs, self.reward, self.terminated, self.truncated
 
     def _prepare(self, actions):
@@ -234,6 +240,7 @@ class BatchEngine:
             rc = fn(ctx, ref, stream_ptr)
             if rc:
                 check(rc, ctx)
+            self._cur_obs = self.obs
 
         launch._keep = (b, actions)  # (the buffer block and the action tensor stay alive with the closure)
         return launch
@@ -274,7 +281,48 @@ class BatchEngine:
         b.final_obs, b.final_info = _ptr(t["final_obs"]), _ptr(t["final_info"])
         with torch.cuda.device(self.device):
             L.check(self.lib.pf_rollout(self._ctx, C.byref(b), k, int(step_index0) & 0xFFFFFFFF, self._stream()), self._ctx)
+        self._cur_obs = t["obs"][k - 1]
         return t["obs"], t["reward"], t["terminated"], t["truncated"], (t["actions"] if actions is None and store_actions else actions)
+
+    def rollout_policy(self, policy, k_steps: int, step_index0: int = 0, store_mean: bool = False):
+        """pf_rollout_policy: `k_steps` env steps in one launch with every action computed on the device by `policy` (an MLPPolicy)
+        from the observation the env has just written -- the closed loop of an on-policy collector. The first step acts on the
+        engine's current observation (self.obs after a reset or a step, the last row of the previous rollout). Returns
+        (obs [k, n, D], reward [k, n], terminated [k, n], truncated [k, n], actions [k, n, 4]) -- the same tensors as rollout(),
+        overwritten by the next call -- and, with store_mean, the policy's means [k, n, 4] as a sixth. `step_index0` keys the
+        exploration noise: advance it by k between calls. QuadX-Hover / QuadX-Waypoints on the specialised kernel; everything else
+        raises PyFlytAmdError with the library's message."""
+        from .policy import MLPPolicy
+
+        if not isinstance(policy, MLPPolicy):
+            raise ValueError(f"policy must be a pyflyt_amd.MLPPolicy, got {type(policy).__name__}")
+        k = int(k_steps)
+        q = policy.fill(L.PfPolicy(), self)
+        t = getattr(self, "_traj", None)
+        if t is None or t["k"] != k:  # (rollout()'s trajectory tensors, shared with it)
+            f32 = dict(dtype=torch.float32, device=self.device)
+            t = dict(k=k, obs=torch.empty(k, self.n, self.obs_dim, **f32), reward=torch.empty(k, self.n, **f32),
+                     terminated=torch.empty(k, self.n, dtype=torch.bool, device=self.device),
+                     truncated=torch.empty(k, self.n, dtype=torch.bool, device=self.device),
+                     actions=torch.empty(k, self.n, self.action_dim, **f32),
+                     final_obs=torch.zeros(k, self.n, self.obs_dim, **f32) if self.final_obs is not None else None,
+                     final_info=torch.zeros(k, self.n, 2, dtype=torch.int32, device=self.device) if self.final_info is not None else None)
+            self._traj = t
+        mean = None
+        if store_mean:
+            mean = t.get("mean")
+            if mean is None:
+                mean = t["mean"] = torch.empty(k, self.n, 4, dtype=torch.float32, device=self.device)
+        q.obs0 = self._cur_obs.data_ptr()
+        q.mean_out = mean.data_ptr() if mean is not None else None
+        b = self._buffers(actions_out=t["actions"])
+        b.obs, b.reward, b.terminated, b.truncated = _ptr(t["obs"]), _ptr(t["reward"]), _ptr(t["terminated"]), _ptr(t["truncated"])
+        b.final_obs, b.final_info = _ptr(t["final_obs"]), _ptr(t["final_info"])
+        with torch.cuda.device(self.device):
+            L.check(self.lib.pf_rollout_policy(self._ctx, C.byref(b), C.byref(q), k, int(step_index0) & 0xFFFFFFFF, self._stream()), self._ctx)
+        self._cur_obs = t["obs"][k - 1]
+        out = (t["obs"], t["reward"], t["terminated"], t["truncated"], t["actions"])
+        return out + (mean,) if store_mean else out
 
     def body_tick(self, wrench, n_ticks: int = 1):
         """pf_body_tick: the free-body tick alone under a held body-frame wrench [n, 6] (force, torque)."""

@@ -127,6 +127,7 @@ class _VecEnvBase:
         self._ret = None
         self._infos_obj = None
         self._final_infos = None
+        self._policy_step = 0  # (rollout(): the step index that keys the policy's exploration noise)
 
     def _make_obs_space(self):
         self.single_observation_space = Box(low=-np.inf, high=np.inf, shape=(self.attitude_dim,), dtype=np.float32)
@@ -147,6 +148,7 @@ class _VecEnvBase:
         elif seed is not None and mask is None:
             # same seed: restart the event counters so that the rollout repeats exactly
             self.engine.state.zero_()
+            self._policy_step = 0
         if mask is not None and not torch.is_tensor(mask):
             mask = torch.as_tensor(np.asarray(mask), dtype=torch.bool, device=self.device)
         self.engine.env_reset(mask=mask)
@@ -192,6 +194,22 @@ class _VecEnvBase:
             r = self._ret
             return self._obs(self.engine.obs), r[1], r[2], r[3], r[4]
         return self._ret
+
+    def rollout(self, policy, k_steps: int, store_mean: bool = False):
+        """`k_steps` closed-loop env steps in ONE launch, every action computed on the device by `policy` (a pyflyt_amd.MLPPolicy)
+        from the observation the env has just returned (BatchEngine.rollout_policy). Returns the trajectories (obs [k, n, D] -- the
+        engine's flat observation rows, what the policy reads --, reward, terminated, truncated, actions [k, n, 4]) and the infos
+        of the LAST step (with store_mean the policy's means before them). The exploration noise's step index advances by k_steps
+        per call and restarts with reset(seed=...)."""
+        if self._needs_reset:
+            raise RuntimeError("call reset() before rollout()")
+        k = int(k_steps)
+        out = self.engine.rollout_policy(policy, k, step_index0=self._policy_step, store_mean=store_mean)
+        self._policy_step = (self._policy_step + k) & 0xFFFFFFFF
+        self._infos_obj.invalidate()
+        if self._final_infos is not None:
+            self._final_infos.invalidate()
+        return out + (self._infos_obj,)
 
     def close(self):
         self.engine.close()
