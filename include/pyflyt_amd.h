@@ -432,6 +432,57 @@ typedef struct pf_policy {
 size_t pf_sizeof_policy(void);
 int pf_rollout_policy(pf_ctx* ctx, const pf_buffers* b, const pf_policy* policy, int k_steps, uint32_t step_index0, void* stream);
 
+/* What an on-policy learner needs for every step of a rollout's trajectory before it can take a gradient step: which steps are real
+ * transitions, advantages and returns by generalised advantage estimation (GAE) with the bootstrap that tells terminated from
+ * truncated, and the log-probability of the action taken. Reads the trajectory buffers of pf_rollout / pf_rollout_policy (k_steps
+ * rows of n lanes) and the caller's value estimates; any context with an env task. (Added without a new PF_ABI_VERSION: a new
+ * function, pf_params and pf_buffers as they were.) Below, done[s] = terminated[s] | truncated[s], and done[-1] = episode_start
+ * under NEXT_STEP (NULL: 0), 0 otherwise.
+ *   - WHICH ROW HOLDS WHAT. values[s] is V of the observation the policy saw at step s: obs0 for s = 0, b->obs[s - 1] after;
+ *     values[k_steps] is V(b->obs[k_steps - 1]). Under NEXT_STEP the row b->obs[s] of a lane that finished in step s is its TERMINAL
+ *     observation, and step s + 1 ignores its action and only resets the lane (pf_env_step writes reward 0 and both flags 0 for it): it
+ *     is no transition. Under SAME_STEP b->obs[s] is already the reset observation and the terminal one is b->final_obs[s]:
+ *     final_values[s] = V(b->final_obs[s]), defined where done[s]; its other rows are stale and are never used.
+ *   - VALID. NEXT_STEP: step s is invalid if and only if done[s - 1] (the reset step). SAME_STEP and OFF: every step is valid.
+ *   - NEXT VALUE. nv[s] = values[s + 1]; under SAME_STEP nv[s] = done[s] ? final_values[s] : values[s + 1].
+ *   - VALID STEPS. delta = reward[s] + gamma * (terminated[s] ? 0 : nv[s]) - values[s];
+ *     advantages[s] = delta + gamma * lambda * (done[s] ? 0 : advantages[s + 1]), advantages[k_steps] = 0;
+ *     returns[s] = advantages[s] + values[s]. Truncation bootstraps, termination does not; both cut the recursion.
+ *   - INVALID STEPS. advantages[s] = 0, returns[s] = values[s] (the same bits), valid_out[s] = 0. Their reward goes into nothing; no
+ *     output of a valid step depends on an input of an invalid one (the step under an invalid step is done: the recursion is cut there).
+ *   - SELECTS. Every `?` above is a selection, not a multiplication by a mask: a NaN in a stale row of final_values, or in the
+ *     reward of an invalid step, reaches no output.
+ *   - LOG-PROBABILITY. logp_out[s] = sum over the A components c, in ascending c, of -1/2 z_c^2 - log_std_c - 1/2 log(2 pi) with
+ *     z_c = (actions_c - mean_c) * exp(-log_std_c): the diagonal Gaussian of pf_rollout_policy's head (|z_c| <= 4.86 for the actions
+ *     it sampled). For every step, valid or not. A = the context's action width (4; 6 for six-wide dogfight actions; 7 for
+ *     Rocket-Landing). actions, mean, log_std and logp_out come together or are all NULL.
+ *   - ARITHMETIC. float32, one fixed sequence of operations per lane: delta = fma(gamma, bootstrap, reward) - value,
+ *     advantage = fma(gamma * lambda, next advantage, delta). The bits do not depend on n, on the launch shape or on the stream. No
+ *     random draw.
+ *   - ERRORS. PF_ERR_ARG, pf_last_error naming the argument: k_steps < 1; a NULL reward, terminated, truncated, values, advantages
+ *     or returns; gamma or lambda outside [0, 1] or not finite; final_values NULL under SAME_STEP or non-NULL otherwise;
+ *     episode_start non-NULL outside NEXT_STEP; some but not all of the four log-probability pointers. PF_ERR_UNSUPPORTED: a
+ *     context without an env task.
+ *   - Enqueued on `stream`: no host synchronisation, no allocation, no copy -- capturable in a HIP graph. */
+typedef struct pf_gae_args {
+  float gamma, lambda;             /* both in [0, 1] */
+  const float*   reward;           /* [k][n]    */
+  const uint8_t* terminated;       /* [k][n]    */
+  const uint8_t* truncated;        /* [k][n]    */
+  const float*   values;           /* [k+1][n]: row s = V(observation the policy saw at step s); row k = V(obs row k-1) */
+  const float*   final_values;     /* [k][n] V(final_obs[s]); required under SAME_STEP, must be NULL otherwise */
+  const uint8_t* episode_start;    /* [n] or NULL(= all 0): NEXT_STEP only, 1 = the lane was waiting for its reset when the rollout began */
+  const float*   actions;          /* [k][n][A] consumed actions, A = the context's action width; NULL with mean/log_std/logp_out = no log-probs */
+  const float*   mean;             /* [k][n][A] */
+  const float*   log_std;          /* [A] */
+  float* advantages;               /* [k][n] */
+  float* returns;                  /* [k][n] */
+  float* logp_out;                 /* [k][n] or NULL */
+  uint8_t* valid_out;              /* [k][n] or NULL */
+} pf_gae_args;
+size_t pf_sizeof_gae(void);
+int pf_gae(pf_ctx* ctx, const pf_gae_args* a, int k_steps, void* stream);
+
 /* The reference's LOWER boundary for one drone: applyExternalForce / applyExternalTorque on the base link in
  * LINK_FRAME followed by stepSimulation (core/drones/quadx.py:502-510, core/aviary.py:516), n_ticks times with
  * the wrench b->wrench held: the free-body tick alone (collision detection, gyroscopic term, +-max_coord_vel

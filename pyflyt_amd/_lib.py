@@ -76,7 +76,7 @@ def _parse_header(path):
 _DEFINES, _ENUMS, _STRUCTS, _PROTOS = _parse_header(HEADER_PATH)
 PF_ABI_VERSION = _DEFINES["PF_ABI_VERSION"]
 PfPid, PfBox, PfSurface, PfRocket = _STRUCTS["pf_pid"], _STRUCTS["pf_box"], _STRUCTS["pf_surface"], _STRUCTS["pf_rocket"]
-PfParams, PfBuffers, PfPolicy = _STRUCTS["pf_params"], _STRUCTS["pf_buffers"], _STRUCTS["pf_policy"]
+PfParams, PfBuffers, PfPolicy, PfGae = _STRUCTS["pf_params"], _STRUCTS["pf_buffers"], _STRUCTS["pf_policy"], _STRUCTS["pf_gae_args"]
 for _k, _v in _ENUMS.items():  # PF_F_TERMINATED -> F_TERMINATED etc. stay spelled out above; expose the rest as PF_*
     globals().setdefault(_k, _v)
 
@@ -133,9 +133,12 @@ def lib():
     L.pf_body_tick.argtypes = [C.c_void_p, C.POINTER(PfBuffers), C.c_int, C.c_void_p]
     L.pf_rollout_policy.argtypes = [C.c_void_p, C.POINTER(PfBuffers), C.POINTER(PfPolicy), C.c_int, C.c_uint32, C.c_void_p]
     L.pf_sizeof_policy.restype = C.c_size_t
+    L.pf_gae.argtypes = [C.c_void_p, C.POINTER(PfGae), C.c_int, C.c_void_p]
+    L.pf_sizeof_gae.restype = C.c_size_t
     L.pf_sizeof_params.restype = C.c_size_t
     L.pf_sizeof_buffers.restype = C.c_size_t
-    if L.pf_sizeof_params() != C.sizeof(PfParams) or L.pf_sizeof_buffers() != C.sizeof(PfBuffers) or L.pf_sizeof_policy() != C.sizeof(PfPolicy):
+    if L.pf_sizeof_params() != C.sizeof(PfParams) or L.pf_sizeof_buffers() != C.sizeof(PfBuffers) or L.pf_sizeof_policy() != C.sizeof(PfPolicy) \
+            or L.pf_sizeof_gae() != C.sizeof(PfGae):
         raise PyFlytAmdError("struct layout mismatch between pyflyt_amd/_lib.py and include/pyflyt_amd.h")
     if L.pf_abi_version() != PF_ABI_VERSION:
         raise PyFlytAmdError("ABI version mismatch between pyflyt_amd/_lib.py and libpyflyt_amd.so")

@@ -722,6 +722,7 @@ __global__ void __launch_bounds__(256) sample_actions_kernel(const pf_params P, 
 }
 
 }  // namespace pf
+#include "gae.hpp"
 
 // ====================================================================== C ABI
 // The env kernel a context runs, chosen once at pf_ctx_create (select_env_kernel).
@@ -941,6 +942,7 @@ int pf_abi_version(void) { return PF_ABI_VERSION; }
 size_t pf_sizeof_params(void) { return sizeof(pf_params); }
 size_t pf_sizeof_buffers(void) { return sizeof(pf_buffers); }
 size_t pf_sizeof_policy(void) { return sizeof(pf_policy); }
+size_t pf_sizeof_gae(void) { return sizeof(pf_gae_args); }
 const char* pf_last_error(const pf_ctx* ctx) { return ctx ? ctx->err : g_err; }
 
 int pf_ctx_create(const pf_params* params, int n_lanes, int device, uint64_t lane_offset, pf_ctx** out) {
@@ -1237,6 +1239,50 @@ int pf_rollout_policy(pf_ctx* ctx, const pf_buffers* b, const pf_policy* q, int 
   const int grid = (ctx->n + 64 * pf::kQuadWPB - 1) / (64 * pf::kQuadWPB);
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * pf::kQuadWPB), 0, s, ctx->K, *b, ctx->P_dev, ctx->n, ctx->lane0, (int)pf::OP_STEP, (const uint8_t*)nullptr,
                      k_steps, step_index0, ctx->launch_ctr, PK);
+  PF_HIP(ctx, hipGetLastError());
+  return PF_OK;
+}
+int pf_gae(pf_ctx* ctx, const pf_gae_args* a, int k_steps, void* stream) {
+  if (!ctx || !a) return fail(ctx, PF_ERR_ARG, "pf_gae: ctx and the argument block are required");
+  const pf_params& P = ctx->P;
+  if (P.task == PF_TASK_NONE) return fail(ctx, PF_ERR_UNSUPPORTED, "pf_gae: needs a context with an env task (this one drives the Aviary level only)");
+  if (k_steps < 1) return fail(ctx, PF_ERR_ARG, "pf_gae: k_steps must be >= 1");
+  if (!a->reward) return fail(ctx, PF_ERR_ARG, "pf_gae: reward is required");
+  if (!a->terminated) return fail(ctx, PF_ERR_ARG, "pf_gae: terminated is required");
+  if (!a->truncated) return fail(ctx, PF_ERR_ARG, "pf_gae: truncated is required");
+  if (!a->values) return fail(ctx, PF_ERR_ARG, "pf_gae: values is required");
+  if (!a->advantages) return fail(ctx, PF_ERR_ARG, "pf_gae: advantages is required");
+  if (!a->returns) return fail(ctx, PF_ERR_ARG, "pf_gae: returns is required");
+  if (!(a->gamma >= 0.0f && a->gamma <= 1.0f)) return fail(ctx, PF_ERR_ARG, "pf_gae: gamma must be finite and in [0, 1]");
+  if (!(a->lambda >= 0.0f && a->lambda <= 1.0f)) return fail(ctx, PF_ERR_ARG, "pf_gae: lambda must be finite and in [0, 1]");
+  if (P.autoreset == PF_AUTORESET_SAME_STEP && !a->final_values)
+    return fail(ctx, PF_ERR_ARG, "pf_gae: final_values is required under SAME_STEP (the value of the terminal observation in final_obs)");
+  if (P.autoreset != PF_AUTORESET_SAME_STEP && a->final_values)
+    return fail(ctx, PF_ERR_ARG, "pf_gae: final_values must be NULL outside SAME_STEP (there is no final_obs)");
+  if (P.autoreset != PF_AUTORESET_NEXT_STEP && a->episode_start)
+    return fail(ctx, PF_ERR_ARG, "pf_gae: episode_start must be NULL outside NEXT_STEP (no other mode has reset steps)");
+  const int n_logp = (a->actions != nullptr) + (a->mean != nullptr) + (a->log_std != nullptr) + (a->logp_out != nullptr);
+  if (n_logp != 0 && n_logp != 4)
+    return fail(ctx, PF_ERR_ARG, "pf_gae: actions, mean, log_std and logp_out come together or are all NULL");
+  int rc = ensure_device(ctx);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const pf::GaeK K{a->gamma, a->lambda, a->reward, a->terminated, a->truncated, a->values, a->final_values, a->episode_start,
+                   a->advantages, a->returns, a->valid_out};
+  const auto scan = P.autoreset == PF_AUTORESET_NEXT_STEP   ? pf::gae_scan_kernel<PF_AUTORESET_NEXT_STEP>
+                    : P.autoreset == PF_AUTORESET_SAME_STEP ? pf::gae_scan_kernel<PF_AUTORESET_SAME_STEP>
+                                                            : pf::gae_scan_kernel<PF_AUTORESET_OFF>;
+  hipLaunchKernelGGL(scan, dim3((ctx->n + 63) / 64), dim3(64), 0, s, K, ctx->n, k_steps);
+  if (n_logp) {
+    const int width = P.task == PF_TASK_ROCKET_LANDING ? pf::kRlActionDim : (P.task == PF_TASK_DOGFIGHT && P.df_action_dim == 6) ? 6 : 4;
+    const size_t rows = (size_t)k_steps * (size_t)ctx->n;
+    const size_t blocks = (rows + pf::kGaeLogpBlock - 1) / pf::kGaeLogpBlock;
+    const dim3 grid((unsigned)(blocks < (size_t)pf::kGaeLogpMaxGrid ? blocks : (size_t)pf::kGaeLogpMaxGrid));
+    // (one float4 per row where the rows are four wide and the caller's pointers allow it; the same arithmetic either way)
+    const bool vec = width == 4 && (((uintptr_t)a->actions | (uintptr_t)a->mean) & 15) == 0;
+    hipLaunchKernelGGL(vec ? pf::gae_logp_kernel<true> : pf::gae_logp_kernel<false>, grid, dim3(pf::kGaeLogpBlock), 0, s, a->actions, a->mean,
+                       a->log_std, a->logp_out, rows, width);
+  }
   PF_HIP(ctx, hipGetLastError());
   return PF_OK;
 }

@@ -313,6 +313,12 @@ class BatchEngine:
             mean = t.get("mean")
             if mean is None:
                 mean = t["mean"] = torch.empty(k, self.n, 4, dtype=torch.float32, device=self.device)
+        self._launch_policy(q, t, k, step_index0, mean)
+        out = (t["obs"], t["reward"], t["terminated"], t["truncated"], t["actions"])
+        return out + (mean,) if store_mean else out
+
+    def _launch_policy(self, q, t, k, step_index0, mean):
+        """pf_rollout_policy into the trajectory tensors `t`, acting first on the engine's current observation."""
         q.obs0 = self._cur_obs.data_ptr()
         q.mean_out = mean.data_ptr() if mean is not None else None
         b = self._buffers(actions_out=t["actions"])
@@ -321,8 +327,99 @@ class BatchEngine:
         with torch.cuda.device(self.device):
             L.check(self.lib.pf_rollout_policy(self._ctx, C.byref(b), C.byref(q), k, int(step_index0) & 0xFFFFFFFF, self._stream()), self._ctx)
         self._cur_obs = t["obs"][k - 1]
-        out = (t["obs"], t["reward"], t["terminated"], t["truncated"], t["actions"])
-        return out + (mean,) if store_mean else out
+
+    def collect_rollout(self, policy, k_steps: int, step_index0: int = 0):
+        """rollout_policy for a learner: the same launch into trajectory tensors of its own whose observations live in ONE buffer
+        `obs_all` [k + 1, n, D]. Row 0 is the observation the first step acts on (an n x D copy of the engine's current observation),
+        the launch writes rows 1 .. k: obs_all[:-1] are the policy's inputs and obs_all[1:] the next observations, both views -- the
+        trajectory is never copied. Returns the dict of tensors (obs_all, obs = obs_all[1:], reward, terminated, truncated, actions,
+        mean, final_obs / final_info under SAME_STEP), overwritten by the next call with the same k_steps."""
+        from .policy import MLPPolicy
+
+        if not isinstance(policy, MLPPolicy):
+            raise ValueError(f"policy must be a pyflyt_amd.MLPPolicy, got {type(policy).__name__}")
+        k = int(k_steps)
+        if k < 1:
+            raise ValueError(f"k_steps must be >= 1, got {k_steps}")
+        q = policy.fill(L.PfPolicy(), self)
+        t = getattr(self, "_ctraj", None)
+        if t is None or t["k"] != k:
+            f32 = dict(dtype=torch.float32, device=self.device)
+            obs_all = torch.empty(k + 1, self.n, self.obs_dim, **f32)
+            t = dict(k=k, obs_all=obs_all, obs=obs_all[1:], reward=torch.empty(k, self.n, **f32),
+                     terminated=torch.empty(k, self.n, dtype=torch.bool, device=self.device),
+                     truncated=torch.empty(k, self.n, dtype=torch.bool, device=self.device),
+                     actions=torch.empty(k, self.n, self.action_dim, **f32), mean=torch.empty(k, self.n, self.action_dim, **f32),
+                     final_obs=torch.zeros(k, self.n, self.obs_dim, **f32) if self.final_obs is not None else None,
+                     final_info=torch.zeros(k, self.n, 2, dtype=torch.int32, device=self.device) if self.final_info is not None else None)
+            self._ctraj = t
+        cur = self._cur_obs
+        t["obs_all"][0].copy_(cur)  # (the previous call's last row, in this buffer or another, or self.obs)
+        self._cur_obs = t["obs_all"][0]
+        try:
+            self._launch_policy(q, t, k, step_index0, t["mean"])
+        except L.PyFlytAmdError:  # (refused: the engine's current observation is where it was)
+            self._cur_obs = cur
+            raise
+        return t
+
+    def gae(self, reward, terminated, truncated, values, gamma: float = 0.99, lam: float = 0.95, final_values=None, episode_start=None,
+            actions=None, mean=None, log_std=None):
+        """pf_gae: which steps of a trajectory are real transitions, their advantages and returns by generalised advantage
+        estimation, and the log-probabilities of the actions (include/pyflyt_amd.h has the semantics). reward / terminated /
+        truncated [k, n] as a rollout wrote them; values [k + 1, n]: row s the value of the observation the policy saw at step s,
+        row k that of the last observation; final_values [k, n]: the value of final_obs, SAME_STEP only (and required there);
+        episode_start [n]: NEXT_STEP only, lanes that were waiting for their reset when the rollout began; actions, mean [k, n, A]
+        and log_std [A] together, or none of them (then logp is None). Returns (advantages [k, n], returns [k, n], logp [k, n] or
+        None, valid [k, n] bool): tensors the engine owns, overwritten by the next call with the same k."""
+        if not torch.is_tensor(reward) or reward.dim() != 2:
+            raise ValueError(f"reward must be a float32 tensor of shape (k, {self.n}), got {type(reward).__name__ if not torch.is_tensor(reward) else tuple(reward.shape)}")
+        k, A = int(reward.shape[0]), self.action_dim
+        if k < 1:
+            raise ValueError("reward must hold at least one step")
+        flags = (torch.bool, torch.uint8)
+        self._check_f32(reward, (k, self.n), "reward")
+        for name, x in (("terminated", terminated), ("truncated", truncated)):
+            if x is None:
+                raise ValueError(f"{name} is required")
+            self._check(x, (k, self.n), flags, name)
+        if values is None:
+            raise ValueError("values is required")
+        self._check_f32(values, (k + 1, self.n), "values")
+        for name, x in (("gamma", gamma), ("lam", lam)):
+            if not 0.0 <= float(x) <= 1.0:  # (False for a NaN as well)
+                raise ValueError(f"{name} must be finite and in [0, 1], got {x}")
+        same, nxt = self.params.autoreset == L.AUTORESET_SAME_STEP, self.params.autoreset == L.AUTORESET_NEXT_STEP
+        if same and final_values is None:
+            raise ValueError("final_values is required under SAME_STEP auto-reset (the value of the terminal observation in final_obs)")
+        if not same and final_values is not None:
+            raise ValueError("final_values must be None outside SAME_STEP auto-reset (there is no final_obs)")
+        if not nxt and episode_start is not None:
+            raise ValueError("episode_start must be None outside NEXT_STEP auto-reset (no other mode has reset steps)")
+        self._check_f32(final_values, (k, self.n), "final_values")
+        self._check(episode_start, (self.n,), flags, "episode_start")
+        given = [x is not None for x in (actions, mean, log_std)]
+        if any(given) and not all(given):
+            raise ValueError("actions, mean and log_std come together or not at all")
+        self._check_f32(actions, (k, self.n, A), "actions")
+        self._check_f32(mean, (k, self.n, A), "mean")
+        self._check_f32(log_std, (A,), "log_std")
+        o = getattr(self, "_gae_out", None)
+        if o is None or o["k"] != k:
+            f32 = dict(dtype=torch.float32, device=self.device)
+            o = self._gae_out = dict(k=k, advantages=torch.empty(k, self.n, **f32), returns=torch.empty(k, self.n, **f32),
+                                     logp=torch.empty(k, self.n, **f32), valid=torch.empty(k, self.n, dtype=torch.bool, device=self.device))
+        a = L.PfGae()
+        a.gamma = float(gamma)
+        setattr(a, "lambda", float(lam))
+        a.reward, a.terminated, a.truncated, a.values = _ptr(reward), _ptr(terminated), _ptr(truncated), _ptr(values)
+        a.final_values, a.episode_start = _ptr(final_values), _ptr(episode_start)
+        a.actions, a.mean, a.log_std = _ptr(actions), _ptr(mean), _ptr(log_std)
+        a.advantages, a.returns, a.valid_out = _ptr(o["advantages"]), _ptr(o["returns"]), _ptr(o["valid"])
+        a.logp_out = _ptr(o["logp"]) if all(given) else None
+        with torch.cuda.device(self.device):
+            L.check(self.lib.pf_gae(self._ctx, C.byref(a), k, self._stream()), self._ctx)
+        return o["advantages"], o["returns"], (o["logp"] if all(given) else None), o["valid"]
 
     def body_tick(self, wrench, n_ticks: int = 1):
         """pf_body_tick: the free-body tick alone under a held body-frame wrench [n, 6] (force, torque)."""

@@ -211,6 +211,58 @@ class _VecEnvBase:
             self._final_infos.invalidate()
         return out + (self._infos_obj,)
 
+    def collect(self, policy, value_fn, k_steps: int, gamma: float = 0.99, lam: float = 0.95):
+        """One PPO batch from `k_steps` closed-loop env steps: the rollout launch of rollout(), the caller's value network, and
+        pf_gae (BatchEngine.gae) -- obs -> policy -> env -> batch ready for the loss, without a host synchronisation.
+        `value_fn`: any torch callable from a float32 [M, D] tensor to [M] or [M, 1] (float32); it is called under torch.no_grad(),
+        once on all k + 1 observation rows and, under SAME_STEP auto-reset, once more on the final_obs trajectory.
+        Returns a dict: obs [k, n, D] the policy's inputs, actions, mean, logp (None for a policy without log_std), values [k, n],
+        advantages, returns, valid [k, n] bool (False on the steps that only reset a lane under NEXT_STEP: mask the losses with it),
+        reward, terminated, truncated, last_value [n] (the value of the observation after the last step) and the infos of the last
+        step. obs is a view of the engine's [k + 1, n, D] buffer: obs[s + 1] is the very row the env wrote as step s's next
+        observation. The tensors belong to the engine and are overwritten by the next collect() with the same
+        k_steps. The exploration noise's step index advances as in rollout()."""
+        if self._needs_reset:
+            raise RuntimeError("call reset() before collect()")
+        from ..policy import MLPPolicy
+
+        if not isinstance(policy, MLPPolicy):
+            raise ValueError(f"policy must be a pyflyt_amd.MLPPolicy, got {type(policy).__name__}")
+        if not callable(value_fn):
+            raise ValueError(f"value_fn must be callable (a float32 [M, D] tensor -> [M] or [M, 1]), got {type(value_fn).__name__}")
+        for name, x in (("gamma", gamma), ("lam", lam)):
+            if not 0.0 <= float(x) <= 1.0:
+                raise ValueError(f"{name} must be finite and in [0, 1], got {x}")
+        eng, k = self.engine, int(k_steps)
+        episode_start = None
+        if eng.params.autoreset == L.AUTORESET_NEXT_STEP:
+            # lanes whose last step ended an episode: the launch's first step only resets them (read before the launch rewrites the flags)
+            episode_start = (eng.flags() & (L.F_TERMINATED | L.F_TRUNCATED)) != 0
+        t = eng.collect_rollout(policy, k, step_index0=self._policy_step)
+        self._policy_step = (self._policy_step + k) & 0xFFFFFFFF
+        self._infos_obj.invalidate()
+        if self._final_infos is not None:
+            self._final_infos.invalidate()
+
+        def value(rows, what):
+            m = rows.shape[0] * rows.shape[1]
+            v = value_fn(rows.view(m, eng.obs_dim))
+            if not torch.is_tensor(v) or v.dtype != torch.float32 or tuple(v.shape) not in ((m,), (m, 1)):
+                raise ValueError(f"value_fn must map the float32 {(m, eng.obs_dim)} {what} to a float32 tensor of shape {(m,)} or {(m, 1)}, "
+                                 f"got {(v.dtype, tuple(v.shape)) if torch.is_tensor(v) else type(v).__name__}")
+            return v.reshape(rows.shape[0], rows.shape[1]).contiguous()
+
+        with torch.no_grad():
+            values = value(t["obs_all"], "observations")
+            final_values = value(t["final_obs"], "final observations") if t["final_obs"] is not None else None
+        has_std = policy.log_std is not None
+        adv, ret, logp, valid = eng.gae(t["reward"], t["terminated"], t["truncated"], values, gamma=gamma, lam=lam, final_values=final_values,
+                                        episode_start=episode_start, actions=t["actions"] if has_std else None,
+                                        mean=t["mean"] if has_std else None, log_std=policy.log_std if has_std else None)
+        return dict(obs=t["obs_all"][:-1], actions=t["actions"], mean=t["mean"], logp=logp, values=values[:-1], advantages=adv, returns=ret,
+                    valid=valid, reward=t["reward"], terminated=t["terminated"], truncated=t["truncated"],
+                    last_value=values[-1], infos=self._infos_obj)
+
     def close(self):
         self.engine.close()
 

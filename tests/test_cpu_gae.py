@@ -1,0 +1,106 @@
+"""pf_gae's host side: the header / binding, and the argument validation of BatchEngine.gae and env.collect that needs no device."""
+import ctypes as C
+import os
+import re
+
+import pytest
+import torch
+
+from pyflyt_amd import MLPPolicy, build_params
+from pyflyt_amd import _lib as L
+from pyflyt_amd.engine import BatchEngine
+from pyflyt_amd.gym_envs.vector_envs import QuadXHoverVecEnv
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+N, K, A = 8, 5, 4
+
+
+def test_header_declares_the_gae_entry_points():
+    text = open(os.path.join(ROOT, "include", "pyflyt_amd.h")).read()
+    assert re.search(r"typedef\s+struct\s+pf_gae_args\s*\{", text)
+    assert re.search(r"size_t\s+pf_sizeof_gae\s*\(\s*void\s*\)", text)
+    assert re.search(r"int\s+pf_gae\s*\(\s*pf_ctx\s*\*\s*ctx\s*,\s*const\s+pf_gae_args\s*\*", text)
+    assert "pf_gae" in L.EXPORTS and "pf_sizeof_gae" in L.EXPORTS
+    assert L.PF_ABI_VERSION == 10
+
+
+def test_sizeof_gae_matches_the_parsed_mirror():
+    assert [f[0] for f in L.PfGae._fields_] == ["gamma", "lambda", "reward", "terminated", "truncated", "values", "final_values", "episode_start",
+                                                "actions", "mean", "log_std", "advantages", "returns", "logp_out", "valid_out"]
+    assert C.sizeof(L.PfGae) == 2 * 4 + 13 * C.sizeof(C.c_void_p)
+    if not os.path.exists(L.LIB_PATH):
+        pytest.fail(f"{L.LIB_PATH} is not built")
+    lib = C.CDLL(L.LIB_PATH)
+    lib.pf_sizeof_gae.restype = C.c_size_t
+    assert lib.pf_sizeof_gae() == C.sizeof(L.PfGae)
+    assert hasattr(lib, "pf_gae")
+
+
+def bare_engine(autoreset="next_step"):
+    """A BatchEngine without a context: what gae() checks before it reaches the library needs the lane count, the device and the
+    parameters only."""
+    eng = object.__new__(BatchEngine)
+    eng.n, eng.device, eng.params, eng._ctx = N, torch.device("cpu"), build_params("quadx", "hover", autoreset=autoreset), None
+    return eng
+
+
+def good(autoreset="next_step"):
+    kw = dict(reward=torch.zeros(K, N), terminated=torch.zeros(K, N, dtype=torch.bool), truncated=torch.zeros(K, N, dtype=torch.bool),
+              values=torch.zeros(K + 1, N), actions=torch.zeros(K, N, A), mean=torch.zeros(K, N, A), log_std=torch.zeros(A))
+    if autoreset == "same_step":
+        kw["final_values"] = torch.zeros(K, N)
+    return kw
+
+
+@pytest.mark.parametrize("change, fragment", [
+    (dict(reward=torch.zeros(K, N + 1)), "reward must be a contiguous float32 tensor of shape (5, 8)"),
+    (dict(reward=torch.zeros(K, N, dtype=torch.float64)), "reward must be a contiguous float32"),
+    (dict(reward=torch.zeros(N)), "reward must be a float32 tensor of shape (k, 8)"),
+    (dict(terminated=torch.zeros(K, N)), "terminated must be a contiguous torch.bool/torch.uint8"),
+    (dict(truncated=torch.zeros(K - 1, N, dtype=torch.bool)), "truncated must be"),
+    (dict(values=torch.zeros(K, N)), "values must be a contiguous float32 tensor of shape (6, 8)"),
+    (dict(values=torch.zeros(N, K + 1).T), "values must be a contiguous"),
+    (dict(values=None), "values is required"),
+    (dict(gamma=1.5), "gamma must be finite and in [0, 1]"),
+    (dict(gamma=float("nan")), "gamma must be finite and in [0, 1]"),
+    (dict(lam=-0.1), "lam must be finite and in [0, 1]"),
+    (dict(final_values=torch.zeros(K, N)), "final_values must be None outside SAME_STEP"),
+    (dict(episode_start=torch.zeros(N)), "episode_start must be a contiguous torch.bool/torch.uint8"),
+    (dict(mean=None), "actions, mean and log_std come together"),
+    (dict(actions=torch.zeros(K, N, A + 1)), "actions must be a contiguous float32 tensor of shape (5, 8, 4)"),
+    (dict(log_std=torch.zeros(A + 2)), "log_std must be a contiguous float32 tensor of shape (4,)"),
+])
+def test_gae_refusals_name_the_argument(change, fragment):
+    kw = good()
+    kw.update(change)
+    with pytest.raises(ValueError) as e:
+        bare_engine().gae(**kw)
+    assert fragment in str(e.value), str(e.value)
+
+
+def test_gae_refusals_that_depend_on_the_autoreset_mode():
+    kw = good("same_step")
+    del kw["final_values"]
+    with pytest.raises(ValueError, match="final_values is required under SAME_STEP"):
+        bare_engine("same_step").gae(**kw)
+    for mode in ("same_step", "off"):
+        with pytest.raises(ValueError, match="episode_start must be None outside NEXT_STEP"):
+            bare_engine(mode).gae(**good(mode), episode_start=torch.zeros(N, dtype=torch.bool))
+
+
+def test_collect_refusals():
+    env = object.__new__(QuadXHoverVecEnv)
+    env._needs_reset = True
+    g = torch.Generator().manual_seed(0)
+    pol = MLPPolicy([(torch.randn(8, 21, generator=g), torch.zeros(8)), (torch.randn(4, 8, generator=g), torch.zeros(4))])
+    with pytest.raises(RuntimeError, match="reset"):
+        env.collect(pol, lambda o: o[:, 0], 4)
+    env._needs_reset = False
+    with pytest.raises(ValueError, match="MLPPolicy"):
+        env.collect(torch.nn.Linear(21, 4), lambda o: o[:, 0], 4)
+    with pytest.raises(ValueError, match="value_fn must be callable"):
+        env.collect(pol, torch.zeros(3), 4)
+    with pytest.raises(ValueError, match="gamma"):
+        env.collect(pol, lambda o: o[:, 0], 4, gamma=2.0)
+    with pytest.raises(ValueError, match="lam"):
+        env.collect(pol, lambda o: o[:, 0], 4, lam=float("nan"))
