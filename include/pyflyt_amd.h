@@ -483,6 +483,62 @@ typedef struct pf_gae_args {
 size_t pf_sizeof_gae(void);
 int pf_gae(pf_ctx* ctx, const pf_gae_args* a, int k_steps, void* stream);
 
+/* What a learner wraps around an env before it trains on pf_gae's batches: the return and the length of every episode that finished
+ * inside a trajectory (gymnasium's RecordEpisodeStatistics), and the running moments an observation and a reward normaliser need
+ * (NormalizeObservation, NormalizeReward). Reads the trajectory buffers of pf_rollout / pf_rollout_policy (k_steps rows of n lanes);
+ * any context with an env task. (Added without a new PF_ABI_VERSION: a new function, pf_params and pf_buffers as they were.) Below,
+ * done[s] = terminated[s] | truncated[s], and done[-1] = episode_start under NEXT_STEP (NULL: 0), 0 otherwise.
+ *   - VALID. Exactly pf_gae's: under NEXT_STEP step s is invalid if and only if done[s - 1] (the step that only resets the lane);
+ *     under SAME_STEP and OFF every step is valid.
+ *   - CARRY. carry_return, carry_length and carry_disc [n] are the caller's, read and written: the running return, length and
+ *     discounted return of every lane's open episode, so that a trajectory may be split over calls. Zero them where a lane is
+ *     reset from outside.
+ *   - RECURSION, ascending s, on VALID steps only: ret = ret + reward[s] (a plain float32 add, in step order); len = len + 1;
+ *     G = fma(gamma, G, reward[s]). Where done[s], the finished episode is (ret, len), and then ret = 0, len = 0, G = 0. An invalid
+ *     step changes nothing and contributes nothing.
+ *   - PER-STEP OUTPUTS. ep_return_out[s], ep_length_out[s] = the finished episode's (ret, len) where valid[s] && done[s], 0
+ *     elsewhere: done itself is their mask. Either may be NULL.
+ *   - SUMMARY. summary[8], overwritten, over the episodes that finished in THIS call: count, sum of returns, sum of squared returns,
+ *     min return (+inf when count is 0), max return (-inf when count is 0), sum of lengths, number that ended terminated, number
+ *     that ended truncated (terminated wins when both are set).
+ *   - RUNNING MOMENTS. ret_moments[3] = (count, mean, M2) of G -- after the step's update, before the cut -- over the valid steps;
+ *     obs_moments[1 + 2 D] = (count, mean[D], M2[D]) of the columns of obs over the valid rows, D = pf_obs_dim(). Row s of obs is the
+ *     observation the policy SAW at step s (values[s]'s observation in pf_gae). Both are updated in place: the batch's count, mean
+ *     and M2 are merged into what the block holds (Chan et al.'s parallel update), so a zeroed block is the empty state and calls
+ *     accumulate. variance = M2 / count. ret_moments may be NULL; obs and obs_moments come together or are both NULL.
+ *   - SELECTS. The reward and the observation row of an invalid step are loaded and not selected: a NaN in them reaches no output,
+ *     no carry and no moment.
+ *   - ARITHMETIC. The float32 sequences above are fixed per lane: ep_return_out, ep_length_out and the carries are bit-identical
+ *     whether k steps go in one call or in two of k / 2, and do not depend on n, on the launch shape or on the stream. The sums
+ *     behind summary and the moments are double, about the mean the block held before the call, in an order that (n, k_steps, D)
+ *     alone decide (no atomics): the same call on the same inputs gives the same bits; splitting a call moves the moments by
+ *     rounding only.
+ *   - ERRORS. PF_ERR_ARG, pf_last_error naming the argument: k_steps < 1; a NULL reward, terminated, truncated, summary,
+ *     carry_return, carry_length or carry_disc; gamma outside [0, 1] or not finite; episode_start non-NULL outside NEXT_STEP; obs
+ *     without obs_moments or the reverse. PF_ERR_UNSUPPORTED: a context without an env task; obs given on a context whose
+ *     observation rows are wider than 128 floats (no env of this library is: the widest, an eight-agent dogfight's, is 123).
+ *   - Enqueued on `stream`: three launches, no host synchronisation, no allocation, no copy -- capturable in a HIP graph. The
+ *     partial sums between the launches live in a block the context owns (sized at pf_ctx_create from n): calls on one context
+ *     must not overlap on different streams. */
+typedef struct pf_traj_stats_args {
+  float gamma;                     /* in [0, 1] */
+  const float*   reward;           /* [k][n]    */
+  const uint8_t* terminated;       /* [k][n]    */
+  const uint8_t* truncated;        /* [k][n]    */
+  const uint8_t* episode_start;    /* [n] or NULL(= all 0): NEXT_STEP only, as for pf_gae */
+  const float*   obs;              /* [k][n][D] policy inputs, or NULL (with obs_moments) = no observation moments */
+  float*   carry_return;           /* [n] in / out */
+  int32_t* carry_length;           /* [n] in / out */
+  float*   carry_disc;             /* [n] in / out */
+  float*   ep_return_out;          /* [k][n] or NULL */
+  int32_t* ep_length_out;          /* [k][n] or NULL */
+  double*  summary;                /* [8] out */
+  double*  ret_moments;            /* [3] in / out, or NULL */
+  double*  obs_moments;            /* [1 + 2 D] in / out, or NULL */
+} pf_traj_stats_args;
+size_t pf_sizeof_traj_stats(void);
+int pf_traj_stats(pf_ctx* ctx, const pf_traj_stats_args* a, int k_steps, void* stream);
+
 /* The reference's LOWER boundary for one drone: applyExternalForce / applyExternalTorque on the base link in
  * LINK_FRAME followed by stepSimulation (core/drones/quadx.py:502-510, core/aviary.py:516), n_ticks times with
  * the wrench b->wrench held: the free-body tick alone (collision detection, gyroscopic term, +-max_coord_vel

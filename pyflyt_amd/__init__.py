@@ -7,7 +7,8 @@ gfx950 called through a C ABI (include/pyflyt_amd.h). There is no CPU fallback.
 from . import _lib
 from ._lib import PyFlytAmdError
 from .params import build_params
+from .moments import RunningMoments
 from .policy import MLPPolicy
 
-__all__ = ["_lib", "PyFlytAmdError", "build_params", "MLPPolicy"]
+__all__ = ["_lib", "PyFlytAmdError", "build_params", "MLPPolicy", "RunningMoments"]
 __version__ = "0.1.0"

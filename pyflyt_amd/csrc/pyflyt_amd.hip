@@ -723,6 +723,7 @@ __global__ void __launch_bounds__(256) sample_actions_kernel(const pf_params P, 
 
 }  // namespace pf
 #include "gae.hpp"
+#include "traj_stats.hpp"
 
 // ====================================================================== C ABI
 // The env kernel a context runs, chosen once at pf_ctx_create (select_env_kernel).
@@ -755,6 +756,7 @@ struct pf_ctx {
   pf::FwK FK;
   pf::FwTable* surf_dev;  // pre-combined surface + body constants (scalar-loaded per tick)
   float* policy_dev;      // the specialised QuadX kernel: pf_rollout_policy's packed weights (policy_mlp.hpp), rewritten by every call
+  double* ts_scratch;     // contexts with an env task: pf_traj_stats's partial sums between its launches (traj_stats.hpp: ts_scratch_words)
 };
 static thread_local char g_err[256] = "";
 
@@ -943,6 +945,7 @@ size_t pf_sizeof_params(void) { return sizeof(pf_params); }
 size_t pf_sizeof_buffers(void) { return sizeof(pf_buffers); }
 size_t pf_sizeof_policy(void) { return sizeof(pf_policy); }
 size_t pf_sizeof_gae(void) { return sizeof(pf_gae_args); }
+size_t pf_sizeof_traj_stats(void) { return sizeof(pf_traj_stats_args); }
 const char* pf_last_error(const pf_ctx* ctx) { return ctx ? ctx->err : g_err; }
 
 int pf_ctx_create(const pf_params* params, int n_lanes, int device, uint64_t lane_offset, pf_ctx** out) {
@@ -1005,7 +1008,7 @@ int pf_ctx_create(const pf_params* params, int n_lanes, int device, uint64_t lan
     return fail(nullptr, PF_ERR_ARG, "the contact model's distances, threshold, erp, friction and restitution must be >= 0");
   pf_ctx* c = new (std::nothrow) pf_ctx;
   if (!c) return fail(nullptr, PF_ERR_ARG, "out of host memory");
-  c->P = P; c->n = n_lanes; c->device = device; c->lane0 = lane_offset; c->err[0] = 0; c->launch_ctr = nullptr; c->policy_dev = nullptr;
+  c->P = P; c->n = n_lanes; c->device = device; c->lane0 = lane_offset; c->err[0] = 0; c->launch_ctr = nullptr; c->policy_dev = nullptr; c->ts_scratch = nullptr;
   {  // the airframe's worst-case contact count (collider vertices), see pf_params.contact_max_points
     int pts = 0;
     for (int k = 0; k < P.n_boxes; ++k) pts += P.boxes[k].kind == 1 ? 16 : (P.contact_manifold_points >= 8 ? 8 : 4);
@@ -1037,8 +1040,10 @@ int pf_ctx_create(const pf_params* params, int n_lanes, int device, uint64_t lan
       e = hipMalloc((void**)&c->surf_dev, sizeof(fsurf));
       if (e == hipSuccess) e = hipMemcpy(c->surf_dev, &fsurf, sizeof(fsurf), hipMemcpyHostToDevice);
     }
+    if (e == hipSuccess && fam != env_family::none)
+      e = hipMalloc((void**)&c->ts_scratch, sizeof(double) * pf::ts_scratch_words(n_lanes, pf_obs_dim(c)));
     if (cur >= 0) (void)hipSetDevice(cur);
-    if (e != hipSuccess) { if (c->P_dev) hipFree(c->P_dev); if (c->launch_ctr) hipFree(c->launch_ctr); if (c->policy_dev) hipFree(c->policy_dev); delete c; return hip_fail(nullptr, e, "pf_ctx_create: device parameter block"); }
+    if (e != hipSuccess) { if (c->P_dev) hipFree(c->P_dev); if (c->launch_ctr) hipFree(c->launch_ctr); if (c->policy_dev) hipFree(c->policy_dev); if (c->surf_dev) hipFree(c->surf_dev); if (c->ts_scratch) hipFree(c->ts_scratch); delete c; return hip_fail(nullptr, e, "pf_ctx_create: device parameter block"); }
   }
   if ((fam == env_family::fixedwing_wp || fam == env_family::generic) && (P.task == PF_TASK_HOVER || P.task == PF_TASK_WAYPOINTS) &&
       (P.vehicle == PF_FIXEDWING || P.noise_mode == PF_NOISE_OFF)) {
@@ -1056,7 +1061,7 @@ int pf_ctx_create(const pf_params* params, int n_lanes, int device, uint64_t lan
       e = hipDeviceSynchronize();
     }
     if (cur >= 0) hipSetDevice(cur);
-    if (e != hipSuccess) { if (c->tmpl) hipFree(c->tmpl); if (c->surf_dev) hipFree(c->surf_dev); hipFree(c->P_dev); delete c; return hip_fail(nullptr, e, "pf_ctx_create: settle template"); }
+    if (e != hipSuccess) { if (c->tmpl) hipFree(c->tmpl); if (c->surf_dev) hipFree(c->surf_dev); if (c->ts_scratch) hipFree(c->ts_scratch); hipFree(c->P_dev); delete c; return hip_fail(nullptr, e, "pf_ctx_create: settle template"); }
   }
   *out = c;
   return PF_OK;
@@ -1068,6 +1073,7 @@ void pf_ctx_destroy(pf_ctx* ctx) {
   if (ctx->policy_dev) hipFree(ctx->policy_dev);
   if (ctx->tmpl) hipFree(ctx->tmpl);
   if (ctx->surf_dev) hipFree(ctx->surf_dev);
+  if (ctx->ts_scratch) hipFree(ctx->ts_scratch);
   delete ctx;
 }
 int pf_state_groups(const pf_ctx* ctx) {
@@ -1283,6 +1289,47 @@ int pf_gae(pf_ctx* ctx, const pf_gae_args* a, int k_steps, void* stream) {
     hipLaunchKernelGGL(vec ? pf::gae_logp_kernel<true> : pf::gae_logp_kernel<false>, grid, dim3(pf::kGaeLogpBlock), 0, s, a->actions, a->mean,
                        a->log_std, a->logp_out, rows, width);
   }
+  PF_HIP(ctx, hipGetLastError());
+  return PF_OK;
+}
+int pf_traj_stats(pf_ctx* ctx, const pf_traj_stats_args* a, int k_steps, void* stream) {
+  if (!ctx || !a) return fail(ctx, PF_ERR_ARG, "pf_traj_stats: ctx and the argument block are required");
+  const pf_params& P = ctx->P;
+  if (P.task == PF_TASK_NONE) return fail(ctx, PF_ERR_UNSUPPORTED, "pf_traj_stats: needs a context with an env task (this one drives the Aviary level only)");
+  if (k_steps < 1) return fail(ctx, PF_ERR_ARG, "pf_traj_stats: k_steps must be >= 1");
+  if (!a->reward) return fail(ctx, PF_ERR_ARG, "pf_traj_stats: reward is required");
+  if (!a->terminated) return fail(ctx, PF_ERR_ARG, "pf_traj_stats: terminated is required");
+  if (!a->truncated) return fail(ctx, PF_ERR_ARG, "pf_traj_stats: truncated is required");
+  if (!a->summary) return fail(ctx, PF_ERR_ARG, "pf_traj_stats: summary is required");
+  if (!a->carry_return) return fail(ctx, PF_ERR_ARG, "pf_traj_stats: carry_return is required");
+  if (!a->carry_length) return fail(ctx, PF_ERR_ARG, "pf_traj_stats: carry_length is required");
+  if (!a->carry_disc) return fail(ctx, PF_ERR_ARG, "pf_traj_stats: carry_disc is required");
+  if (!(a->gamma >= 0.0f && a->gamma <= 1.0f)) return fail(ctx, PF_ERR_ARG, "pf_traj_stats: gamma must be finite and in [0, 1]");
+  if (P.autoreset != PF_AUTORESET_NEXT_STEP && a->episode_start)
+    return fail(ctx, PF_ERR_ARG, "pf_traj_stats: episode_start must be NULL outside NEXT_STEP (no other mode has reset steps)");
+  if (a->obs && !a->obs_moments) return fail(ctx, PF_ERR_ARG, "pf_traj_stats: obs comes with obs_moments (the block its moments are merged into)");
+  if (!a->obs && a->obs_moments) return fail(ctx, PF_ERR_ARG, "pf_traj_stats: obs_moments comes with obs");
+  const int D = pf_obs_dim(ctx);
+  if (a->obs && D > pf::kTsMaxD) return fail(ctx, PF_ERR_UNSUPPORTED, "pf_traj_stats: observation rows wider than 128 have no moments kernel");
+  int rc = ensure_device(ctx);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const bool next = P.autoreset == PF_AUTORESET_NEXT_STEP;
+  const int waves = (ctx->n + 63) / 64;
+  double* scan_part = ctx->ts_scratch;
+  double* obs_part = ctx->ts_scratch + pf::ts_scan_words(ctx->n);
+  const pf::TsK K{a->gamma, a->reward, a->terminated, a->truncated, a->episode_start, a->carry_return, a->carry_length, a->carry_disc,
+                  a->ep_return_out, a->ep_length_out, a->ret_moments};
+  hipLaunchKernelGGL(next ? pf::ts_scan_kernel<true> : pf::ts_scan_kernel<false>, dim3(waves), dim3(64), 0, s, K, ctx->n, k_steps, scan_part);
+  unsigned grid = 0;
+  if (a->obs) {
+    const size_t rows = (size_t)k_steps * (size_t)ctx->n;
+    grid = pf::ts_obs_grid(rows * (size_t)D);
+    hipLaunchKernelGGL(next ? pf::ts_obs_kernel<true> : pf::ts_obs_kernel<false>, dim3(grid), dim3(pf::kTsObsBlock), 0, s, a->obs, a->terminated,
+                       a->truncated, a->episode_start, a->obs_moments, obs_part, rows, ctx->n, D);
+  }
+  hipLaunchKernelGGL(pf::ts_finish_kernel, dim3(1), dim3(pf::kTsFinishBlock), 0, s, scan_part, waves, a->obs ? obs_part : nullptr, (int)grid, D,
+                     a->summary, a->ret_moments, a->obs_moments);
   PF_HIP(ctx, hipGetLastError());
   return PF_OK;
 }

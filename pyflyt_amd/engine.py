@@ -176,6 +176,10 @@ class BatchEngine:
         with torch.cuda.device(self.device):
             L.check(self.lib.pf_env_reset(self._ctx, C.byref(b), _ptr(mask), self._stream()), self._ctx)
         self._cur_obs = self.obs
+        ts = getattr(self, "_ts", None)
+        if ts is not None:  # (traj_stats' carries: the open episodes of the lanes that were reset are gone)
+            for name in ("carry_return", "carry_length", "carry_disc"):
+                ts[name].zero_() if mask is None else ts[name].masked_fill_(mask.bool(), 0)
         return self.obs
 
     @property
@@ -420,6 +424,79 @@ class BatchEngine:
         with torch.cuda.device(self.device):
             L.check(self.lib.pf_gae(self._ctx, C.byref(a), k, self._stream()), self._ctx)
         return o["advantages"], o["returns"], (o["logp"] if all(given) else None), o["valid"]
+
+    def _traj_state(self):
+        """What traj_stats keeps between calls, made at its first use: the per-lane carries, summary and the two running moment blocks."""
+        ts = getattr(self, "_ts", None)
+        if ts is None:
+            f32, f64 = dict(dtype=torch.float32, device=self.device), dict(dtype=torch.float64, device=self.device)
+            ts = self._ts = dict(carry_return=torch.zeros(self.n, **f32), carry_length=torch.zeros(self.n, dtype=torch.int32, device=self.device),
+                                 carry_disc=torch.zeros(self.n, **f32), summary=torch.zeros(8, **f64),
+                                 obs_moments=torch.zeros(1 + 2 * self.obs_dim, **f64), ret_moments=torch.zeros(3, **f64), k=0)
+        return ts
+
+    @property
+    def obs_moments(self):
+        """[1 + 2 D] float64 (count, mean[D], M2[D]): the running moments of the observation columns (traj_stats with obs=)."""
+        return self._traj_state()["obs_moments"]
+
+    @property
+    def ret_moments(self):
+        """[3] float64 (count, mean, M2): the running moments of the discounted return G (traj_stats)."""
+        return self._traj_state()["ret_moments"]
+
+    def reset_moments(self):
+        """Zero the running moments of traj_stats (the empty state). The carries of the open episodes stay."""
+        ts = self._traj_state()
+        ts["obs_moments"].zero_()
+        ts["ret_moments"].zero_()
+
+    def traj_stats(self, reward, terminated, truncated, gamma: float = 0.99, episode_start=None, obs=None, store_steps: bool = True):
+        """pf_traj_stats: the return and length of every episode that finished inside a trajectory, and the running moments of a
+        reward and an observation normaliser (include/pyflyt_amd.h has the semantics). reward / terminated / truncated [k, n] as a
+        rollout wrote them; episode_start [n]: NEXT_STEP only, as for gae(); obs [k, n, D]: the observations the policy saw (collect's
+        obs), or None for no observation moments; store_steps=False skips the two per-step outputs. The engine owns the per-lane
+        carries (a trajectory may be split over calls; env_reset zeroes the lanes it resets), summary and the running moments
+        (self.obs_moments, self.ret_moments; reset_moments() empties them). The carries describe the lanes' open episodes only if
+        EVERY env step since the last reset goes through traj_stats, in order: steps taken by env_step, rollout or a collect without
+        stats in between are not seen, and the next finished episode's return and length would miss them -- reset the lanes (or
+        zero the carries) before mixing the two. Returns (episode_return [k, n], episode_length [k, n]
+        int32 -- both None without store_steps --, summary [8] float64): overwritten by the next call with the same k."""
+        if not torch.is_tensor(reward) or reward.dim() != 2:
+            raise ValueError(f"reward must be a float32 tensor of shape (k, {self.n}), got {type(reward).__name__ if not torch.is_tensor(reward) else tuple(reward.shape)}")
+        k = int(reward.shape[0])
+        if k < 1:
+            raise ValueError("reward must hold at least one step")
+        flags = (torch.bool, torch.uint8)
+        self._check_f32(reward, (k, self.n), "reward")
+        for name, x in (("terminated", terminated), ("truncated", truncated)):
+            if x is None:
+                raise ValueError(f"{name} is required")
+            self._check(x, (k, self.n), flags, name)
+        if not 0.0 <= float(gamma) <= 1.0:  # (False for a NaN as well)
+            raise ValueError(f"gamma must be finite and in [0, 1], got {gamma}")
+        if self.params.autoreset != L.AUTORESET_NEXT_STEP and episode_start is not None:
+            raise ValueError("episode_start must be None outside NEXT_STEP auto-reset (no other mode has reset steps)")
+        self._check(episode_start, (self.n,), flags, "episode_start")
+        if obs is not None and not torch.is_tensor(obs):
+            raise ValueError(f"obs must be a float32 tensor of shape (k, {self.n}, D), got {type(obs).__name__}")
+        if obs is not None:
+            self._check_f32(obs, (k, self.n, self.obs_dim), "obs")
+        ts = self._traj_state()
+        if store_steps and ts["k"] != k:
+            ts.update(k=k, episode_return=torch.empty(k, self.n, dtype=torch.float32, device=self.device),
+                      episode_length=torch.empty(k, self.n, dtype=torch.int32, device=self.device))
+        a = L.PfTrajStats()
+        a.gamma = float(gamma)
+        a.reward, a.terminated, a.truncated, a.episode_start = _ptr(reward), _ptr(terminated), _ptr(truncated), _ptr(episode_start)
+        a.obs, a.obs_moments = _ptr(obs), (_ptr(ts["obs_moments"]) if obs is not None else None)
+        a.carry_return, a.carry_length, a.carry_disc = _ptr(ts["carry_return"]), _ptr(ts["carry_length"]), _ptr(ts["carry_disc"])
+        a.ep_return_out = _ptr(ts["episode_return"]) if store_steps else None
+        a.ep_length_out = _ptr(ts["episode_length"]) if store_steps else None
+        a.summary, a.ret_moments = _ptr(ts["summary"]), _ptr(ts["ret_moments"])
+        with torch.cuda.device(self.device):
+            L.check(self.lib.pf_traj_stats(self._ctx, C.byref(a), k, self._stream()), self._ctx)
+        return (ts["episode_return"] if store_steps else None), (ts["episode_length"] if store_steps else None), ts["summary"]
 
     def body_tick(self, wrench, n_ticks: int = 1):
         """pf_body_tick: the free-body tick alone under a held body-frame wrench [n, 6] (force, torque)."""

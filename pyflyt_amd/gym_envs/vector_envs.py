@@ -143,8 +143,12 @@ class _VecEnvBase:
             if mask is not None:
                 raise ValueError("cannot re-seed and partially reset in one call")
             self._seed = int(seed)
+            moments = getattr(self.engine, "_ts", None)  # (traj_stats' running moments outlive the engine; its carries do not)
             self.engine.close()
             self._build(self._seed)
+            if moments is not None:
+                self.engine.obs_moments.copy_(moments["obs_moments"])
+                self.engine.ret_moments.copy_(moments["ret_moments"])
         elif seed is not None and mask is None:
             # same seed: restart the event counters so that the rollout repeats exactly
             self.engine.state.zero_()
@@ -211,7 +215,7 @@ class _VecEnvBase:
             self._final_infos.invalidate()
         return out + (self._infos_obj,)
 
-    def collect(self, policy, value_fn, k_steps: int, gamma: float = 0.99, lam: float = 0.95):
+    def collect(self, policy, value_fn, k_steps: int, gamma: float = 0.99, lam: float = 0.95, stats: bool = False, normalize_reward: bool = False):
         """One PPO batch from `k_steps` closed-loop env steps: the rollout launch of rollout(), the caller's value network, and
         pf_gae (BatchEngine.gae) -- obs -> policy -> env -> batch ready for the loss, without a host synchronisation.
         `value_fn`: any torch callable from a float32 [M, D] tensor to [M] or [M, 1] (float32); it is called under torch.no_grad(),
@@ -221,9 +225,21 @@ class _VecEnvBase:
         reward, terminated, truncated, last_value [n] (the value of the observation after the last step) and the infos of the last
         step. obs is a view of the engine's [k + 1, n, D] buffer: obs[s + 1] is the very row the env wrote as step s's next
         observation. The tensors belong to the engine and are overwritten by the next collect() with the same
-        k_steps. The exploration noise's step index advances as in rollout()."""
+        k_steps. The exploration noise's step index advances as in rollout().
+        stats=True runs pf_traj_stats (BatchEngine.traj_stats) on the same trajectory before pf_gae and adds episode_return,
+        episode_length [k, n] (the finished episode's return and length where an episode ended in a valid step, 0 elsewhere) and
+        episode_summary ([8] float64 on the device; episode_summary_dict() reads it back); it updates the running moments behind
+        obs_rms (the columns of the policy's inputs) and ret_rms (the discounted return, with this call's gamma) over the valid steps.
+        normalize_reward=True implies stats, hands pf_gae reward / sqrt(ret_rms.var + 1e-8) with the moments AFTER this batch's
+        update, and adds it as reward_scaled; reward stays raw. The episode accounting is carried from one collect(stats=True) to the
+        next and sees only their steps: a step(), rollout() or collect() without stats in between advances the env behind its back,
+        and the first episode_return / episode_length after it would lack those steps -- reset() the env before switching."""
         if self._needs_reset:
             raise RuntimeError("call reset() before collect()")
+        for name, x in (("stats", stats), ("normalize_reward", normalize_reward)):
+            if not isinstance(x, bool):
+                raise ValueError(f"{name} must be a bool, got {type(x).__name__}")
+        stats = stats or normalize_reward
         from ..policy import MLPPolicy
 
         if not isinstance(policy, MLPPolicy):
@@ -256,12 +272,42 @@ class _VecEnvBase:
             values = value(t["obs_all"], "observations")
             final_values = value(t["final_obs"], "final observations") if t["final_obs"] is not None else None
         has_std = policy.log_std is not None
-        adv, ret, logp, valid = eng.gae(t["reward"], t["terminated"], t["truncated"], values, gamma=gamma, lam=lam, final_values=final_values,
+        extra, reward = {}, t["reward"]
+        if stats:
+            ep_ret, ep_len, summary = eng.traj_stats(t["reward"], t["terminated"], t["truncated"], gamma=gamma, episode_start=episode_start,
+                                                     obs=t["obs_all"][:-1])
+            extra = dict(episode_return=ep_ret, episode_length=ep_len, episode_summary=summary)
+            if normalize_reward:
+                reward = extra["reward_scaled"] = t["reward"] / (self.ret_rms.var + 1e-8).sqrt()
+        adv, ret, logp, valid = eng.gae(reward, t["terminated"], t["truncated"], values, gamma=gamma, lam=lam, final_values=final_values,
                                         episode_start=episode_start, actions=t["actions"] if has_std else None,
                                         mean=t["mean"] if has_std else None, log_std=policy.log_std if has_std else None)
         return dict(obs=t["obs_all"][:-1], actions=t["actions"], mean=t["mean"], logp=logp, values=values[:-1], advantages=adv, returns=ret,
                     valid=valid, reward=t["reward"], terminated=t["terminated"], truncated=t["truncated"],
-                    last_value=values[-1], infos=self._infos_obj)
+                    last_value=values[-1], infos=self._infos_obj, **extra)
+
+    @property
+    def obs_rms(self):
+        """RunningMoments of the observation columns the policy saw on valid steps, updated by collect(stats=True)."""
+        from ..moments import RunningMoments
+
+        return RunningMoments(self.engine.obs_moments)
+
+    @property
+    def ret_rms(self):
+        """RunningMoments (dim 1) of the discounted return over the valid steps, updated by collect(stats=True)."""
+        from ..moments import RunningMoments
+
+        return RunningMoments(self.engine.ret_moments)
+
+    def episode_summary_dict(self):
+        """The last collect(stats=True)'s episode_summary as Python numbers (THE place that synchronises with the device): episodes,
+        return_mean / return_std / return_min / return_max, length_mean, terminated, truncated; the means are nan when no episode
+        finished in that call."""
+        c, s1, s2, lo, hi, ln, te, tr = self.engine._traj_state()["summary"].tolist()
+        mean = s1 / c if c else float("nan")
+        return dict(episodes=int(c), return_mean=mean, return_std=max(s2 / c - mean * mean, 0.0) ** 0.5 if c else float("nan"), return_min=lo,
+                    return_max=hi, length_mean=ln / c if c else float("nan"), terminated=int(te), truncated=int(tr))
 
     def close(self):
         self.engine.close()

@@ -93,6 +93,20 @@ class MLPPolicy:
         self._first = (wf, bf)
         return self
 
+    def set_obs_stats(self, mean, std):
+        """The statistics of the observation normaliser, e.g. env.obs_rms.mean and env.obs_rms.std() after a collect(stats=True):
+        copied into obs_mean / obs_std (created on the first layer's device if the policy had none), then refresh()."""
+        for name, t in (("mean", mean), ("std", std)):
+            _check_param(t, name, 1)
+            if t.shape[0] != self.obs_dim:
+                raise ValueError(f"{name} has {t.shape[0]} entries for an observation width of {self.obs_dim}")
+        if self.obs_mean is None:
+            self.obs_mean, self.obs_std = torch.empty(self.obs_dim, device=self.device), torch.empty(self.obs_dim, device=self.device)
+        with torch.no_grad():
+            self.obs_mean.copy_(mean)
+            self.obs_std.copy_(std)
+        return self.refresh()
+
     def device_layers(self):
         """The (weight, bias) tensors the kernel reads: the folded first layer, then the others as given."""
         return [self._first] + self.layers[1:]
