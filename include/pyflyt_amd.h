@@ -539,6 +539,58 @@ typedef struct pf_traj_stats_args {
 size_t pf_sizeof_traj_stats(void);
 int pf_traj_stats(pf_ctx* ctx, const pf_traj_stats_args* a, int k_steps, void* stream);
 
+/* The clipped PPO objective of a diagonal-Gaussian policy over M rows of a batch, its statistics, and its gradients with respect to
+ * the actor's means, the critic's values and log_std: everything between the outputs of the caller's two networks and their
+ * output-gradients, in one call. Any context, with an env task or without: it serves the error string and owns the partial sums.
+ * rows = M >= 1 is any number of rows (a whole pf_gae batch flattened, or a gathered minibatch); width = A in 1..8. (Added without
+ * a new PF_ABI_VERSION: a new function, pf_params and pf_buffers as they were.) Below, c = the number of valid rows, w = 1 / c.
+ *   - ADVANTAGE. With normalize_advantage: mu = sum A / c and sigma = sqrt(sum (A - mu)^2 / c) over the valid rows (the population
+ *     form), both accumulated in double; a_i = (A_i - mu32) * inv32 with mu32, inv32 the float32 roundings of mu and of
+ *     1 / max(sigma, 1e-8). Without it a_i = A_i. No gradient flows through mu or sigma.
+ *   - LOG-PROBABILITY. Exactly pf_gae's: logp_i = sum over c, ascending from 0, of -1/2 z_c^2 - log_std_c - 1/2 log(2 pi) with
+ *     z_c = (actions_c - mean_c) * exp(-log_std_c).
+ *   - SURROGATE. r = exp(logp - logp_old); u = r * a; v = clamp(r, 1 - clip, 1 + clip) * a. The row contributes -w min(u, v) to
+ *     policy_loss. The gradient branch is live where u <= v: there d loss / d logp = -w a r; elsewhere it is 0.
+ *   - VALUE. value_loss = 1/2 sum w (value - returns)^2; grad_value_i = vf_coef w (value_i - returns_i). No value clipping.
+ *   - ENTROPY. H = sum_c (log_std_c + 1/2 (1 + log 2 pi)): state-independent.
+ *   - LOSS. loss = policy_loss + vf_coef * value_loss - ent_coef * H.
+ *   - GRADIENTS. grad_mean_ic = (d loss / d logp_i) z_ic exp(-log_std_c);
+ *     grad_log_std_c = sum_i (d loss / d logp_i) (z_ic^2 - 1) - ent_coef.
+ *   - STATS. stats[16], overwritten: 0 c; 1 loss; 2 policy_loss; 3 value_loss; 4 H; 5 approx_kl = sum w ((r - 1) - (logp - logp_old));
+ *     6 clip_fraction = sum w [|r - 1| > clip]; 7 mu; 8 sigma (computed whether or not they are applied); 9 explained variance
+ *     1 - Var(returns - value) / Var(returns) over the valid rows; 10 min r; 11 max r; 12-15 0.
+ *   - INVALID ROWS (valid_i = 0; valid NULL = every row is valid). Their grad_mean row and grad_value entry are exactly 0 and they
+ *     enter no sum. Every such choice is a selection, not a multiplication by a mask: a NaN anywhere in an invalid row reaches no
+ *     output. With c = 0 every gradient is 0 except grad_log_std = -ent_coef; slots 1-3 and 5-8 are 0 apart from the entropy term
+ *     of slot 1; slot 9 is NaN; slots 10 / 11 are +inf / -inf.
+ *   - ARITHMETIC. Per row one fixed float32 sequence (w enters it as the float32 rounding of 1 / c). All sums are double, in an
+ *     order that (rows, width) alone decide; no atomics: the same call on the same inputs gives the same bits whatever the stream,
+ *     and whether the four-wide rows are 16-byte aligned or not.
+ *   - ERRORS. PF_ERR_ARG, pf_last_error naming the argument: rows < 1; width outside 1..8; any NULL pointer other than valid;
+ *     clip not finite or <= 0; vf_coef or ent_coef negative or not finite; normalize_advantage other than 0 / 1.
+ *   - Enqueued on `stream`: four launches, no host synchronisation, no allocation, no copy -- capturable in a HIP graph. The partial
+ *     sums between the launches live in a fixed-size block the context allocates at pf_ctx_create (the grid is capped at 1024
+ *     blocks, so its size does not depend on rows): calls on one context must not overlap on different streams. */
+typedef struct pf_ppo_loss_args {
+  float clip;                      /* > 0 */
+  float vf_coef, ent_coef;         /* >= 0 */
+  int32_t normalize_advantage;     /* 0 / 1 */
+  const float*   mean;             /* [M][A] the new policy's means */
+  const float*   log_std;          /* [A] */
+  const float*   actions;          /* [M][A] */
+  const float*   logp_old;         /* [M] */
+  const float*   advantages;       /* [M] */
+  const float*   returns;          /* [M] */
+  const float*   value;            /* [M] the new critic's output */
+  const uint8_t* valid;            /* [M] or NULL(= all 1) */
+  float*  grad_mean;               /* [M][A] */
+  float*  grad_value;              /* [M] */
+  float*  grad_log_std;            /* [A] */
+  double* stats;                   /* [16] */
+} pf_ppo_loss_args;
+size_t pf_sizeof_ppo_loss(void);
+int pf_ppo_loss(pf_ctx* ctx, const pf_ppo_loss_args* a, size_t rows, int width, void* stream);
+
 /* The reference's LOWER boundary for one drone: applyExternalForce / applyExternalTorque on the base link in
  * LINK_FRAME followed by stepSimulation (core/drones/quadx.py:502-510, core/aviary.py:516), n_ticks times with
  * the wrench b->wrench held: the free-body tick alone (collision detection, gyroscopic term, +-max_coord_vel

@@ -9,6 +9,7 @@ from ._lib import PyFlytAmdError
 from .params import build_params
 from .moments import RunningMoments
 from .policy import MLPPolicy
+from .ppo import ppo_loss, ppo_stats_dict
 
-__all__ = ["_lib", "PyFlytAmdError", "build_params", "MLPPolicy", "RunningMoments"]
+__all__ = ["_lib", "PyFlytAmdError", "build_params", "MLPPolicy", "RunningMoments", "ppo_loss", "ppo_stats_dict"]
 __version__ = "0.1.0"

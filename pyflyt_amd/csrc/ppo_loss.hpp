@@ -1,0 +1,326 @@
+// pf_ppo_loss: the clipped PPO objective of a diagonal-Gaussian policy, its statistics and its gradients with respect to the
+// actor's means, the critic's values and log_std, in one pass over the M rows of a batch (include/pyflyt_amd.h states the semantics).
+// Four kernels in one call:
+//
+//   ppo_adv_kernel         the count, the sum and the sum of squares of the valid advantages, grid-strided; a thread issues the loads
+//                          of eight rows (the float and the validity byte) before it uses the first, and keeps its three sums in double.
+//                          The sums are about the shift 0 (DESIGN.md section 14 says what that costs).
+//   ppo_adv_finish_kernel  one block: the block partials in ascending order; c, mu, sigma, and the float32 roundings of mu and of
+//                          1 / max(sigma, 1e-8) that the main kernel applies.
+//   ppo_main_kernel        grid-strided over the rows, U rows per trip: every load of the U rows (mean, action, old log-probability,
+//                          advantage, return, value, validity byte; rows past M re-read row M - 1 and select nothing) is issued,
+//                          unconditionally, before the first value is used. Per row one fixed float32 sequence; the two per-row
+//                          gradients leave by streaming stores (nobody in this call reads them again); the sums behind `stats` and
+//                          grad_log_std stay per thread in double, are added over the wave by the fixed butterfly of traj_stats.hpp
+//                          and over the block's four waves through LDS in ascending order: one row of partials per block.
+//                          <W, VEC>: W = the action width; VEC (W = 4 and 16-byte aligned rows) moves one float4 per operand and
+//                          row, the other instantiations component by component. Same arithmetic, and a row belongs to the same
+//                          thread either way, so the bits agree.
+//   ppo_finish_kernel      one block: the block partials cut into eight contiguous segments, summed in ascending order, the
+//                          segments added in ascending order; `stats` and grad_log_std written.
+//
+// The grid of the two strided kernels is min(ceil(M / 256), 1024): a function of M alone, so (M, A) fix the order of every sum. No
+// atomics. Selections are selects: every input of an invalid row is loaded and then NOT chosen, so a NaN there reaches nothing.
+// A missing `valid` is served without a second instantiation: the byte is read from memory that is readable anyway and masked off.
+#pragma once
+
+namespace pf {
+
+constexpr int kPpoBlock = 256;
+constexpr int kPpoMaxGrid = 1024;    // 4 blocks per CU; the rest of the extent is grid-strided
+constexpr int kPpoMaxA = 8;          // widest action row
+constexpr int kPpoAdvUnroll = 8;     // rows a thread of the advantage pass has in flight
+constexpr int kPpoRowsVec = 3;       // rows a thread of the main kernel has in flight: float4 rows ...
+constexpr int kPpoRowsGen = 2;       // ... and component-wise rows (up to 16 loads each)
+constexpr int kPpoAdvQ = 3;          // count, sum, sum of squares
+constexpr int kPpoAdvStride = 4;
+constexpr int kPpoFinWords = 8;      // c, mu, sigma, mu32, inv32 (the float32 values, held as doubles)
+constexpr int kPpoSums = 7;          // sum min(u, v); sum (V - R)^2; sum (r - 1) - d; rows with |r - 1| > clip; sum R; sum R^2; sum (V - R)
+constexpr int kPpoQ = kPpoSums + 2 + kPpoMaxA;  // then min r, max r, then the grad_log_std sums
+constexpr int kPpoStride = 20;
+constexpr int kPpoSeg = 8;           // contiguous segments a finish kernel cuts the list of block partials into
+constexpr int kPpoWaves = kPpoBlock / 64;
+
+// doubles of scratch a context holds for the call: advantage partials, the advantage finish's block, the main partials
+constexpr size_t kPpoAdvOffset = 0;
+constexpr size_t kPpoFinOffset = (size_t)kPpoMaxGrid * kPpoAdvStride;
+constexpr size_t kPpoMainOffset = kPpoFinOffset + kPpoFinWords;
+constexpr size_t kPpoScratchWords = kPpoMainOffset + (size_t)kPpoMaxGrid * kPpoStride;
+
+inline unsigned ppo_grid(size_t rows) {
+  const size_t blocks = (rows + kPpoBlock - 1) / kPpoBlock;
+  return (unsigned)(blocks < (size_t)kPpoMaxGrid ? blocks : (size_t)kPpoMaxGrid);
+}
+
+typedef float ppo_f4 __attribute__((ext_vector_type(4)));
+
+struct PpoK {
+  float clip, vf_coef;
+  int32_t normalize;
+  const float* mean;
+  const float* log_std;
+  const float* actions;
+  const float* logp_old;
+  const float* advantages;
+  const float* returns;
+  const float* value;
+  const uint8_t* vbytes;  // `valid`, or any M readable bytes with vmask 0 where the caller gave none
+  uint32_t vmask;
+  float* grad_mean;
+  float* grad_value;
+};
+
+__global__ __launch_bounds__(kPpoBlock) void ppo_adv_kernel(const float* __restrict__ adv, const uint8_t* __restrict__ vbytes, uint32_t vmask,
+                                                             size_t rows, double* __restrict__ partials) {
+  __shared__ double sh[kPpoWaves][kPpoAdvQ];
+  const size_t stride = (size_t)gridDim.x * kPpoBlock;
+  const uint32_t all = vmask == 0u ? 1u : 0u;  // (no branch on it: a bit OR-ed into every row's byte)
+  uint32_t n = 0;
+  double s1 = 0.0, s2 = 0.0;
+  for (size_t r0 = (size_t)blockIdx.x * kPpoBlock + threadIdx.x; r0 < rows; r0 += (size_t)kPpoAdvUnroll * stride) {
+    float x[kPpoAdvUnroll];
+    uint32_t b[kPpoAdvUnroll];
+#pragma unroll
+    for (int u = 0; u < kPpoAdvUnroll; ++u) {  // every load of the eight rows (nothing here waits)
+      const size_t rw = r0 + (size_t)u * stride;
+      const size_t i = rw < rows ? rw : rows - 1;
+      x[u] = adv[i];
+      b[u] = vbytes[i];
+    }
+#pragma unroll
+    for (int u = 0; u < kPpoAdvUnroll; ++u) {
+      const bool ok = r0 + (size_t)u * stride < rows && ((b[u] & vmask) | all) != 0u;
+      const double d = (double)x[u];
+      n += ok ? 1u : 0u;
+      s1 = s1 + (ok ? d : 0.0);
+      s2 = s2 + (ok ? d * d : 0.0);
+    }
+  }
+  const double q0 = ts_wave_sum((double)n), q1 = ts_wave_sum(s1), q2 = ts_wave_sum(s2);
+  const int wave = (int)threadIdx.x / 64, lane = (int)threadIdx.x % 64;
+  if (lane < kPpoAdvQ) sh[wave][lane] = lane == 0 ? q0 : lane == 1 ? q1 : q2;
+  __syncthreads();
+  if (threadIdx.x < kPpoAdvQ) {
+    double v = sh[0][threadIdx.x];
+#pragma unroll
+    for (int w = 1; w < kPpoWaves; ++w) v = v + sh[w][threadIdx.x];
+    partials[(size_t)blockIdx.x * kPpoAdvStride + threadIdx.x] = v;
+  }
+}
+
+// One block. fin: c, mu, sigma, then the float32 roundings of mu and of 1 / max(sigma, 1e-8)
+__global__ __launch_bounds__(kPpoBlock) void ppo_adv_finish_kernel(const double* __restrict__ partials, int n_blocks, double* __restrict__ fin) {
+  __shared__ double seg[kPpoAdvQ * kPpoSeg];
+  const int t = (int)threadIdx.x;
+  if (t < kPpoAdvQ * kPpoSeg) {
+    const int q = t / kPpoSeg, sg = t % kPpoSeg, chunk = (n_blocks + kPpoSeg - 1) / kPpoSeg;
+    const int b1 = (sg + 1) * chunk < n_blocks ? (sg + 1) * chunk : n_blocks;
+    double v = 0.0;
+    for (int b = sg * chunk; b < b1; ++b) v = v + partials[(size_t)b * kPpoAdvStride + q];
+    seg[t] = v;
+  }
+  __syncthreads();
+  if (t == 0) {
+    double tot[kPpoAdvQ];
+#pragma unroll
+    for (int q = 0; q < kPpoAdvQ; ++q) {
+      double v = seg[q * kPpoSeg];
+      for (int sg = 1; sg < kPpoSeg; ++sg) v = v + seg[q * kPpoSeg + sg];
+      tot[q] = v;
+    }
+    const double c = tot[0];
+    const double mu = c > 0.0 ? tot[1] / c : 0.0;
+    const double var = c > 0.0 ? tot[2] / c - mu * mu : 0.0;  // sum (A - mu)^2 / c from the sums about 0
+    const double sigma = sqrt(var > 0.0 ? var : 0.0);
+    fin[0] = c;
+    fin[1] = mu;
+    fin[2] = sigma;
+    fin[3] = (double)(float)mu;
+    fin[4] = (double)(float)(1.0 / (sigma > 1e-8 ? sigma : 1e-8));
+  }
+}
+
+// (amdgpu_waves_per_eu(4, 4) and kPpoMaxGrid go together: 1024 blocks of four waves are 16 waves per CU on 256 CUs, four per SIMD, so the
+//  whole grid is resident at once whatever the instantiation; the float4 one needs the cap for its registers, the generic ones just obey it)
+template <int W, bool VEC>
+__global__ __launch_bounds__(kPpoBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) void ppo_main_kernel(PpoK a, size_t rows, const double* __restrict__ fin, double* __restrict__ partials) {
+  static_assert(!VEC || W == 4, "the float4 path is four wide");
+  constexpr int U = VEC ? kPpoRowsVec : kPpoRowsGen;
+  __shared__ double sh[kPpoWaves][kPpoQ];
+  float ls[W], inv[W];
+#pragma unroll
+  for (int c = 0; c < W; ++c) {
+    ls[c] = a.log_std[c];
+    inv[c] = expf(-ls[c]);
+  }
+  const double cnt = fin[0];
+  const float w32 = cnt > 0.0 ? (float)(1.0 / cnt) : 0.0f;
+  const float mu32 = (float)fin[3], inv32 = (float)fin[4];
+  const float lo_clip = 1.0f - a.clip, hi_clip = 1.0f + a.clip, kv = a.vf_coef * w32;
+  const uint32_t all = a.vmask == 0u ? 1u : 0u;  // (no branch on it: a bit OR-ed into every row's byte)
+  const bool norm = a.normalize != 0;
+  const size_t stride = (size_t)gridDim.x * kPpoBlock;
+  double sum[kPpoSums], gls[W];
+  uint32_t n_clip = 0;  // (sum[3] stays 0 until the end: the count is a whole number)
+#pragma unroll
+  for (int q = 0; q < kPpoSums; ++q) sum[q] = 0.0;
+#pragma unroll
+  for (int c = 0; c < W; ++c) gls[c] = 0.0;
+  float r_lo = INFINITY, r_hi = -INFINITY;
+  for (size_t r0 = (size_t)blockIdx.x * kPpoBlock + threadIdx.x; r0 < rows; r0 += (size_t)U * stride) {
+    float m[U][W], x[U][W], lpo[U], ad[U], rt[U], vl[U];
+    uint32_t b[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {  // every load of the U rows (nothing here waits); the rows past M read row M - 1 again
+      const size_t rw = r0 + (size_t)u * stride;
+      const size_t i = rw < rows ? rw : rows - 1;
+      if constexpr (VEC) {
+        const float4 mm = reinterpret_cast<const float4*>(a.mean)[i];
+        const float4 xx = reinterpret_cast<const float4*>(a.actions)[i];
+        m[u][0] = mm.x, m[u][1] = mm.y, m[u][2] = mm.z, m[u][3] = mm.w;
+        x[u][0] = xx.x, x[u][1] = xx.y, x[u][2] = xx.z, x[u][3] = xx.w;
+      } else {
+#pragma unroll
+        for (int c = 0; c < W; ++c) {
+          m[u][c] = a.mean[i * W + c];
+          x[u][c] = a.actions[i * W + c];
+        }
+      }
+      lpo[u] = a.logp_old[i];
+      ad[u] = a.advantages[i];
+      rt[u] = a.returns[i];
+      vl[u] = a.value[i];
+      b[u] = a.vbytes[i];
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const size_t rw = r0 + (size_t)u * stride;
+      const bool in = rw < rows;
+      const bool live = in && ((b[u] & a.vmask) | all) != 0u;
+      float z[W], logp = 0.0f;
+#pragma unroll
+      for (int c = 0; c < W; ++c) {
+        z[c] = (x[u][c] - m[u][c]) * inv[c];
+        logp = logp + gae_logp_term(x[u][c], m[u][c], ls[c], inv[c]);
+      }
+      const float adv = norm ? (ad[u] - mu32) * inv32 : ad[u];
+      const float d = logp - lpo[u];
+      const float r = expf(d);
+      const float su = r * adv;
+      const float sv = fminf(fmaxf(r, lo_clip), hi_clip) * adv;
+      const float surr = fminf(su, sv);
+      const bool act = live && su <= sv;  // the branch of the minimum that depends on the new policy
+      const float gl = act ? ((-w32) * adv) * r : 0.0f;  // d loss / d logp
+      const float dv = vl[u] - rt[u];
+      float gm[W];
+#pragma unroll
+      for (int c = 0; c < W; ++c) {
+        gm[c] = act ? (gl * z[c]) * inv[c] : 0.0f;
+        gls[c] = gls[c] + (double)(act ? gl * (z[c] * z[c] - 1.0f) : 0.0f);
+      }
+      const float gv = live ? kv * dv : 0.0f;
+      if (in) {
+        if constexpr (VEC) {
+          ppo_f4 o;
+          o.x = gm[0], o.y = gm[1], o.z = gm[2], o.w = gm[3];
+          __builtin_nontemporal_store(o, reinterpret_cast<ppo_f4*>(a.grad_mean) + rw);
+        } else {
+#pragma unroll
+          for (int c = 0; c < W; ++c) __builtin_nontemporal_store(gm[c], a.grad_mean + rw * W + c);
+        }
+        __builtin_nontemporal_store(gv, a.grad_value + rw);
+      }
+      const double R = (double)rt[u], D = (double)dv;
+      sum[0] = sum[0] + (live ? (double)surr : 0.0);
+      sum[1] = sum[1] + (live ? D * D : 0.0);
+      sum[2] = sum[2] + (live ? (double)((r - 1.0f) - d) : 0.0);
+      n_clip += live && fabsf(r - 1.0f) > a.clip ? 1u : 0u;
+      sum[4] = sum[4] + (live ? R : 0.0);
+      sum[5] = sum[5] + (live ? R * R : 0.0);
+      sum[6] = sum[6] + (live ? D : 0.0);
+      r_lo = live ? fminf(r_lo, r) : r_lo;
+      r_hi = live ? fmaxf(r_hi, r) : r_hi;
+    }
+  }
+  sum[3] = (double)n_clip;
+  double q[kPpoQ];
+#pragma unroll
+  for (int j = 0; j < kPpoSums; ++j) q[j] = ts_wave_sum(sum[j]);
+  q[kPpoSums] = ts_wave_min((double)r_lo);
+  q[kPpoSums + 1] = ts_wave_max((double)r_hi);
+#pragma unroll
+  for (int c = 0; c < kPpoMaxA; ++c) q[kPpoSums + 2 + c] = c < W ? ts_wave_sum(gls[c < W ? c : 0]) : 0.0;
+  const int wave = (int)threadIdx.x / 64, lane = (int)threadIdx.x % 64;
+  if (lane < kPpoQ) {  // (every lane holds all of them: lane t writes the t-th)
+    double v = q[0];
+#pragma unroll
+    for (int j = 1; j < kPpoQ; ++j) v = lane == j ? q[j] : v;
+    sh[wave][lane] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < kPpoQ) {  // the block's four waves in ascending order
+    const int j = (int)threadIdx.x;
+    double v = sh[0][j];
+#pragma unroll
+    for (int w = 1; w < kPpoWaves; ++w) v = j == kPpoSums ? fmin(v, sh[w][j]) : j == kPpoSums + 1 ? fmax(v, sh[w][j]) : v + sh[w][j];
+    partials[(size_t)blockIdx.x * kPpoStride + j] = v;
+  }
+}
+
+constexpr double kPpoEntropyConst = 1.41893853320467274178;  // 1/2 (1 + log 2 pi)
+
+// One block. partials: n_blocks rows of kPpoStride; fin: ppo_adv_finish_kernel's
+__global__ __launch_bounds__(kPpoBlock) void ppo_finish_kernel(const double* __restrict__ partials, int n_blocks, const double* __restrict__ fin,
+                                                                const float* __restrict__ log_std, int width, float vf_coef, float ent_coef,
+                                                                double* __restrict__ stats, float* __restrict__ grad_log_std) {
+  __shared__ double seg[kPpoQ * kPpoSeg];
+  const int t = (int)threadIdx.x;
+  if (t < kPpoQ * kPpoSeg) {
+    const int q = t / kPpoSeg, sg = t % kPpoSeg, chunk = (n_blocks + kPpoSeg - 1) / kPpoSeg;
+    const int b1 = (sg + 1) * chunk < n_blocks ? (sg + 1) * chunk : n_blocks;
+    double v = q == kPpoSums ? (double)INFINITY : q == kPpoSums + 1 ? -(double)INFINITY : 0.0;
+    for (int b = sg * chunk; b < b1; ++b) {
+      const double x = partials[(size_t)b * kPpoStride + q];
+      v = q == kPpoSums ? fmin(v, x) : q == kPpoSums + 1 ? fmax(v, x) : v + x;
+    }
+    seg[t] = v;
+  }
+  __syncthreads();
+  auto total = [&](int q) {
+    double v = seg[q * kPpoSeg];
+    for (int sg = 1; sg < kPpoSeg; ++sg) {
+      const double x = seg[q * kPpoSeg + sg];
+      v = q == kPpoSums ? fmin(v, x) : q == kPpoSums + 1 ? fmax(v, x) : v + x;
+    }
+    return v;
+  };
+  if (t < width) grad_log_std[t] = (float)(total(kPpoSums + 2 + t) - (double)ent_coef);
+  if (t == 64) {  // (another wave than the one that writes grad_log_std)
+    const double c = fin[0];
+    const double w = c > 0.0 ? 1.0 / c : 0.0;
+    double H = 0.0;
+    for (int k = 0; k < width; ++k) H = H + ((double)log_std[k] + kPpoEntropyConst);
+    const double policy_loss = -(w * total(0));
+    const double value_loss = 0.5 * (w * total(1));
+    const double mean_r = w * total(4), mean_d = w * total(6);
+    const double var_r = w * total(5) - mean_r * mean_r, var_d = w * total(1) - mean_d * mean_d;
+    stats[0] = c;
+    stats[1] = (policy_loss + (double)vf_coef * value_loss) - (double)ent_coef * H;
+    stats[2] = policy_loss;
+    stats[3] = value_loss;
+    stats[4] = H;
+    stats[5] = w * total(2);
+    stats[6] = w * total(3);
+    stats[7] = fin[1];
+    stats[8] = fin[2];
+    stats[9] = 1.0 - var_d / var_r;
+    stats[10] = total(kPpoSums);
+    stats[11] = total(kPpoSums + 1);
+    stats[12] = 0.0;
+    stats[13] = 0.0;
+    stats[14] = 0.0;
+    stats[15] = 0.0;
+  }
+}
+
+}  // namespace pf

@@ -724,6 +724,7 @@ __global__ void __launch_bounds__(256) sample_actions_kernel(const pf_params P, 
 }  // namespace pf
 #include "gae.hpp"
 #include "traj_stats.hpp"
+#include "ppo_loss.hpp"
 
 // ====================================================================== C ABI
 // The env kernel a context runs, chosen once at pf_ctx_create (select_env_kernel).
@@ -757,6 +758,7 @@ struct pf_ctx {
   pf::FwTable* surf_dev;  // pre-combined surface + body constants (scalar-loaded per tick)
   float* policy_dev;      // the specialised QuadX kernel: pf_rollout_policy's packed weights (policy_mlp.hpp), rewritten by every call
   double* ts_scratch;     // contexts with an env task: pf_traj_stats's partial sums between its launches (traj_stats.hpp: ts_scratch_words)
+  double* ppo_scratch;    // every context: pf_ppo_loss's partial sums between its launches (ppo_loss.hpp: kPpoScratchWords)
 };
 static thread_local char g_err[256] = "";
 
@@ -946,6 +948,7 @@ size_t pf_sizeof_buffers(void) { return sizeof(pf_buffers); }
 size_t pf_sizeof_policy(void) { return sizeof(pf_policy); }
 size_t pf_sizeof_gae(void) { return sizeof(pf_gae_args); }
 size_t pf_sizeof_traj_stats(void) { return sizeof(pf_traj_stats_args); }
+size_t pf_sizeof_ppo_loss(void) { return sizeof(pf_ppo_loss_args); }
 const char* pf_last_error(const pf_ctx* ctx) { return ctx ? ctx->err : g_err; }
 
 int pf_ctx_create(const pf_params* params, int n_lanes, int device, uint64_t lane_offset, pf_ctx** out) {
@@ -1008,7 +1011,7 @@ int pf_ctx_create(const pf_params* params, int n_lanes, int device, uint64_t lan
     return fail(nullptr, PF_ERR_ARG, "the contact model's distances, threshold, erp, friction and restitution must be >= 0");
   pf_ctx* c = new (std::nothrow) pf_ctx;
   if (!c) return fail(nullptr, PF_ERR_ARG, "out of host memory");
-  c->P = P; c->n = n_lanes; c->device = device; c->lane0 = lane_offset; c->err[0] = 0; c->launch_ctr = nullptr; c->policy_dev = nullptr; c->ts_scratch = nullptr;
+  c->P = P; c->n = n_lanes; c->device = device; c->lane0 = lane_offset; c->err[0] = 0; c->launch_ctr = nullptr; c->policy_dev = nullptr; c->ts_scratch = nullptr; c->ppo_scratch = nullptr;
   {  // the airframe's worst-case contact count (collider vertices), see pf_params.contact_max_points
     int pts = 0;
     for (int k = 0; k < P.n_boxes; ++k) pts += P.boxes[k].kind == 1 ? 16 : (P.contact_manifold_points >= 8 ? 8 : 4);
@@ -1042,8 +1045,9 @@ int pf_ctx_create(const pf_params* params, int n_lanes, int device, uint64_t lan
     }
     if (e == hipSuccess && fam != env_family::none)
       e = hipMalloc((void**)&c->ts_scratch, sizeof(double) * pf::ts_scratch_words(n_lanes, pf_obs_dim(c)));
+    if (e == hipSuccess) e = hipMalloc((void**)&c->ppo_scratch, sizeof(double) * pf::kPpoScratchWords);
     if (cur >= 0) (void)hipSetDevice(cur);
-    if (e != hipSuccess) { if (c->P_dev) hipFree(c->P_dev); if (c->launch_ctr) hipFree(c->launch_ctr); if (c->policy_dev) hipFree(c->policy_dev); if (c->surf_dev) hipFree(c->surf_dev); if (c->ts_scratch) hipFree(c->ts_scratch); delete c; return hip_fail(nullptr, e, "pf_ctx_create: device parameter block"); }
+    if (e != hipSuccess) { if (c->P_dev) hipFree(c->P_dev); if (c->launch_ctr) hipFree(c->launch_ctr); if (c->policy_dev) hipFree(c->policy_dev); if (c->surf_dev) hipFree(c->surf_dev); if (c->ts_scratch) hipFree(c->ts_scratch); if (c->ppo_scratch) hipFree(c->ppo_scratch); delete c; return hip_fail(nullptr, e, "pf_ctx_create: device parameter block"); }
   }
   if ((fam == env_family::fixedwing_wp || fam == env_family::generic) && (P.task == PF_TASK_HOVER || P.task == PF_TASK_WAYPOINTS) &&
       (P.vehicle == PF_FIXEDWING || P.noise_mode == PF_NOISE_OFF)) {
@@ -1061,7 +1065,7 @@ int pf_ctx_create(const pf_params* params, int n_lanes, int device, uint64_t lan
       e = hipDeviceSynchronize();
     }
     if (cur >= 0) hipSetDevice(cur);
-    if (e != hipSuccess) { if (c->tmpl) hipFree(c->tmpl); if (c->surf_dev) hipFree(c->surf_dev); if (c->ts_scratch) hipFree(c->ts_scratch); hipFree(c->P_dev); delete c; return hip_fail(nullptr, e, "pf_ctx_create: settle template"); }
+    if (e != hipSuccess) { if (c->tmpl) hipFree(c->tmpl); if (c->surf_dev) hipFree(c->surf_dev); if (c->ts_scratch) hipFree(c->ts_scratch); if (c->ppo_scratch) hipFree(c->ppo_scratch); hipFree(c->P_dev); delete c; return hip_fail(nullptr, e, "pf_ctx_create: settle template"); }
   }
   *out = c;
   return PF_OK;
@@ -1074,6 +1078,7 @@ void pf_ctx_destroy(pf_ctx* ctx) {
   if (ctx->tmpl) hipFree(ctx->tmpl);
   if (ctx->surf_dev) hipFree(ctx->surf_dev);
   if (ctx->ts_scratch) hipFree(ctx->ts_scratch);
+  if (ctx->ppo_scratch) hipFree(ctx->ppo_scratch);
   delete ctx;
 }
 int pf_state_groups(const pf_ctx* ctx) {
@@ -1330,6 +1335,58 @@ int pf_traj_stats(pf_ctx* ctx, const pf_traj_stats_args* a, int k_steps, void* s
   }
   hipLaunchKernelGGL(pf::ts_finish_kernel, dim3(1), dim3(pf::kTsFinishBlock), 0, s, scan_part, waves, a->obs ? obs_part : nullptr, (int)grid, D,
                      a->summary, a->ret_moments, a->obs_moments);
+  PF_HIP(ctx, hipGetLastError());
+  return PF_OK;
+}
+int pf_ppo_loss(pf_ctx* ctx, const pf_ppo_loss_args* a, size_t rows, int width, void* stream) {
+  if (!ctx || !a) return fail(ctx, PF_ERR_ARG, "pf_ppo_loss: ctx and the argument block are required");
+  if (rows < 1) return fail(ctx, PF_ERR_ARG, "pf_ppo_loss: rows must be >= 1");
+  if (width < 1 || width > pf::kPpoMaxA) return fail(ctx, PF_ERR_ARG, "pf_ppo_loss: width must be in 1..8");
+  if (!a->mean) return fail(ctx, PF_ERR_ARG, "pf_ppo_loss: mean is required");
+  if (!a->log_std) return fail(ctx, PF_ERR_ARG, "pf_ppo_loss: log_std is required");
+  if (!a->actions) return fail(ctx, PF_ERR_ARG, "pf_ppo_loss: actions is required");
+  if (!a->logp_old) return fail(ctx, PF_ERR_ARG, "pf_ppo_loss: logp_old is required");
+  if (!a->advantages) return fail(ctx, PF_ERR_ARG, "pf_ppo_loss: advantages is required");
+  if (!a->returns) return fail(ctx, PF_ERR_ARG, "pf_ppo_loss: returns is required");
+  if (!a->value) return fail(ctx, PF_ERR_ARG, "pf_ppo_loss: value is required");
+  if (!a->grad_mean) return fail(ctx, PF_ERR_ARG, "pf_ppo_loss: grad_mean is required");
+  if (!a->grad_value) return fail(ctx, PF_ERR_ARG, "pf_ppo_loss: grad_value is required");
+  if (!a->grad_log_std) return fail(ctx, PF_ERR_ARG, "pf_ppo_loss: grad_log_std is required");
+  if (!a->stats) return fail(ctx, PF_ERR_ARG, "pf_ppo_loss: stats is required");
+  if (!(a->clip > 0.0f && a->clip < INFINITY)) return fail(ctx, PF_ERR_ARG, "pf_ppo_loss: clip must be finite and > 0");
+  if (!(a->vf_coef >= 0.0f && a->vf_coef < INFINITY)) return fail(ctx, PF_ERR_ARG, "pf_ppo_loss: vf_coef must be finite and >= 0");
+  if (!(a->ent_coef >= 0.0f && a->ent_coef < INFINITY)) return fail(ctx, PF_ERR_ARG, "pf_ppo_loss: ent_coef must be finite and >= 0");
+  if (a->normalize_advantage != 0 && a->normalize_advantage != 1) return fail(ctx, PF_ERR_ARG, "pf_ppo_loss: normalize_advantage must be 0 or 1");
+  int rc = ensure_device(ctx);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  double* adv_part = ctx->ppo_scratch + pf::kPpoAdvOffset;
+  double* fin = ctx->ppo_scratch + pf::kPpoFinOffset;
+  double* main_part = ctx->ppo_scratch + pf::kPpoMainOffset;
+  // (no valid: the byte loads read the advantages' first M bytes and the mask drops them)
+  const uint8_t* vbytes = a->valid ? a->valid : reinterpret_cast<const uint8_t*>(a->advantages);
+  const uint32_t vmask = a->valid ? 0xFFu : 0u;
+  const unsigned grid = pf::ppo_grid(rows);
+  hipLaunchKernelGGL(pf::ppo_adv_kernel, dim3(grid), dim3(pf::kPpoBlock), 0, s, a->advantages, vbytes, vmask, rows, adv_part);
+  hipLaunchKernelGGL(pf::ppo_adv_finish_kernel, dim3(1), dim3(pf::kPpoBlock), 0, s, adv_part, (int)grid, fin);
+  const pf::PpoK K{a->clip, a->vf_coef, a->normalize_advantage, a->mean, a->log_std, a->actions, a->logp_old, a->advantages, a->returns, a->value,
+                   vbytes, vmask, a->grad_mean, a->grad_value};
+  // (one float4 per row where the rows are four wide and the caller's pointers allow it; the same arithmetic either way)
+  const bool vec = width == 4 && (((uintptr_t)a->actions | (uintptr_t)a->mean | (uintptr_t)a->grad_mean) & 15) == 0;
+  void (*main_kernel)(pf::PpoK, size_t, const double*, double*) = nullptr;
+  switch (width) {
+    case 1: main_kernel = pf::ppo_main_kernel<1, false>; break;
+    case 2: main_kernel = pf::ppo_main_kernel<2, false>; break;
+    case 3: main_kernel = pf::ppo_main_kernel<3, false>; break;
+    case 4: main_kernel = vec ? pf::ppo_main_kernel<4, true> : pf::ppo_main_kernel<4, false>; break;
+    case 5: main_kernel = pf::ppo_main_kernel<5, false>; break;
+    case 6: main_kernel = pf::ppo_main_kernel<6, false>; break;
+    case 7: main_kernel = pf::ppo_main_kernel<7, false>; break;
+    default: main_kernel = pf::ppo_main_kernel<8, false>; break;
+  }
+  hipLaunchKernelGGL(main_kernel, dim3(grid), dim3(pf::kPpoBlock), 0, s, K, rows, (const double*)fin, main_part);
+  hipLaunchKernelGGL(pf::ppo_finish_kernel, dim3(1), dim3(pf::kPpoBlock), 0, s, (const double*)main_part, (int)grid, (const double*)fin, a->log_std, width,
+                     a->vf_coef, a->ent_coef, a->stats, a->grad_log_std);
   PF_HIP(ctx, hipGetLastError());
   return PF_OK;
 }

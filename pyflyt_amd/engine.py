@@ -498,6 +498,68 @@ class BatchEngine:
             L.check(self.lib.pf_traj_stats(self._ctx, C.byref(a), k, self._stream()), self._ctx)
         return (ts["episode_return"] if store_steps else None), (ts["episode_length"] if store_steps else None), ts["summary"]
 
+    def ppo_loss(self, mean, log_std, value, actions, logp_old, advantages, returns, valid=None, clip: float = 0.2, vf_coef: float = 0.5,
+                 ent_coef: float = 0.0, normalize_advantage: bool = True):
+        """pf_ppo_loss: the clipped PPO objective of a diagonal-Gaussian policy, its statistics and its gradients with respect to
+        mean, value and log_std (include/pyflyt_amd.h has the semantics). mean, actions [..., A] of one shape, A in 1..8; value,
+        logp_old, advantages, returns [...] (a trailing axis of 1 is accepted: a critic's output); valid [...] bool / uint8 or None
+        (every row valid); all flattened to M = the product of the leading axes, which need not be k n: a gathered minibatch is a
+        valid input. Returns (grad_mean [M, A], grad_value [M], grad_log_std [A], stats [16] float64): tensors the engine owns,
+        overwritten by the next call with the same M and A (stats and grad_log_std by every call)."""
+        if not torch.is_tensor(mean) or mean.dim() < 1:
+            raise ValueError(f"mean must be a float32 tensor of shape (..., A), got {type(mean).__name__ if not torch.is_tensor(mean) else tuple(mean.shape)}")
+        A = int(mean.shape[-1])
+        if not 1 <= A <= 8:
+            raise ValueError(f"mean's last axis (the action width) must be in 1..8, got {A}")
+        lead = tuple(mean.shape[:-1])
+        M = 1
+        for d in lead:
+            M *= int(d)
+        if M < 1:
+            raise ValueError(f"mean must hold at least one row, got shape {tuple(mean.shape)}")
+
+        def flat(t, shapes, dtypes, name):
+            if not torch.is_tensor(t):
+                raise ValueError(f"{name} is required: a tensor of shape {shapes[0]}, got {type(t).__name__}")
+            if t.dtype not in dtypes or t.device != self.device or not t.is_contiguous() or tuple(t.shape) not in shapes:
+                raise ValueError(f"{name} must be a contiguous {'/'.join(str(d) for d in dtypes)} tensor of shape {shapes[0]} on {self.device}, "
+                                 f"got {t.dtype} {tuple(t.shape)} on {t.device}")
+            return t
+
+        f32, rows = (torch.float32,), (lead, lead + (1,))
+        flat(mean, (tuple(mean.shape),), f32, "mean")
+        flat(actions, (tuple(mean.shape),), f32, "actions")
+        flat(log_std, ((A,),), f32, "log_std")
+        for name, x in (("value", value), ("logp_old", logp_old), ("advantages", advantages), ("returns", returns)):
+            flat(x, rows, f32, name)
+        if valid is not None:
+            flat(valid, rows, (torch.bool, torch.uint8), "valid")
+        for name, x in (("clip", clip), ("vf_coef", vf_coef), ("ent_coef", ent_coef)):
+            if isinstance(x, bool) or not isinstance(x, (int, float)):
+                raise ValueError(f"{name} must be a Python number, got {type(x).__name__}")
+        if not isinstance(normalize_advantage, bool):
+            raise ValueError(f"normalize_advantage must be a bool, got {type(normalize_advantage).__name__}")
+        if not 0.0 < float(clip) < float("inf"):  # (False for a NaN as well)
+            raise ValueError(f"clip must be finite and > 0, got {clip}")
+        for name, x in (("vf_coef", vf_coef), ("ent_coef", ent_coef)):
+            if not 0.0 <= float(x) < float("inf"):
+                raise ValueError(f"{name} must be finite and >= 0, got {x}")
+        o = getattr(self, "_ppo_out", None)
+        if o is None:
+            o = self._ppo_out = dict(M=0, A=0, stats=torch.zeros(16, dtype=torch.float64, device=self.device), calls=0)
+        if o["M"] != M or o["A"] != A:
+            kw = dict(dtype=torch.float32, device=self.device)
+            o.update(M=M, A=A, grad_mean=torch.empty(M, A, **kw), grad_value=torch.empty(M, **kw), grad_log_std=torch.empty(A, **kw))
+        o["calls"] += 1  # (pyflyt_amd.ppo_loss's backward checks that its gradients are still the ones this call wrote)
+        a = L.PfPpoLoss()
+        a.clip, a.vf_coef, a.ent_coef, a.normalize_advantage = float(clip), float(vf_coef), float(ent_coef), int(normalize_advantage)
+        a.mean, a.log_std, a.actions, a.logp_old = _ptr(mean), _ptr(log_std), _ptr(actions), _ptr(logp_old)
+        a.advantages, a.returns, a.value, a.valid = _ptr(advantages), _ptr(returns), _ptr(value), _ptr(valid)
+        a.grad_mean, a.grad_value, a.grad_log_std, a.stats = _ptr(o["grad_mean"]), _ptr(o["grad_value"]), _ptr(o["grad_log_std"]), _ptr(o["stats"])
+        with torch.cuda.device(self.device):
+            L.check(self.lib.pf_ppo_loss(self._ctx, C.byref(a), M, A, self._stream()), self._ctx)
+        return o["grad_mean"], o["grad_value"], o["grad_log_std"], o["stats"]
+
     def body_tick(self, wrench, n_ticks: int = 1):
         """pf_body_tick: the free-body tick alone under a held body-frame wrench [n, 6] (force, torque)."""
         self._aviary_outputs()

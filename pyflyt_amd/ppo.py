@@ -1,0 +1,73 @@
+"""pf_ppo_loss behind torch.autograd: the clipped PPO objective as ONE differentiable call between the outputs of the caller's actor
+and critic and their output-gradients (BatchEngine.ppo_loss; include/pyflyt_amd.h has the semantics)."""
+from __future__ import annotations
+
+import torch
+from torch.autograd.function import once_differentiable
+
+STAT_NAMES = ("valid_rows", "loss", "policy_loss", "value_loss", "entropy", "approx_kl", "clip_fraction", "advantage_mean", "advantage_std",
+              "explained_variance", "ratio_min", "ratio_max")
+
+
+class _PpoLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mean, log_std, value, engine, actions, logp_old, advantages, returns, valid, coefficients):
+        gm, gv, gls, stats = engine.ppo_loss(mean.detach().contiguous(), log_std.detach().contiguous(), value.detach().contiguous(), actions, logp_old,
+                                             advantages, returns, valid=valid, **coefficients)
+        # (the gradients stay in the engine's buffers until backward: the call count tells whether they are still this call's)
+        ctx.engine, ctx.calls = engine, engine._ppo_out["calls"]
+        ctx.shapes = (mean.shape, value.shape)
+        ctx.save_for_backward(gm, gv, gls)
+        stats = stats.clone()  # (the engine's block is overwritten by the next call)
+        ctx.mark_non_differentiable(stats)
+        return stats[1].to(torch.float32), stats
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss, _grad_stats):
+        if ctx.engine._ppo_out["calls"] != ctx.calls:
+            raise RuntimeError("pyflyt_amd.ppo_loss: backward() came after another ppo_loss call on the same engine, which has overwritten "
+                               "this call's gradients; call backward() before the next ppo_loss")
+        gm, gv, gls = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        return (gm.view(ctx.shapes[0]) * grad_loss if need[0] else None, gls * grad_loss if need[1] else None,
+                gv.view(ctx.shapes[1]) * grad_loss if need[2] else None, None, None, None, None, None, None, None)
+
+
+def ppo_loss(env_or_engine, mean, log_std, value, *batch, valid=None, clip: float = 0.2, vf_coef: float = 0.5, ent_coef: float = 0.0,
+             normalize_advantage: bool = True):
+    """loss, stats = ppo_loss(env, actor(obs), log_std, critic(obs), batch) with `batch` the dict env.collect returned (its actions,
+    logp, advantages, returns and valid, flattened and used whole), or ppo_loss(env, mean, log_std, value, actions, logp_old,
+    advantages, returns, valid=...) with explicit tensors such as a gathered minibatch. `loss` is a float32 scalar on the device
+    (policy_loss + vf_coef * value_loss - ent_coef * entropy over the valid rows) whose backward() hands mean, log_std and value
+    their gradients; `stats` is the [16] float64 device tensor of pf_ppo_loss (ppo_stats_dict names it). Nothing synchronises with
+    the host. A deliberate trade: the gradients wait in buffers the engine owns and are NOT copied for backward (a copy would move
+    another 40 bytes per row next to a pass of 74), so backward() must come before the next ppo_loss on the same env or engine; a
+    later one raises RuntimeError, whatever that next call's shape was, and never uses overwritten gradients. Two losses from one
+    engine that are both to be backpropagated need .backward() after each, or an engine each."""
+    engine = getattr(env_or_engine, "engine", env_or_engine)
+    if not hasattr(engine, "ppo_loss"):
+        raise ValueError(f"the first argument must be a vector env or a BatchEngine, got {type(env_or_engine).__name__}")
+    if len(batch) == 1 and isinstance(batch[0], dict):
+        b = batch[0]
+        missing = [k for k in ("actions", "logp", "advantages", "returns") if b.get(k) is None]
+        if missing:
+            raise ValueError(f"the batch lacks {missing} (env.collect returns logp only for a policy with a log_std)")
+        if valid is not None:
+            raise ValueError("valid comes from the batch dict; give it only with explicit tensors")
+        actions, logp_old, advantages, returns, valid = b["actions"], b["logp"], b["advantages"], b["returns"], b.get("valid")
+        mean, value = mean.reshape(actions.shape), value.reshape(advantages.shape)  # ([k n, A] and [k n, 1] from the networks)
+    elif len(batch) == 4:
+        actions, logp_old, advantages, returns = batch
+    else:
+        raise ValueError("give the dict env.collect returned, or the four tensors actions, logp_old, advantages, returns")
+    coefficients = dict(clip=clip, vf_coef=vf_coef, ent_coef=ent_coef, normalize_advantage=normalize_advantage)
+    return _PpoLoss.apply(mean, log_std, value, engine, actions, logp_old, advantages, returns, valid, coefficients)
+
+
+def ppo_stats_dict(stats):
+    """The [16] stats tensor of ppo_loss as Python numbers by name (THE place that synchronises with the device)."""
+    values = stats.tolist()
+    out = dict(zip(STAT_NAMES, values))
+    out["valid_rows"] = int(out["valid_rows"])
+    return out
