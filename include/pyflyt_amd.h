@@ -432,6 +432,33 @@ typedef struct pf_policy {
 size_t pf_sizeof_policy(void);
 int pf_rollout_policy(pf_ctx* ctx, const pf_buffers* b, const pf_policy* policy, int k_steps, uint32_t step_index0, void* stream);
 
+/* The policy of pf_rollout_policy as a launch of its own: rows in, rows out, for ANY context with an env task -- the closed loop
+ * k x (pf_policy_act, pf_env_step) where pf_rollout_policy has no instantiation (Fixedwing-Waypoints, Rocket-Landing, the dogfight
+ * and the multi-agent hover, the cascaded flight modes, the generic kernel, the 8-point manifold). (Added without a new
+ * PF_ABI_VERSION: a new function; pf_policy is used as it is.)
+ *   - ARGUMENTS: policy->obs0 the [n][D] input rows, D = pf_obs_dim(ctx) (at most 128; the widest env, an eight-aircraft dogfight
+ *     with six-wide actions, has 123); actions_out [n][A], required; policy->mean_out [n][A] or NULL. A is the context's action
+ *     width: 4, 6 (PF_TASK_DOGFIGHT with df_action_dim 6) or 7 (PF_TASK_ROCKET_LANDING); the last layer's `out` must equal it.
+ *   - THE MLP is pf_rollout_policy's, word for word: 2 or 3 affine layers, hidden widths 1..PF_POLICY_MAX_HIDDEN, tanh or ReLU,
+ *     torch.nn.Linear's [out][in] layout, read at every call. Every sum starts with the bias, then takes the inputs in ascending
+ *     index with one fused multiply-add each, in float32 (computed by the float32-input matrix instruction, which is that chain bit
+ *     for bit); the same float32 tanh, exp(log_std) from the same expf, a_c = fmaf(std_c, eps_c, mean_c). No clipping.
+ *   - NOISE: the same draw -- ONE Philox call per lane keyed by (seed, global lane, step_index, 0), stream constant 4; eps_c is
+ *     normal c of the call's eight for c < A, so six- and seven-wide heads use normals 4-6 of the same call. log_std == NULL: no
+ *     call, a = mean exactly.
+ *   - CONSEQUENCE: on a context that pf_rollout_policy serves, k x (pf_policy_act(step_index0 + s) on the current observation, then
+ *     pf_env_step on actions_out) gives the same actions, means, observations, rewards, flags and state as
+ *     pf_rollout_policy(k, step_index0).
+ *   - NO RESTRICTION on vehicle, kernel family, flight mode, noise mode, auto-reset mode or manifold: it only maps rows to rows.
+ *     obs0 and the outputs must not overlap.
+ *   - ERRORS: PF_ERR_UNSUPPORTED for a context without an env task or a hidden width over PF_POLICY_MAX_HIDDEN; PF_ERR_ARG, the
+ *     argument named, for a NULL policy / obs0 / actions_out / layer's w or b, n_layers not 2 or 3, a width below 1, an unknown
+ *     activation.
+ *   - Enqueued on `stream`: no host synchronisation, no allocation, no copy -- capturable in a HIP graph. The call keeps nothing in
+ *     the context (no packed block: the kernel stages the caller's tensors itself), so calls on one context may run on different
+ *     streams as long as their outputs are distinct. */
+int pf_policy_act(pf_ctx* ctx, const pf_policy* policy, float* actions_out, uint32_t step_index, void* stream);
+
 /* What an on-policy learner needs for every step of a rollout's trajectory before it can take a gradient step: which steps are real
  * transitions, advantages and returns by generalised advantage estimation (GAE) with the bootstrap that tells terminated from
  * truncated, and the log-probability of the action taken. Reads the trajectory buffers of pf_rollout / pf_rollout_policy (k_steps

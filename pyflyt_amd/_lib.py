@@ -134,6 +134,7 @@ def lib():
     L.pf_body_tick.argtypes = [C.c_void_p, C.POINTER(PfBuffers), C.c_int, C.c_void_p]
     L.pf_rollout_policy.argtypes = [C.c_void_p, C.POINTER(PfBuffers), C.POINTER(PfPolicy), C.c_int, C.c_uint32, C.c_void_p]
     L.pf_sizeof_policy.restype = C.c_size_t
+    L.pf_policy_act.argtypes = [C.c_void_p, C.POINTER(PfPolicy), C.c_void_p, C.c_uint32, C.c_void_p]
     L.pf_gae.argtypes = [C.c_void_p, C.POINTER(PfGae), C.c_int, C.c_void_p]
     L.pf_sizeof_gae.restype = C.c_size_t
     L.pf_traj_stats.argtypes = [C.c_void_p, C.POINTER(PfTrajStats), C.c_int, C.c_void_p]

@@ -725,6 +725,7 @@ __global__ void __launch_bounds__(256) sample_actions_kernel(const pf_params P, 
 #include "gae.hpp"
 #include "traj_stats.hpp"
 #include "ppo_loss.hpp"
+#include "policy_act.hpp"
 
 // ====================================================================== C ABI
 // The env kernel a context runs, chosen once at pf_ctx_create (select_env_kernel).
@@ -759,6 +760,7 @@ struct pf_ctx {
   float* policy_dev;      // the specialised QuadX kernel: pf_rollout_policy's packed weights (policy_mlp.hpp), rewritten by every call
   double* ts_scratch;     // contexts with an env task: pf_traj_stats's partial sums between its launches (traj_stats.hpp: ts_scratch_words)
   double* ppo_scratch;    // every context: pf_ppo_loss's partial sums between its launches (ppo_loss.hpp: kPpoScratchWords)
+  int act_grid_cap;       // pf_policy_act: the most workgroups a launch takes, two per CU of the device: what its registers admit (two waves per SIMD; profiles/policy_act/resources.txt) (policy_act.hpp)
 };
 static thread_local char g_err[256] = "";
 
@@ -1020,6 +1022,11 @@ int pf_ctx_create(const pf_params* params, int n_lanes, int device, uint64_t lan
   c->P_dev = nullptr; c->tmpl = nullptr; c->surf_dev = nullptr;
   pf::FwTable fsurf;
   c->ek = select_env_kernel(P, n_lanes, device, c->K, c->FK, fsurf);
+  {
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus < 1) cus = 256;
+    c->act_grid_cap = 2 * cus;
+  }
   const env_family fam = c->ek.family;
   {  // device copy of the parameter block (LDS constant tables, the out-of-line floor test)
     int cur = -1;
@@ -1250,6 +1257,35 @@ int pf_rollout_policy(pf_ctx* ctx, const pf_buffers* b, const pf_policy* q, int 
   const int grid = (ctx->n + 64 * pf::kQuadWPB - 1) / (64 * pf::kQuadWPB);
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * pf::kQuadWPB), 0, s, ctx->K, *b, ctx->P_dev, ctx->n, ctx->lane0, (int)pf::OP_STEP, (const uint8_t*)nullptr,
                      k_steps, step_index0, ctx->launch_ctr, PK);
+  PF_HIP(ctx, hipGetLastError());
+  return PF_OK;
+}
+int pf_policy_act(pf_ctx* ctx, const pf_policy* q, float* actions_out, uint32_t step_index, void* stream) {
+  if (!ctx) return fail(ctx, PF_ERR_ARG, "pf_policy_act: ctx is required");
+  if (!q) return fail(ctx, PF_ERR_ARG, "pf_policy_act: policy is required");
+  const pf_params& P = ctx->P;
+  if (P.task == PF_TASK_NONE) return fail(ctx, PF_ERR_UNSUPPORTED, "pf_policy_act: needs a context with an env task (this one drives the Aviary level only)");
+  if (!actions_out) return fail(ctx, PF_ERR_ARG, "pf_policy_act: actions_out is required");
+  if (!q->obs0) return fail(ctx, PF_ERR_ARG, "pf_policy_act: obs0 (the [n][pf_obs_dim()] input rows) is required");
+  if (q->n_layers != 2 && q->n_layers != 3) return fail(ctx, PF_ERR_ARG, "pf_policy_act: n_layers must be 2 or 3");
+  for (int l = 0; l + 1 < q->n_layers; ++l) {
+    if (q->width[l] > PF_POLICY_MAX_HIDDEN) return fail(ctx, PF_ERR_UNSUPPORTED, "pf_policy_act: hidden widths over PF_POLICY_MAX_HIDDEN (64) are not supported");
+    if (q->width[l] < 1) return fail(ctx, PF_ERR_ARG, "pf_policy_act: hidden widths must be >= 1");
+  }
+  if (q->activation != PF_ACT_TANH && q->activation != PF_ACT_RELU) return fail(ctx, PF_ERR_ARG, "pf_policy_act: activation must be PF_ACT_TANH or PF_ACT_RELU");
+  for (int l = 0; l < q->n_layers; ++l)
+    if (!q->w[l] || !q->b[l]) return fail(ctx, PF_ERR_ARG, "pf_policy_act: every layer needs w and b");
+  const int D = pf_obs_dim(ctx);
+  if (D > pf::kActMaxIn) return fail(ctx, PF_ERR_UNSUPPORTED, "pf_policy_act: observation wider than 128");
+  const int A = P.task == PF_TASK_ROCKET_LANDING ? pf::kRlActionDim : (P.task == PF_TASK_DOGFIGHT && P.df_action_dim == 6) ? 6 : 4;
+  static_assert(pf::kRlActionDim <= pf::kActMaxA, "the output layer's block holds the widest action");
+  int rc = ensure_device(ctx);
+  if (rc) return rc;
+  const pf::ActK AK{*q, actions_out, ctx->n, D, A, (uint32_t)P.seed, (uint32_t)(P.seed >> 32), step_index, ctx->lane0};
+  // workgroups stride over the 64-row tiles, two per CU at the most (all resident): the weight staging is paid once per workgroup
+  const int tiles = (ctx->n + pf::kActRows - 1) / pf::kActRows;
+  const int grid = tiles < ctx->act_grid_cap ? tiles : ctx->act_grid_cap;
+  hipLaunchKernelGGL(pf::policy_act_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, AK);
   PF_HIP(ctx, hipGetLastError());
   return PF_OK;
 }

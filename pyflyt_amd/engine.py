@@ -295,7 +295,7 @@ class BatchEngine:
         (obs [k, n, D], reward [k, n], terminated [k, n], truncated [k, n], actions [k, n, 4]) -- the same tensors as rollout(),
         overwritten by the next call -- and, with store_mean, the policy's means [k, n, 4] as a sixth. `step_index0` keys the
         exploration noise: advance it by k between calls. QuadX-Hover / QuadX-Waypoints on the specialised kernel; everything else
-        raises PyFlytAmdError with the library's message."""
+        raises PyFlytAmdError with the library's message -- rollout_policy_steps is the same loop on every env."""
         from .policy import MLPPolicy
 
         if not isinstance(policy, MLPPolicy):
@@ -321,6 +321,112 @@ class BatchEngine:
         out = (t["obs"], t["reward"], t["terminated"], t["truncated"], t["actions"])
         return out + (mean,) if store_mean else out
 
+    def policy_act(self, policy, step_index: int = 0, obs=None, out=None, mean_out=None):
+        """pf_policy_act: `policy` (an MLPPolicy) on `obs` [n, D] (default: the engine's current observation) in one launch, on any
+        engine with an env task. Returns the actions [n, action_dim] (`out`, or a new tensor), and with `mean_out` [n, action_dim]
+        the pair (actions, mean_out). The same network arithmetic and the same draw as rollout_policy's step `step_index`:
+        k x (policy_act(step_index0 + s), env_step) is rollout_policy(k, step_index0) bit for bit where that exists."""
+        from .policy import MLPPolicy
+
+        if not isinstance(policy, MLPPolicy):
+            raise ValueError(f"policy must be a pyflyt_amd.MLPPolicy, got {type(policy).__name__}")
+        q = policy.fill(L.PfPolicy(), self)
+        obs = self._cur_obs if obs is None else self._check_f32(obs, (self.n, self.obs_dim), "obs")
+        if out is None:
+            out = torch.empty(self.n, self.action_dim, dtype=torch.float32, device=self.device)
+        self._check_f32(out, (self.n, self.action_dim), "out")
+        self._check_f32(mean_out, (self.n, self.action_dim), "mean_out")
+        q.obs0 = obs.data_ptr()
+        q.mean_out = _ptr(mean_out)
+        with torch.cuda.device(self.device):
+            L.check(self.lib.pf_policy_act(self._ctx, C.byref(q), _ptr(out), int(step_index) & 0xFFFFFFFF, self._stream()), self._ctx)
+        return out if mean_out is None else (out, mean_out)
+
+    def rollout_policy_steps(self, policy, k_steps: int, step_index0: int = 0, store_mean: bool = False):
+        """rollout_policy, step by step: k x (pf_policy_act, pf_env_step) into the same trajectory tensors, the same return value.
+        Two launches per step instead of one for the whole rollout, on every single-agent env: QuadX, Fixedwing-Waypoints and
+        Rocket-Landing, the cascaded flight modes, the generic kernel, the 8-point manifold. Each env step writes straight into its
+        trajectory rows (final_obs / final_info rows included under SAME_STEP): nothing is copied. Where rollout_policy runs, the
+        results are bit-identical. Needs an auto-reset mode and PF_NOISE_OFF / PF_NOISE_PHILOX (ValueError otherwise) -- so the
+        multi-agent tasks (dogfight, multi-agent hover), which exist with auto-reset OFF only, are refused here: their loop is
+        policy_act and env_step, with the culling of finished agents in between."""
+        from .policy import MLPPolicy
+
+        if not isinstance(policy, MLPPolicy):
+            raise ValueError(f"policy must be a pyflyt_amd.MLPPolicy, got {type(policy).__name__}")
+        k = int(k_steps)
+        if k < 1:
+            raise ValueError(f"k_steps must be >= 1, got {k_steps}")
+        self._check_stepwise()
+        q = policy.fill(L.PfPolicy(), self)
+        t = getattr(self, "_traj", None)
+        if t is None or t["k"] != k or t["actions"].shape[-1] != self.action_dim:  # (rollout()'s trajectory tensors, shared with it)
+            f32 = dict(dtype=torch.float32, device=self.device)
+            t = dict(k=k, obs=torch.empty(k, self.n, self.obs_dim, **f32), reward=torch.empty(k, self.n, **f32),
+                     terminated=torch.empty(k, self.n, dtype=torch.bool, device=self.device),
+                     truncated=torch.empty(k, self.n, dtype=torch.bool, device=self.device),
+                     actions=torch.empty(k, self.n, self.action_dim, **f32),
+                     final_obs=torch.zeros(k, self.n, self.obs_dim, **f32) if self.final_obs is not None else None,
+                     final_info=torch.zeros(k, self.n, 2, dtype=torch.int32, device=self.device) if self.final_info is not None else None)
+            self._traj = t
+        mean = None
+        if store_mean:
+            mean = t.get("mean")
+            if mean is None or mean.shape[-1] != self.action_dim:
+                mean = t["mean"] = torch.empty(k, self.n, self.action_dim, dtype=torch.float32, device=self.device)
+        self._launch_policy_steps(q, t, k, step_index0, mean)
+        out = (t["obs"], t["reward"], t["terminated"], t["truncated"], t["actions"])
+        return out + (mean,) if store_mean else out
+
+    def _check_stepwise(self):
+        """What the stepwise closed loop cannot run, refused before any launch."""
+        if self.params.task == L.TASK_NONE:
+            raise ValueError("the stepwise policy rollout needs an engine with an env task")
+        if self.params.autoreset == L.AUTORESET_OFF:
+            raise ValueError("the stepwise policy rollout needs an auto-reset mode (auto-reset disabled: finished lanes would idle for the rest of the rollout)")
+        if self.params.noise_mode == L.NOISE_INJECT:
+            raise ValueError("the stepwise policy rollout runs under PF_NOISE_OFF / PF_NOISE_PHILOX (PF_NOISE_INJECT passes per-step noise tensors; use policy_act and env_step)")
+
+    def _fused_policy(self, fused):
+        """Which closed loop a `fused` argument selects: None = the fused launch where the library has one for the vehicle and task
+        (QuadX-Hover / QuadX-Waypoints, with all its refusals), the stepwise path everywhere else."""
+        if fused is None:
+            return self.params.vehicle == L.QUADX and self.params.task in (L.TASK_HOVER, L.TASK_WAYPOINTS)
+        if not isinstance(fused, bool):
+            raise ValueError(f"fused must be None, True or False, got {fused!r}")
+        return fused
+
+    def _launch_policy_steps(self, q, t, k, step_index0, mean):
+        """k x (pf_policy_act, pf_env_step) into the trajectory tensors `t`, acting first on the engine's current observation: the
+        act of step s reads the row the env wrote at step s - 1, the env's buffer block points at the rows of step s."""
+        b = self._buffers()
+        act, step, ctx, qref, bref = self.lib.pf_policy_act, self.lib.pf_env_step, self._ctx, C.byref(q), C.byref(b)
+        n, D, A = self.n, self.obs_dim, self.action_dim
+        p_obs, p_act, p_rew = t["obs"].data_ptr(), t["actions"].data_ptr(), t["reward"].data_ptr()
+        p_term, p_trunc = t["terminated"].data_ptr(), t["truncated"].data_ptr()
+        p_fobs = t["final_obs"].data_ptr() if t["final_obs"] is not None else None
+        p_finfo = t["final_info"].data_ptr() if t["final_info"] is not None else None
+        p_mean = mean.data_ptr() if mean is not None else None
+        cur = self._cur_obs.data_ptr()
+        with torch.cuda.device(self.device):
+            stream = self._stream()
+            for s in range(k):
+                q.obs0 = cur
+                q.mean_out = p_mean + 4 * n * A * s if p_mean is not None else None
+                a = p_act + 4 * n * A * s
+                rc = act(ctx, qref, a, (int(step_index0) + s) & 0xFFFFFFFF, stream)
+                if rc:
+                    L.check(rc, ctx)
+                cur = p_obs + 4 * n * D * s
+                b.actions, b.obs, b.reward = a, cur, p_rew + 4 * n * s
+                b.terminated, b.truncated = p_term + n * s, p_trunc + n * s
+                if p_fobs is not None:
+                    b.final_obs, b.final_info = p_fobs + 4 * n * D * s, p_finfo + 8 * n * s
+                rc = step(ctx, bref, stream)
+                if rc:
+                    L.check(rc, ctx)
+        self._cur_obs = t["obs"][k - 1]
+
     def _launch_policy(self, q, t, k, step_index0, mean):
         """pf_rollout_policy into the trajectory tensors `t`, acting first on the engine's current observation."""
         q.obs0 = self._cur_obs.data_ptr()
@@ -332,8 +438,10 @@ class BatchEngine:
             L.check(self.lib.pf_rollout_policy(self._ctx, C.byref(b), C.byref(q), k, int(step_index0) & 0xFFFFFFFF, self._stream()), self._ctx)
         self._cur_obs = t["obs"][k - 1]
 
-    def collect_rollout(self, policy, k_steps: int, step_index0: int = 0):
-        """rollout_policy for a learner: the same launch into trajectory tensors of its own whose observations live in ONE buffer
+    def collect_rollout(self, policy, k_steps: int, step_index0: int = 0, fused=None):
+        """rollout_policy for a learner: the same launch (`fused`: None = where the library has it, QuadX-Hover / QuadX-Waypoints, and
+        rollout_policy_steps' k x (pf_policy_act, pf_env_step) on every other env; True = the fused launch or its refusal; False =
+        the stepwise path -- the act of step s reads row s, the env writes row s + 1) into trajectory tensors of its own whose observations live in ONE buffer
         `obs_all` [k + 1, n, D]. Row 0 is the observation the first step acts on (an n x D copy of the engine's current observation),
         the launch writes rows 1 .. k: obs_all[:-1] are the policy's inputs and obs_all[1:] the next observations, both views -- the
         trajectory is never copied. Returns the dict of tensors (obs_all, obs = obs_all[1:], reward, terminated, truncated, actions,
@@ -345,6 +453,9 @@ class BatchEngine:
         k = int(k_steps)
         if k < 1:
             raise ValueError(f"k_steps must be >= 1, got {k_steps}")
+        fused = self._fused_policy(fused)
+        if not fused:
+            self._check_stepwise()
         q = policy.fill(L.PfPolicy(), self)
         t = getattr(self, "_ctraj", None)
         if t is None or t["k"] != k:
@@ -361,7 +472,7 @@ class BatchEngine:
         t["obs_all"][0].copy_(cur)  # (the previous call's last row, in this buffer or another, or self.obs)
         self._cur_obs = t["obs_all"][0]
         try:
-            self._launch_policy(q, t, k, step_index0, t["mean"])
+            (self._launch_policy if fused else self._launch_policy_steps)(q, t, k, step_index0, t["mean"])
         except L.PyFlytAmdError:  # (refused: the engine's current observation is where it was)
             self._cur_obs = cur
             raise

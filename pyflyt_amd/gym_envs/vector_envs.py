@@ -199,24 +199,34 @@ class _VecEnvBase:
             return self._obs(self.engine.obs), r[1], r[2], r[3], r[4]
         return self._ret
 
-    def rollout(self, policy, k_steps: int, store_mean: bool = False):
-        """`k_steps` closed-loop env steps in ONE launch, every action computed on the device by `policy` (a pyflyt_amd.MLPPolicy)
-        from the observation the env has just returned (BatchEngine.rollout_policy). Returns the trajectories (obs [k, n, D] -- the
-        engine's flat observation rows, what the policy reads --, reward, terminated, truncated, actions [k, n, 4]) and the infos
-        of the LAST step (with store_mean the policy's means before them). The exploration noise's step index advances by k_steps
-        per call and restarts with reset(seed=...)."""
+    def rollout(self, policy, k_steps: int, store_mean: bool = False, fused=None):
+        """`k_steps` closed-loop env steps, every action computed on the device by `policy` (a pyflyt_amd.MLPPolicy) from the
+        observation the env has just returned. Returns the trajectories (obs [k, n, D] -- the engine's flat observation rows, what
+        the policy reads --, reward, terminated, truncated, actions [k, n, action width]) and the infos of the LAST step (with
+        store_mean the policy's means before them). The exploration noise's step index advances by k_steps per call and restarts
+        with reset(seed=...).
+        `fused`: None (default) = ONE launch (BatchEngine.rollout_policy) on QuadX-Hover and QuadX-Waypoints, with that launch's
+        refusals, and the stepwise path on every other vehicle or task; True = the fused launch, or the library's refusal;
+        False = the stepwise path, k x (pf_policy_act, pf_env_step) (BatchEngine.rollout_policy_steps), on any env -- how a
+        cascaded flight mode, the generic kernel or the 8-point manifold get a closed loop. The stepwise path needs an auto-reset
+        mode (ValueError). Where both exist they give the same bits."""
         if self._needs_reset:
             raise RuntimeError("call reset() before rollout()")
         k = int(k_steps)
-        out = self.engine.rollout_policy(policy, k, step_index0=self._policy_step, store_mean=store_mean)
+        if self.engine._fused_policy(fused):
+            out = self.engine.rollout_policy(policy, k, step_index0=self._policy_step, store_mean=store_mean)
+        else:
+            out = self.engine.rollout_policy_steps(policy, k, step_index0=self._policy_step, store_mean=store_mean)
         self._policy_step = (self._policy_step + k) & 0xFFFFFFFF
         self._infos_obj.invalidate()
         if self._final_infos is not None:
             self._final_infos.invalidate()
         return out + (self._infos_obj,)
 
-    def collect(self, policy, value_fn, k_steps: int, gamma: float = 0.99, lam: float = 0.95, stats: bool = False, normalize_reward: bool = False):
-        """One PPO batch from `k_steps` closed-loop env steps: the rollout launch of rollout(), the caller's value network, and
+    def collect(self, policy, value_fn, k_steps: int, gamma: float = 0.99, lam: float = 0.95, stats: bool = False, normalize_reward: bool = False,
+                fused=None):
+        """One PPO batch from `k_steps` closed-loop env steps: the closed loop of rollout() (`fused` as there: one launch on
+        QuadX-Hover / QuadX-Waypoints, the stepwise path on every other env), the caller's value network, and
         pf_gae (BatchEngine.gae) -- obs -> policy -> env -> batch ready for the loss, without a host synchronisation.
         `value_fn`: any torch callable from a float32 [M, D] tensor to [M] or [M, 1] (float32); it is called under torch.no_grad(),
         once on all k + 1 observation rows and, under SAME_STEP auto-reset, once more on the final_obs trajectory.
@@ -250,11 +260,13 @@ class _VecEnvBase:
             if not 0.0 <= float(x) <= 1.0:
                 raise ValueError(f"{name} must be finite and in [0, 1], got {x}")
         eng, k = self.engine, int(k_steps)
+        if not eng._fused_policy(fused):  # (refused before the flags are read or anything is launched)
+            eng._check_stepwise()
         episode_start = None
         if eng.params.autoreset == L.AUTORESET_NEXT_STEP:
             # lanes whose last step ended an episode: the launch's first step only resets them (read before the launch rewrites the flags)
             episode_start = (eng.flags() & (L.F_TERMINATED | L.F_TRUNCATED)) != 0
-        t = eng.collect_rollout(policy, k, step_index0=self._policy_step)
+        t = eng.collect_rollout(policy, k, step_index0=self._policy_step, fused=fused)
         self._policy_step = (self._policy_step + k) & 0xFFFFFFFF
         self._infos_obj.invalidate()
         if self._final_infos is not None:

@@ -1,5 +1,6 @@
 """MLPPolicy: the small policy network that BatchEngine.rollout_policy evaluates on the device, per lane, between two env steps of
-one launch (pf_rollout_policy, include/pyflyt_amd.h).
+one launch (pf_rollout_policy, include/pyflyt_amd.h), and that BatchEngine.policy_act evaluates for all lanes in a launch of its own
+(pf_policy_act: every env, action widths 4, 6 and 7).
 
 The policy HOLDS REFERENCES to the parameter tensors it is given, not copies: the library reads them at every rollout, so an
 optimiser step that updates them in place is seen by the next rollout without any call. The one exception is observation
