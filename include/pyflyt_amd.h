@@ -618,6 +618,53 @@ typedef struct pf_ppo_loss_args {
 size_t pf_sizeof_ppo_loss(void);
 int pf_ppo_loss(pf_ctx* ctx, const pf_ppo_loss_args* a, size_t rows, int width, void* stream);
 
+/* The two networks of a PPO epoch without a GEMM library: a small MLP over any number of rows, and from the output-gradients of those
+ * rows (pf_ppo_loss's grad_mean / grad_value) the gradients of every weight and bias. With them an epoch is pf_mlp_forward ->
+ * pf_ppo_loss -> pf_mlp_backward -> the optimiser's step, and no hidden activation is ever written to memory. The context serves its
+ * device and pf_last_error only: any context works, with an env task or without. (Added without a new PF_ABI_VERSION: new functions;
+ * pf_policy and every other struct as they were.)
+ *   - THE NETWORK is pf_policy_act's family: 2 or 3 affine layers, hidden widths 1..PF_POLICY_MAX_HIDDEN, tanh or ReLU between them,
+ *     torch.nn.Linear's [out][in] layout, read at every call; in_dim 1..128, out_dim 1..8 (the critic's 1 included).
+ *   - FORWARD. out[r] = MLP(x[r]) for x [rows][in_dim], out [rows][out_dim], with pf_policy_act's arithmetic word for word -- it is
+ *     the same kernel, launched with the draw off: every sum starts with the bias, then takes the inputs in ascending index with one
+ *     float32 fused multiply-add each; the same float32 tanh. For in_dim = pf_obs_dim(), out_dim = the action width and the same
+ *     rows, `out` holds the bits of pf_policy_act's mean_out.
+ *   - BACKWARD. grad_w[l][j][i] = sum over the rows r of delta_l[r][j] * in_l[r][i], grad_b[l][j] = sum_r delta_l[r][j], where in_0 = x,
+ *     in_l = h_(l-1) = act(layer l - 1), delta_last = grad_out [rows][out_dim], delta_l = (delta_(l+1) W_(l+1)) * act'(h_l),
+ *     act' = 1 - h^2 for tanh and (h > 0 ? 1 : 0) for ReLU. The hidden activations are computed again from x: the forward saves
+ *     nothing and there is no state between the two calls. No gradient is produced for x.
+ *   - ARITHMETIC. float32 on the float32-input matrix instruction. Each 64-row tile's products start from zero and are added to its
+ *     workgroup's running float32 sums; a workgroup writes one block of partial sums to `workspace`, and a second launch adds the
+ *     workgroups' blocks in ascending order in double and rounds to float32. The grid is a function of `rows` alone and there are
+ *     no atomics: the same call on the same inputs gives the same bits on any stream and at every repetition.
+ *   - ZERO ROWS. A row whose grad_out is all +0 contributes exact zeros, PROVIDED ITS x IS FINITE: the row's activations are still
+ *     computed and multiplied by the zero deltas, so a NaN or an infinity in x poisons the sums even under a zero gradient (0 * NaN).
+ *     pf_ppo_loss's zeroed invalid rows are safe: the reset rows of a NEXT_STEP trajectory hold finite terminal observations. Rows
+ *     past `rows` are never read: the ragged last tile masks its deltas to zero.
+ *   - WORKSPACE. The caller's, at least pf_mlp_backward_workspace_bytes(mlp, rows) bytes (a pure host function of the network's shape
+ *     and of rows: it grows with rows up to the grid's cap and is constant from there; 0 for a shape the calls refuse). Its contents
+ *     mean nothing before or after the call.
+ *   - ERRORS. PF_ERR_ARG, pf_last_error naming the argument: a NULL ctx, mlp, x, out, grad_out, grad_w, grad_b, workspace, layer's w /
+ *     b / grad_w / grad_b; rows < 1 (or 2^31 - 64 and more); n_layers not 2 or 3; a width outside 1..64; in_dim outside 1..128;
+ *     out_dim outside 1..8; an unknown activation; workspace_bytes too small (refused by size, before any launch); x, grad_out,
+ *     workspace or an output overlapping one another (forward: x and out).
+ *   - Enqueued on `stream`: one launch (forward), two (backward); no host synchronisation, no allocation, no copy -- capturable in a
+ *     HIP graph. Calls on one context may run on different streams as long as their outputs and workspaces are distinct. */
+typedef struct pf_mlp {
+  int32_t n_layers;      /* 2 or 3 affine layers = 1 or 2 hidden layers */
+  int32_t width[2];      /* hidden widths, 1..PF_POLICY_MAX_HIDDEN */
+  int32_t activation;    /* pf_activation, on the hidden layers; the output layer is affine */
+  int32_t in_dim;        /* 1..128 */
+  int32_t out_dim;       /* 1..8 */
+  const float* w[3];     /* device, row-major [out][in] = torch.nn.Linear.weight */
+  const float* b[3];     /* device, [out] */
+} pf_mlp;
+size_t pf_sizeof_mlp(void);
+int pf_mlp_forward(pf_ctx* ctx, const pf_mlp* mlp, const float* x, int64_t rows, float* out, void* stream);
+size_t pf_mlp_backward_workspace_bytes(const pf_mlp* mlp, int64_t rows);
+int pf_mlp_backward(pf_ctx* ctx, const pf_mlp* mlp, const float* x, const float* grad_out, int64_t rows, float* const grad_w[3],
+                    float* const grad_b[3], void* workspace, size_t workspace_bytes, void* stream);
+
 /* The reference's LOWER boundary for one drone: applyExternalForce / applyExternalTorque on the base link in
  * LINK_FRAME followed by stepSimulation (core/drones/quadx.py:502-510, core/aviary.py:516), n_ticks times with
  * the wrench b->wrench held: the free-body tick alone (collision detection, gyroscopic term, +-max_coord_vel

@@ -10,6 +10,7 @@ from .params import build_params
 from .moments import RunningMoments
 from .policy import MLPPolicy
 from .ppo import ppo_loss, ppo_stats_dict
+from .nets import mlp
 
-__all__ = ["_lib", "PyFlytAmdError", "build_params", "MLPPolicy", "RunningMoments", "ppo_loss", "ppo_stats_dict"]
+__all__ = ["_lib", "PyFlytAmdError", "build_params", "MLPPolicy", "RunningMoments", "ppo_loss", "ppo_stats_dict", "mlp"]
 __version__ = "0.1.0"

@@ -726,6 +726,7 @@ __global__ void __launch_bounds__(256) sample_actions_kernel(const pf_params P, 
 #include "traj_stats.hpp"
 #include "ppo_loss.hpp"
 #include "policy_act.hpp"
+#include "mlp.hpp"
 
 // ====================================================================== C ABI
 // The env kernel a context runs, chosen once at pf_ctx_create (select_env_kernel).
@@ -951,6 +952,7 @@ size_t pf_sizeof_policy(void) { return sizeof(pf_policy); }
 size_t pf_sizeof_gae(void) { return sizeof(pf_gae_args); }
 size_t pf_sizeof_traj_stats(void) { return sizeof(pf_traj_stats_args); }
 size_t pf_sizeof_ppo_loss(void) { return sizeof(pf_ppo_loss_args); }
+size_t pf_sizeof_mlp(void) { return sizeof(pf_mlp); }
 const char* pf_last_error(const pf_ctx* ctx) { return ctx ? ctx->err : g_err; }
 
 int pf_ctx_create(const pf_params* params, int n_lanes, int device, uint64_t lane_offset, pf_ctx** out) {
@@ -1423,6 +1425,130 @@ int pf_ppo_loss(pf_ctx* ctx, const pf_ppo_loss_args* a, size_t rows, int width, 
   hipLaunchKernelGGL(main_kernel, dim3(grid), dim3(pf::kPpoBlock), 0, s, K, rows, (const double*)fin, main_part);
   hipLaunchKernelGGL(pf::ppo_finish_kernel, dim3(1), dim3(pf::kPpoBlock), 0, s, (const double*)main_part, (int)grid, (const double*)fin, a->log_std, width,
                      a->vf_coef, a->ent_coef, a->stats, a->grad_log_std);
+  PF_HIP(ctx, hipGetLastError());
+  return PF_OK;
+}
+// pf_mlp_forward / pf_mlp_backward: what both check of the network; `who` is the call's name
+static const char* mlp_shape_error(const pf_mlp* q) {
+  if (q->n_layers != 2 && q->n_layers != 3) return "n_layers must be 2 or 3";
+  for (int l = 0; l + 1 < q->n_layers; ++l)
+    if (q->width[l] < 1 || q->width[l] > PF_POLICY_MAX_HIDDEN) return "width: hidden widths must be in 1..PF_POLICY_MAX_HIDDEN (64)";
+  if (q->activation != PF_ACT_TANH && q->activation != PF_ACT_RELU) return "activation must be PF_ACT_TANH or PF_ACT_RELU";
+  if (q->in_dim < 1 || q->in_dim > pf::kActMaxIn) return "in_dim must be in 1..128";
+  if (q->out_dim < 1 || q->out_dim > pf::kActMaxA) return "out_dim must be in 1..8";
+  return nullptr;
+}
+static int mlp_fail(pf_ctx* ctx, const char* who, const char* what) {
+  char buf[256];
+  snprintf(buf, sizeof(buf), "%s: %s", who, what);
+  return fail(ctx, PF_ERR_ARG, buf);
+}
+static int mlp_check(pf_ctx* ctx, const char* who, const pf_mlp* q, int64_t rows) {
+  if (!q) return mlp_fail(ctx, who, "mlp is required");
+  if (const char* e = mlp_shape_error(q)) return mlp_fail(ctx, who, e);
+  for (int l = 0; l < q->n_layers; ++l)
+    if (!q->w[l] || !q->b[l]) return mlp_fail(ctx, who, "w / b: every layer needs w and b");
+  if (rows < 1) return mlp_fail(ctx, who, "rows must be >= 1");
+  if (rows > (int64_t)INT32_MAX - pf::kActRows) return mlp_fail(ctx, who, "rows must be below 2^31 - 64 (the kernels index rows with 32 bits)");
+  return PF_OK;
+}
+struct mlp_span {
+  const char* name;
+  const void* p;
+  size_t bytes;
+};
+// the first pair of spans that share a byte, or null
+static const char* mlp_overlap(const mlp_span* s, int count, char* buf, size_t len) {
+  for (int i = 0; i < count; ++i)
+    for (int j = i + 1; j < count; ++j) {
+      const uintptr_t a = (uintptr_t)s[i].p, b = (uintptr_t)s[j].p;
+      if (a < b + s[j].bytes && b < a + s[i].bytes) {
+        snprintf(buf, len, "%s and %s overlap", s[i].name, s[j].name);
+        return buf;
+      }
+    }
+  return nullptr;
+}
+int pf_mlp_forward(pf_ctx* ctx, const pf_mlp* q, const float* x, int64_t rows, float* out, void* stream) {
+  static const char* who = "pf_mlp_forward";
+  if (!ctx) return mlp_fail(ctx, who, "ctx is required");
+  int rc = mlp_check(ctx, who, q, rows);
+  if (rc) return rc;
+  if (!x) return mlp_fail(ctx, who, "x is required");
+  if (!out) return mlp_fail(ctx, who, "out is required");
+  char buf[128];
+  const mlp_span spans[2] = {{"x", x, sizeof(float) * (size_t)rows * q->in_dim}, {"out", out, sizeof(float) * (size_t)rows * q->out_dim}};
+  if (const char* e = mlp_overlap(spans, 2, buf, sizeof(buf))) return mlp_fail(ctx, who, e);
+  rc = ensure_device(ctx);
+  if (rc) return rc;
+  // policy_act_kernel itself, the draw off (no log_std), the caller's rows as its observations and out_dim as its action width
+  pf_policy P;
+  P.n_layers = q->n_layers;
+  P.width[0] = q->width[0];
+  P.width[1] = q->width[1];
+  P.activation = q->activation;
+  for (int l = 0; l < 3; ++l) {
+    P.w[l] = l < q->n_layers ? q->w[l] : nullptr;
+    P.b[l] = l < q->n_layers ? q->b[l] : nullptr;
+  }
+  P.log_std = nullptr;
+  P.obs0 = x;
+  P.mean_out = nullptr;
+  const pf::ActK AK{P, out, (int)rows, q->in_dim, q->out_dim, 0u, 0u, 0u, 0ull};
+  const int64_t tiles = (rows + pf::kActRows - 1) / pf::kActRows;
+  const int grid = tiles < (int64_t)ctx->act_grid_cap ? (int)tiles : ctx->act_grid_cap;
+  hipLaunchKernelGGL(pf::policy_act_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, AK);
+  PF_HIP(ctx, hipGetLastError());
+  return PF_OK;
+}
+size_t pf_mlp_backward_workspace_bytes(const pf_mlp* q, int64_t rows) {
+  if (!q || mlp_shape_error(q) || rows < 1) return 0;
+  return sizeof(float) * (size_t)pf::mlp_grid(rows) * (size_t)pf::mlp_param_count(*q, nullptr);
+}
+int pf_mlp_backward(pf_ctx* ctx, const pf_mlp* q, const float* x, const float* grad_out, int64_t rows, float* const grad_w[3], float* const grad_b[3],
+                    void* workspace, size_t workspace_bytes, void* stream) {
+  static const char* who = "pf_mlp_backward";
+  if (!ctx) return mlp_fail(ctx, who, "ctx is required");
+  int rc = mlp_check(ctx, who, q, rows);
+  if (rc) return rc;
+  if (!x) return mlp_fail(ctx, who, "x is required");
+  if (!grad_out) return mlp_fail(ctx, who, "grad_out is required");
+  if (!grad_w) return mlp_fail(ctx, who, "grad_w is required");
+  if (!grad_b) return mlp_fail(ctx, who, "grad_b is required");
+  for (int l = 0; l < q->n_layers; ++l) {
+    if (!grad_w[l]) return mlp_fail(ctx, who, "grad_w: every layer needs its output");
+    if (!grad_b[l]) return mlp_fail(ctx, who, "grad_b: every layer needs its output");
+  }
+  if (!workspace) return mlp_fail(ctx, who, "workspace is required");
+  const size_t need = pf_mlp_backward_workspace_bytes(q, rows);
+  if (workspace_bytes < need) return mlp_fail(ctx, who, "workspace_bytes is below pf_mlp_backward_workspace_bytes(mlp, rows)");
+  static const char* const wn[3] = {"grad_w[0]", "grad_w[1]", "grad_w[2]"};
+  static const char* const bn[3] = {"grad_b[0]", "grad_b[1]", "grad_b[2]"};
+  mlp_span spans[9];
+  int ns = 0;
+  spans[ns++] = {"x", x, sizeof(float) * (size_t)rows * q->in_dim};
+  spans[ns++] = {"grad_out", grad_out, sizeof(float) * (size_t)rows * q->out_dim};
+  spans[ns++] = {"workspace", workspace, need};
+  for (int l = 0; l < q->n_layers; ++l) {
+    const size_t n_in = l == 0 ? q->in_dim : q->width[l - 1], n_out = l + 1 == q->n_layers ? q->out_dim : q->width[l];
+    spans[ns++] = {wn[l], grad_w[l], sizeof(float) * n_in * n_out};
+    spans[ns++] = {bn[l], grad_b[l], sizeof(float) * n_out};
+  }
+  char buf[128];
+  if (const char* e = mlp_overlap(spans, ns, buf, sizeof(buf))) return mlp_fail(ctx, who, e);
+  rc = ensure_device(ctx);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const int grid = pf::mlp_grid(rows);
+  const pf::MlpK K{*q, x, grad_out, (float*)workspace, (int)rows};
+  hipLaunchKernelGGL(pf::mlp_backward_kernel, dim3(grid), dim3(256), 0, s, K);
+  pf::MlpOutK O;
+  const int P = pf::mlp_param_count(*q, O.end);
+  for (int l = 0; l < 3; ++l) {
+    O.p[2 * l] = l < q->n_layers ? grad_w[l] : nullptr;
+    O.p[2 * l + 1] = l < q->n_layers ? grad_b[l] : nullptr;
+  }
+  hipLaunchKernelGGL(pf::mlp_reduce_kernel, dim3((P + 255) / 256), dim3(256), 0, s, (const float*)workspace, grid, P, O);
   PF_HIP(ctx, hipGetLastError());
   return PF_OK;
 }

@@ -671,6 +671,96 @@ class BatchEngine:
             L.check(self.lib.pf_ppo_loss(self._ctx, C.byref(a), M, A, self._stream()), self._ctx)
         return o["grad_mean"], o["grad_value"], o["grad_log_std"], o["stats"]
 
+    def _mlp_block(self, x, layers, activation):
+        """The pf_mlp block of `layers` [(weight, bias), ...] for the rows of x [..., in_dim], every tensor checked; returns
+        (block, rows, [(out, in), ...])."""
+        from .policy import _ACTIVATIONS, MAX_HIDDEN
+
+        if activation not in _ACTIVATIONS:
+            raise ValueError(f"activation must be 'tanh' or 'relu', got {activation!r}")
+        layers = [tuple(l) for l in layers]
+        if len(layers) not in (2, 3):
+            raise ValueError(f"layers: 2 or 3 (weight, bias) pairs (1 or 2 hidden layers), got {len(layers)}")
+        if not torch.is_tensor(x) or x.dim() < 1:
+            raise ValueError(f"x must be a float32 tensor of shape (..., in_dim), got {type(x).__name__ if not torch.is_tensor(x) else tuple(x.shape)}")
+        dims = []
+        for l, (w, b) in enumerate(layers):
+            if not torch.is_tensor(w) or w.dim() != 2:
+                raise ValueError(f"layers[{l}].weight must be a float32 tensor of shape (out, in), got {type(w).__name__ if not torch.is_tensor(w) else tuple(w.shape)}")
+            n_out, n_in = int(w.shape[0]), int(w.shape[1])
+            want_in = int(x.shape[-1]) if l == 0 else dims[-1][0]
+            self._check_f32(w, (n_out, want_in), f"layers[{l}].weight")
+            if not torch.is_tensor(b):
+                raise ValueError(f"layers[{l}].bias must be a float32 tensor of shape ({n_out},), got {type(b).__name__}")
+            self._check_f32(b, (n_out,), f"layers[{l}].bias")
+            if l + 1 < len(layers) and not 1 <= n_out <= MAX_HIDDEN:
+                raise ValueError(f"layers[{l}].weight: hidden width {n_out} is outside 1..{MAX_HIDDEN} (PF_POLICY_MAX_HIDDEN)")
+            dims.append((n_out, n_in))
+        in_dim, out_dim = dims[0][1], dims[-1][0]
+        if not 1 <= in_dim <= 128:
+            raise ValueError(f"x's last axis (in_dim) must be in 1..128, got {in_dim}")
+        if not 1 <= out_dim <= 8:
+            raise ValueError(f"the last layer's width (out_dim) must be in 1..8, got {out_dim}")
+        self._check_f32(x, tuple(x.shape), "x")
+        rows = x.numel() // in_dim
+        if rows < 1:
+            raise ValueError(f"x must hold at least one row, got shape {tuple(x.shape)}")
+        q = L.PfMlp()
+        q.n_layers, q.activation, q.in_dim, q.out_dim = len(layers), _ACTIVATIONS[activation], in_dim, out_dim
+        for l in range(2):
+            q.width[l] = dims[l][0] if l + 1 < len(layers) else 0
+        for l in range(3):
+            q.w[l] = layers[l][0].data_ptr() if l < len(layers) else None
+            q.b[l] = layers[l][1].data_ptr() if l < len(layers) else None
+        return q, rows, dims
+
+    def mlp_forward(self, x, layers, activation="tanh", out=None):
+        """pf_mlp_forward: the MLP `layers` [(weight, bias), ...] (torch.nn.Linear's layout; 2 or 3 of them, hidden widths 1..64, the
+        last 1..8 wide) on the rows of x [..., in_dim], in_dim 1..128, with policy_act's arithmetic bit for bit. Any engine. Returns
+        `out` [rows, out_dim]; without `out`, a tensor the engine owns, overwritten by the next call of the same shape."""
+        q, rows, dims = self._mlp_block(x, layers, activation)
+        out_dim = dims[-1][0]
+        if out is None:
+            cache = self.__dict__.setdefault("_mlp_fwd", {})
+            out = cache.get((rows, out_dim))
+            if out is None:
+                out = cache[(rows, out_dim)] = torch.empty(rows, out_dim, dtype=torch.float32, device=self.device)
+        else:
+            if not torch.is_tensor(out):
+                raise ValueError(f"out must be a float32 tensor of shape {(rows, out_dim)}, got {type(out).__name__}")
+            self._check_f32(out, (rows, out_dim), "out")
+        with torch.cuda.device(self.device):
+            L.check(self.lib.pf_mlp_forward(self._ctx, C.byref(q), _ptr(x), rows, _ptr(out), self._stream()), self._ctx)
+        return out
+
+    def mlp_backward(self, x, grad_out, layers, activation="tanh"):
+        """pf_mlp_backward: [(grad_weight, grad_bias), ...] of the MLP `layers` on the rows of x [..., in_dim] under the
+        output-gradients grad_out [rows, out_dim] (a [rows] tensor is accepted for out_dim 1). The hidden activations are computed
+        again from x; x gets no gradient. The gradients and the workspace are tensors the engine owns, reused by the next call with
+        the same rows and layer shapes. Deterministic: the same call gives the same bits on any stream."""
+        q, rows, dims = self._mlp_block(x, layers, activation)
+        out_dim = dims[-1][0]
+        if not torch.is_tensor(grad_out):
+            raise ValueError(f"grad_out must be a float32 tensor of shape {(rows, out_dim)}, got {type(grad_out).__name__}")
+        self._check_f32(grad_out, tuple(grad_out.shape) if out_dim == 1 and tuple(grad_out.shape) == (rows,) else (rows, out_dim), "grad_out")
+        cache = self.__dict__.setdefault("_mlp_bwd", {})
+        key = (rows, tuple(dims))
+        o = cache.get(key)
+        if o is None:
+            kw = dict(dtype=torch.float32, device=self.device)
+            nbytes = int(self.lib.pf_mlp_backward_workspace_bytes(C.byref(q), rows))
+            if nbytes < 1:
+                raise L.PyFlytAmdError("pf_mlp_backward_workspace_bytes refused the network's shape")
+            grads = [(torch.empty(n_out, n_in, **kw), torch.empty(n_out, **kw)) for n_out, n_in in dims]
+            gw, gb = (C.c_void_p * 3)(), (C.c_void_p * 3)()
+            for l, (w, b) in enumerate(grads):
+                gw[l], gb[l] = w.data_ptr(), b.data_ptr()
+            o = cache[key] = dict(grads=grads, gw=gw, gb=gb, bytes=nbytes, workspace=torch.empty((nbytes + 3) // 4, **kw))
+        with torch.cuda.device(self.device):
+            L.check(self.lib.pf_mlp_backward(self._ctx, C.byref(q), _ptr(x), _ptr(grad_out), rows, o["gw"], o["gb"], _ptr(o["workspace"]), o["bytes"],
+                                             self._stream()), self._ctx)
+        return o["grads"]
+
     def body_tick(self, wrench, n_ticks: int = 1):
         """pf_body_tick: the free-body tick alone under a held body-frame wrench [n, 6] (force, torque)."""
         self._aviary_outputs()
