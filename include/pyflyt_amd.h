@@ -665,6 +665,70 @@ size_t pf_mlp_backward_workspace_bytes(const pf_mlp* mlp, int64_t rows);
 int pf_mlp_backward(pf_ctx* ctx, const pf_mlp* mlp, const float* x, const float* grad_out, int64_t rows, float* const grad_w[3],
                     float* const grad_b[3], void* workspace, size_t workspace_bytes, void* stream);
 
+/* The optimiser's step of a PPO epoch: Adam / AdamW with global gradient-norm clipping over a set of 1..PF_ADAM_MAX_TENSORS float32
+ * parameter tensors, in two launches. With it an epoch is pf_mlp_forward -> pf_ppo_loss -> pf_mlp_backward -> pf_adam_step and holds
+ * nothing but this library's launches. The context serves its device and pf_last_error only: any context works, with an env task or
+ * without. (Added without a new PF_ABI_VERSION: new functions; every other struct as it was.)
+ *   - NORM. norm = sqrt(sum over every element of every tensor of g^2): each square and every sum in double, in an order that
+ *     numel[] alone decides; no atomics.
+ *   - CLIP. coef = min(1, max_grad_norm / (norm + 1e-6)), torch.nn.utils.clip_grad_norm_'s form, in double: exactly 1 where clipping
+ *     is off (max_grad_norm = +infinity) or not reached. g' = g * coef32 with coef32 the float32 rounding of coef (a multiplication
+ *     by 1 where coef is 1: the same bits as no clip). grad[] itself is never written.
+ *   - STEP. t = state[0] + 1, and with lr the learning rate of this call (*lr_dev, read on the device at every call, where lr_dev is
+ *     given; the argument lr otherwise), torch.optim.Adam's / AdamW's update:
+ *         p *= 1 - lr weight_decay                 (only where weight_decay > 0: decoupled, AdamW; 0 = plain Adam)
+ *         m  = m + (1 - beta1) (g' - m)
+ *         v  = beta2 v + (1 - beta2) g'^2
+ *         p -= (lr / (1 - beta1^t)) m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
+ *     The hyperparameters are the float32 values of this block: beta2 = 0.999f is 0.99900001287..., and that is the beta2 applied.
+ *   - ARITHMETIC. The launch-uniform scalars are computed once in double from those values and rounded to float32: coef32,
+ *     decay = 1 - lr weight_decay, omb1 = 1 - beta1, omb2 = 1 - beta2, nstep = -lr / (1 - beta1^t), c2 = sqrt(1 - beta2^t) (the two
+ *     powers by double pow). Per element one fixed float32 sequence, every operation correctly rounded:
+ *         gc = g * coef32;  p0 = weight_decay > 0 ? p * decay : p;
+ *         m = fmaf(omb1, gc - m, m);  v = fmaf(omb2, gc * gc, beta2 * v);
+ *         p = fmaf(nstep, m / (sqrtf(v) / c2 + eps), p0)
+ *     with a fused multiply-add exactly where fmaf is written and nowhere else.
+ *   - STATE. state[8], double, read and then overwritten: 0 t, the steps taken; 1 norm, before clipping; 2 coef; 3 the learning rate
+ *     used; 4 the number of skipped calls so far; 5-7 0. A zeroed block with zeroed exp_avg / exp_avg_sq is a fresh optimiser.
+ *   - SKIP. With skip_nonfinite = 1 and a norm that is not finite, no parameter, no moment and not t changes; slot 4 is incremented,
+ *     slot 1 reports the norm and slot 2 a coef of 0. The decision is taken on the device and is a selection, not a multiplication
+ *     by a mask. With skip_nonfinite = 0 the arithmetic runs as written and a NaN spreads as it does in torch (an infinite norm
+ *     under a finite max_grad_norm gives coef 0 and 0 * inf = NaN in that element; under max_grad_norm = +infinity coef is NaN).
+ *   - DETERMINISM. The grid is a function of numel[] alone: the same call on the same inputs gives the same bits on any stream and
+ *     at every repetition. A tensor whose four pointers are 16-byte aligned moves as float4s, any other element by element; the
+ *     arithmetic is elementwise and an element belongs to the same thread either way, so the bits do not depend on the alignment.
+ *   - WORKSPACE. The caller's, at least pf_adam_workspace_bytes(the total of numel[]) bytes (a pure host function: it grows with
+ *     the total up to the grid's cap and is constant from there; 0 for a total below 1 or of 2^31 and more). It holds the partial
+ *     sums of the norm and what the first launch read of `state`; its contents mean nothing before or after the call.
+ *   - ERRORS. PF_ERR_ARG, pf_last_error naming the argument: a NULL ctx, argument block, state, workspace, or param[i] / grad[i] /
+ *     exp_avg[i] / exp_avg_sq[i]; n_tensors outside 1..32; a numel[i] < 1, or a total of 2^31 or more; lr negative or not finite
+ *     while lr_dev is NULL; beta1 or beta2 outside [0, 1); eps not > 0 or not finite; weight_decay negative or not finite;
+ *     max_grad_norm not > 0 (a NaN included); skip_nonfinite other than 0 / 1; workspace_bytes too small (refused by size, before
+ *     any launch); any two of the 4 n tensor ranges, state, workspace and lr_dev overlapping (both are named).
+ *   - Enqueued on `stream`: two launches, no host synchronisation, no allocation, no copy -- capturable in a HIP graph. The tensor
+ *     pointers travel in the kernel arguments: there is no descriptor table in device memory. The call keeps nothing in the
+ *     context, so calls with distinct workspaces, states and tensors may run on different streams. */
+#define PF_ADAM_MAX_TENSORS 32
+typedef struct pf_adam_args {
+  int32_t n_tensors;            /* 1..PF_ADAM_MAX_TENSORS */
+  int32_t skip_nonfinite;       /* 0 / 1 */
+  float   lr;                   /* used when lr_dev is NULL; finite, >= 0 */
+  const float* lr_dev;          /* device, [1], or NULL: read by the kernel at every call */
+  float   beta1, beta2;         /* in [0, 1) */
+  float   eps;                  /* > 0 */
+  float   weight_decay;         /* >= 0, decoupled (AdamW); 0 = plain Adam */
+  float   max_grad_norm;        /* > 0; +infinity = no clipping (the norm is still reported) */
+  int64_t numel[PF_ADAM_MAX_TENSORS];
+  float*       param[PF_ADAM_MAX_TENSORS];
+  const float* grad[PF_ADAM_MAX_TENSORS];
+  float*       exp_avg[PF_ADAM_MAX_TENSORS];
+  float*       exp_avg_sq[PF_ADAM_MAX_TENSORS];
+  double* state;                /* device, [8], in / out */
+} pf_adam_args;
+size_t pf_sizeof_adam(void);
+size_t pf_adam_workspace_bytes(int64_t total_numel);
+int pf_adam_step(pf_ctx* ctx, const pf_adam_args* a, void* workspace, size_t workspace_bytes, void* stream);
+
 /* The reference's LOWER boundary for one drone: applyExternalForce / applyExternalTorque on the base link in
  * LINK_FRAME followed by stepSimulation (core/drones/quadx.py:502-510, core/aviary.py:516), n_ticks times with
  * the wrench b->wrench held: the free-body tick alone (collision detection, gyroscopic term, +-max_coord_vel

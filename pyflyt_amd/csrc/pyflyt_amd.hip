@@ -727,6 +727,7 @@ __global__ void __launch_bounds__(256) sample_actions_kernel(const pf_params P, 
 #include "ppo_loss.hpp"
 #include "policy_act.hpp"
 #include "mlp.hpp"
+#include "adam.hpp"
 
 // ====================================================================== C ABI
 // The env kernel a context runs, chosen once at pf_ctx_create (select_env_kernel).
@@ -953,6 +954,7 @@ size_t pf_sizeof_gae(void) { return sizeof(pf_gae_args); }
 size_t pf_sizeof_traj_stats(void) { return sizeof(pf_traj_stats_args); }
 size_t pf_sizeof_ppo_loss(void) { return sizeof(pf_ppo_loss_args); }
 size_t pf_sizeof_mlp(void) { return sizeof(pf_mlp); }
+size_t pf_sizeof_adam(void) { return sizeof(pf_adam_args); }
 const char* pf_last_error(const pf_ctx* ctx) { return ctx ? ctx->err : g_err; }
 
 int pf_ctx_create(const pf_params* params, int n_lanes, int device, uint64_t lane_offset, pf_ctx** out) {
@@ -1549,6 +1551,88 @@ int pf_mlp_backward(pf_ctx* ctx, const pf_mlp* q, const float* x, const float* g
     O.p[2 * l + 1] = l < q->n_layers ? grad_b[l] : nullptr;
   }
   hipLaunchKernelGGL(pf::mlp_reduce_kernel, dim3((P + 255) / 256), dim3(256), 0, s, (const float*)workspace, grid, P, O);
+  PF_HIP(ctx, hipGetLastError());
+  return PF_OK;
+}
+size_t pf_adam_workspace_bytes(int64_t total_numel) {
+  if (total_numel < 1 || total_numel > (int64_t)INT32_MAX) return 0;
+  return sizeof(double) * (pf::adam_grid_bound(total_numel) + pf::kAdamHeader);
+}
+// what pf_adam_step refuses, or null; `buf` holds a composed message
+static const char* adam_error(const pf_adam_args* a, const void* workspace, size_t workspace_bytes, char* buf, size_t len) {
+  if (!a) return "the argument block is required";
+  if (a->n_tensors < 1 || a->n_tensors > PF_ADAM_MAX_TENSORS) return "n_tensors must be in 1..PF_ADAM_MAX_TENSORS (32)";
+  if (a->skip_nonfinite != 0 && a->skip_nonfinite != 1) return "skip_nonfinite must be 0 or 1";
+  if (!a->lr_dev && !(a->lr >= 0.0f && a->lr < INFINITY)) return "lr must be finite and >= 0";
+  if (!(a->beta1 >= 0.0f && a->beta1 < 1.0f)) return "beta1 must be in [0, 1)";
+  if (!(a->beta2 >= 0.0f && a->beta2 < 1.0f)) return "beta2 must be in [0, 1)";
+  if (!(a->eps > 0.0f && a->eps < INFINITY)) return "eps must be finite and > 0";
+  if (!(a->weight_decay >= 0.0f && a->weight_decay < INFINITY)) return "weight_decay must be finite and >= 0";
+  if (!(a->max_grad_norm > 0.0f)) return "max_grad_norm must be > 0 (+infinity: no clipping)";
+  if (!a->state) return "state is required";
+  if (!workspace) return "workspace is required";
+  static const char* const kinds[4] = {"param", "grad", "exp_avg", "exp_avg_sq"};
+  mlp_span spans[4 * PF_ADAM_MAX_TENSORS + 3];
+  char names[4 * PF_ADAM_MAX_TENSORS][16];
+  int ns = 0;
+  int64_t total = 0;
+  for (int i = 0; i < a->n_tensors; ++i) {
+    if (a->numel[i] < 1) {
+      snprintf(buf, len, "numel[%d] must be >= 1", i);
+      return buf;
+    }
+    total += a->numel[i];
+    if (total > (int64_t)INT32_MAX) return "numel: the total must be below 2^31";
+    const void* const ptrs[4] = {a->param[i], a->grad[i], a->exp_avg[i], a->exp_avg_sq[i]};
+    for (int k = 0; k < 4; ++k) {
+      snprintf(names[ns], sizeof(names[ns]), "%s[%d]", kinds[k], i);
+      if (!ptrs[k]) {
+        snprintf(buf, len, "%s is required", names[ns]);
+        return buf;
+      }
+      spans[ns] = {names[ns], ptrs[k], sizeof(float) * (size_t)a->numel[i]};
+      ++ns;
+    }
+  }
+  const size_t need = pf_adam_workspace_bytes(total);
+  if (workspace_bytes < need) return "workspace_bytes is below pf_adam_workspace_bytes(the total of numel)";
+  spans[ns++] = {"state", a->state, sizeof(double) * 8};
+  spans[ns++] = {"workspace", workspace, need};
+  if (a->lr_dev) spans[ns++] = {"lr_dev", a->lr_dev, sizeof(float)};
+  return mlp_overlap(spans, ns, buf, len);
+}
+int pf_adam_step(pf_ctx* ctx, const pf_adam_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+  static const char* who = "pf_adam_step";
+  if (!ctx) return mlp_fail(ctx, who, "ctx is required");
+  char buf[128];
+  if (const char* e = adam_error(a, workspace, workspace_bytes, buf, sizeof(buf))) return mlp_fail(ctx, who, e);
+  int rc = ensure_device(ctx);
+  if (rc) return rc;
+  pf::AdamK K;
+  K.n_tensors = a->n_tensors;
+  K.skip_nonfinite = a->skip_nonfinite;
+  K.lr = a->lr;
+  K.beta1 = a->beta1, K.beta2 = a->beta2, K.eps = a->eps, K.weight_decay = a->weight_decay, K.max_grad_norm = a->max_grad_norm;
+  K.lr_dev = a->lr_dev;
+  K.state = a->state;
+  K.work = (double*)workspace;
+  int chunks = 0;
+  for (int i = 0; i < PF_ADAM_MAX_TENSORS; ++i) {
+    const bool on = i < a->n_tensors;
+    K.first_chunk[i] = chunks;
+    K.numel[i] = on ? (int32_t)a->numel[i] : 0;
+    K.param[i] = on ? a->param[i] : nullptr;
+    K.grad[i] = on ? a->grad[i] : nullptr;
+    K.exp_avg[i] = on ? a->exp_avg[i] : nullptr;
+    K.exp_avg_sq[i] = on ? a->exp_avg_sq[i] : nullptr;
+    if (on) chunks += (int)((a->numel[i] + pf::kAdamChunk - 1) / pf::kAdamChunk);
+  }
+  K.first_chunk[PF_ADAM_MAX_TENSORS] = chunks;
+  K.chunks = chunks;
+  const int grid = chunks < pf::kAdamMaxGrid ? chunks : pf::kAdamMaxGrid;  // (<= adam_grid_bound(total): a chunk holds an element or more)
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(pf::adam_norm_kernel, dim3(grid), dim3(pf::kAdamBlock), 0, s, K);
+  hipLaunchKernelGGL(pf::adam_update_kernel, dim3(grid), dim3(pf::kAdamBlock), 0, s, K);
   PF_HIP(ctx, hipGetLastError());
   return PF_OK;
 }

@@ -761,6 +761,92 @@ class BatchEngine:
                                              self._stream()), self._ctx)
         return o["grads"]
 
+    def adam_step(self, params, grads, exp_avg, exp_avg_sq, state, *, lr=3e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
+                  max_grad_norm=None, skip_nonfinite: bool = False):
+        """pf_adam_step: one Adam / AdamW step with global gradient-norm clipping over the tensors `params` (1..32 of them), in
+        place, in two launches (include/pyflyt_amd.h has the semantics). grads, exp_avg and exp_avg_sq are lists of tensors shaped
+        like the parameters; state is the [8] float64 block (steps, norm, clip coefficient, learning rate, skipped calls), read
+        and overwritten. lr is a Python number or a one-element float32 device tensor, read by the kernel at every call.
+        max_grad_norm None = no clipping. The hyperparameters reach the kernel as float32. The workspace (one per total size) and
+        the filled argument block (one per set of addresses) are the engine's. Returns `state`; nothing synchronises."""
+        lists = dict(params=params, grads=grads, exp_avg=exp_avg, exp_avg_sq=exp_avg_sq)
+        for name, ts in lists.items():
+            if not isinstance(ts, (list, tuple)):
+                raise ValueError(f"{name} must be a list of tensors, got {type(ts).__name__}")
+        n = len(params)
+        if not 1 <= n <= L.PF_ADAM_MAX_TENSORS:
+            raise ValueError(f"params: 1..{L.PF_ADAM_MAX_TENSORS} tensors (PF_ADAM_MAX_TENSORS), got {n}")
+        for name, ts in lists.items():
+            if len(ts) != n:
+                raise ValueError(f"{name} must hold one tensor per parameter ({n}), got {len(ts)}")
+        lr_dev = lr if torch.is_tensor(lr) else None
+        for i, (p, g) in enumerate(zip(params, grads)):  # (the gradients are checked at every call: autograd makes new ones)
+            if not torch.is_tensor(p) or not torch.is_tensor(g):
+                raise ValueError(f"params[{i}] and grads[{i}] must be tensors, got {type(p).__name__} and {type(g).__name__}")
+            self._check_f32(g, tuple(p.shape), f"grads[{i}]")
+        key = tuple(t.data_ptr() for ts in lists.values() for t in ts) + (state.data_ptr() if torch.is_tensor(state) else None,
+                                                                          None if lr_dev is None else lr_dev.data_ptr())
+        cache = self.__dict__.setdefault("_adam", {})
+        o = cache.get(key)
+        if o is None:
+            for i, p in enumerate(params):
+                self._check_f32(p, tuple(p.shape), f"params[{i}]")
+                for name in ("exp_avg", "exp_avg_sq"):
+                    if not torch.is_tensor(lists[name][i]):
+                        raise ValueError(f"{name}[{i}] must be a tensor, got {type(lists[name][i]).__name__}")
+                    self._check_f32(lists[name][i], tuple(p.shape), f"{name}[{i}]")
+                if p.numel() < 1:
+                    raise ValueError(f"params[{i}] must hold at least one element, got shape {tuple(p.shape)}")
+            if not torch.is_tensor(state):
+                raise ValueError(f"state must be a float64 tensor of shape (8,), got {type(state).__name__}")
+            self._check(state, (8,), (torch.float64,), "state")
+            if lr_dev is not None:
+                self._check_f32(lr_dev, tuple(lr_dev.shape) if lr_dev.numel() == 1 else (1,), "lr")
+            total = sum(p.numel() for p in params)
+            nbytes = int(self.lib.pf_adam_workspace_bytes(total))
+            if nbytes < 1:
+                raise ValueError(f"params: the total number of elements must be below 2^31, got {total}")
+            spaces = self.__dict__.setdefault("_adam_ws", {})
+            if total not in spaces:
+                spaces[total] = torch.empty(nbytes // 8, dtype=torch.float64, device=self.device)
+            a = L.PfAdam()
+            a.n_tensors, a.state, a.lr_dev = n, _ptr(state), _ptr(lr_dev)
+            for i in range(n):
+                a.numel[i] = params[i].numel()
+                a.param[i], a.grad[i] = params[i].data_ptr(), grads[i].data_ptr()
+                a.exp_avg[i], a.exp_avg_sq[i] = exp_avg[i].data_ptr(), exp_avg_sq[i].data_ptr()
+            # (the tensors ride along: an address in the key stays theirs for as long as the entry lives)
+            o = cache[key] = dict(args=a, ref=C.byref(a), workspace=_ptr(spaces[total]), bytes=nbytes, keep=(list(params), list(exp_avg), list(exp_avg_sq), state, lr_dev))
+            if len(cache) > 64:
+                cache.pop(next(iter(cache)))
+        for name, x in (("eps", eps), ("weight_decay", weight_decay)) + (() if lr_dev is not None else (("lr", lr),)) \
+                + (() if max_grad_norm is None else (("max_grad_norm", max_grad_norm),)):
+            if isinstance(x, bool) or not isinstance(x, (int, float)):
+                raise ValueError(f"{name} must be a Python number" + (" or a one-element float32 device tensor" if name == "lr" else "") + f", got {type(x).__name__}")
+        try:
+            b1, b2 = betas
+            b1, b2 = float(b1), float(b2)
+        except (TypeError, ValueError):
+            raise ValueError(f"betas must be a pair of numbers, got {betas!r}") from None
+        if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+            raise ValueError(f"betas must lie in [0, 1), got {betas!r}")
+        if lr_dev is None and not 0.0 <= float(lr) < float("inf"):
+            raise ValueError(f"lr must be finite and >= 0, got {lr}")
+        if not 0.0 < float(eps) < float("inf"):
+            raise ValueError(f"eps must be finite and > 0, got {eps}")
+        if not 0.0 <= float(weight_decay) < float("inf"):
+            raise ValueError(f"weight_decay must be finite and >= 0, got {weight_decay}")
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError(f"max_grad_norm must be > 0 or None (no clipping), got {max_grad_norm}")
+        if not isinstance(skip_nonfinite, bool):
+            raise ValueError(f"skip_nonfinite must be a bool, got {type(skip_nonfinite).__name__}")
+        a = o["args"]
+        a.lr, a.beta1, a.beta2, a.eps, a.weight_decay = (0.0 if lr_dev is not None else float(lr)), b1, b2, float(eps), float(weight_decay)
+        a.max_grad_norm, a.skip_nonfinite = (float("inf") if max_grad_norm is None else float(max_grad_norm)), int(skip_nonfinite)
+        with torch.cuda.device(self.device):
+            L.check(self.lib.pf_adam_step(self._ctx, o["ref"], o["workspace"], o["bytes"], C.c_void_p(_raw_stream(self._index))), self._ctx)
+        return state
+
     def body_tick(self, wrench, n_ticks: int = 1):
         """pf_body_tick: the free-body tick alone under a held body-frame wrench [n, 6] (force, torque)."""
         self._aviary_outputs()
