@@ -84,6 +84,8 @@ def run(name, n_steps, seed, policy, options="default", env_kwargs=None, setup=N
                    ceiling=np.array(env.ceiling), max_displacement=np.array(env.max_displacement),
                    angle_repr=np.array(env.angle_representation), sparse=np.array(env.sparse_reward),
                    start_pos=np.array(env.start_pos, dtype=np.float64).reshape(-1), start_orn=np.array(env.start_orn, dtype=np.float64).reshape(-1))
+        if "max_duration_seconds" in kw:  # (the env keeps max_steps only; the default, 60 s, is not stored)
+            out.update(max_duration_seconds=np.array(float(kw["max_duration_seconds"])))
         return out
     finally:
         ref_stubs.RecordingRNG.F32 = False
@@ -106,6 +108,12 @@ def pulsed_descent(v_target, z_cut):
         z = float(env.lin_pos[2])
         ign = 1.0 if (z > z_cut and vz < v_target(z)) else 0.0
         return np.array([0.0, 0.0, 0.0, ign, 0.0, 0.0, 0.0])
+    return f
+
+
+def constant_action(a):
+    def f(env, rng, k):
+        return np.array(a, dtype=np.float64)
     return f
 
 
@@ -157,6 +165,34 @@ def gen_hard():
     # onto the pad too fast: fatal_collision from the pad branch (previous speed > 1 m/s)
     save("env_rocket_landing_hard", **run("hard", 60, 15, idle_action, options={}, env_kwargs=dict(ceiling=20.0),
                                          setup=start_at((0.2, 0.1, 4.0))))
+
+
+@group
+def gen_timeout():
+    # a half-second episode (20 steps at 40 Hz), default options, random actions: truncated by the time limit in free flight, twice
+    save("env_rocket_landing_timeout", **run("timeout", 50, 21, uniform_action, env_kwargs=dict(max_duration_seconds=0.5)))
+
+
+@group
+def gen_ceiling():
+    # full throttle from 17 m under a 20 m ceiling: out_of_bounds through the ceiling branch, three times
+    save("env_rocket_landing_ceiling", **run("ceiling", 60, 22, constant_action((0, 0, 0, 1, 1, 0, 0)), options={}, env_kwargs=dict(ceiling=20.0),
+                                            setup=start_at((0.5, 0.5, 17.0))))
+
+
+@group
+def gen_lateral():
+    # the gimbal hard over at 30 % throttle, 2 m from the axis with 3 m allowed: out_of_bounds through the lateral branch
+    save("env_rocket_landing_lateral", **run("lateral", 120, 23, constant_action((0, 0, 0, 1, 0.3, 1, 0)), options={},
+                                            env_kwargs=dict(ceiling=60.0, max_displacement=3.0), setup=start_at((2.0, 0.0, 30.0))))
+
+
+@group
+def gen_rest_tilt():
+    # set down on the pad a hair's breadth up, slightly tilted and yawed, engine off: a pad contact that lasts the whole episode (the
+    # pad bit and the +5 - 0.3 |gvz| bonus on every step) until the rocket has come to rest -> env_complete, four times
+    save("env_rocket_landing_rest_tilt", **run("rest_tilt", 80, 26, idle_action, options={}, env_kwargs=dict(ceiling=20.0),
+                                              setup=start_at((0.3, -0.4, 2.60), (0.01, -0.01, 0.5))))
 
 
 if __name__ == "__main__":

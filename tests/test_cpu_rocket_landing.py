@@ -1,5 +1,6 @@
-"""Rocket-Landing without a GPU: the parameter block, the spaces, agent_hz validation, and the fp64 landing-pad model
-(tests/golden/pad_bullet.py) the fixtures are recorded on."""
+"""Rocket-Landing without a GPU: the parameter block, the spaces, agent_hz validation, the fp64 landing-pad model
+(tests/golden/pad_bullet.py) the fixtures are recorded on, what each fixture is for, and the schedule of the mixed-wave replay
+(tests/rocket_lane_programs.py)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -16,7 +17,7 @@ from pyflyt_amd import _lib as L  # noqa: E402
 from pyflyt_amd.params import build_params  # noqa: E402
 
 GOLD = os.path.join(HERE, "golden")
-FIXTURES = ("random", "euler", "offpad", "land", "hard")
+FIXTURES = ("random", "euler", "offpad", "land", "hard", "timeout", "ceiling", "lateral", "rest_tilt")
 
 
 def test_params_fields():
@@ -109,6 +110,68 @@ def test_fixture_outcomes():
     off = f["offpad"]
     k = int(np.argmax(off["info_col"]))
     assert off["term"][k] and off["obs"][k][12] < 2.5 and not off["obs"][:, -1].any()
+    ends = lambda g, key: np.nonzero(g[key])[0].tolist()  # noqa: E731
+    nothing_else = lambda g, *keys: not any(g[k].any() for k in ("term", "trunc", "info_oob", "info_col", "info_complete") if k not in keys)  # noqa: E731
+    # the time limit, in free flight: a 0.5 s episode is max_steps = 20, and `step_count > max_steps` lets 22 steps through
+    t = f["timeout"]
+    assert float(t["max_duration_seconds"]) == 0.5 and int(t["options"]) == -1
+    assert ends(t, "trunc") == [21, 43] and t["reset_before"].tolist() == [22, 44] and nothing_else(t, "trunc")
+    assert t["obs"][:, 12].min() > 300.0 and not t["obs"][:, -1].any()
+    # the ceiling branch of out_of_bounds: z crosses 20 m with the rocket over the pad
+    c = f["ceiling"]
+    assert ends(c, "term") == ends(c, "info_oob") == [16, 33, 50] and nothing_else(c, "term", "info_oob")
+    assert all(c["obs"][k][12] > float(c["ceiling"]) == 20.0 > c["obs"][k - 1][12] for k in (16, 33, 50))
+    assert np.linalg.norm(c["obs"][:, 10:12], axis=1).max() < float(c["max_displacement"])
+    # the lateral branch: 3 m from the axis, far below the ceiling
+    la = f["lateral"]
+    assert ends(la, "term") == ends(la, "info_oob") == [61] and nothing_else(la, "term", "info_oob")
+    assert float(la["max_displacement"]) == 3.0 and np.linalg.norm(la["obs"][61][10:12]) > 3.0 > np.linalg.norm(la["obs"][60][10:12])
+    assert la["obs"][:, 12].max() < float(la["ceiling"]) == 60.0
+    # a pad contact that lasts: the pad bit on EVERY step, the pad bonus on every step, env_complete once the rocket is at rest
+    r = f["rest_tilt"]
+    assert int(r["obs"][:, -1].sum()) == len(r["action"]) == 80
+    assert ends(r, "trunc") == ends(r, "info_complete") == [18, 37, 56, 75] and nothing_else(r, "trunc", "info_complete")
+    assert r["reward"].min() > 4.0 and all(r["reward"][k] > r["reward"][k - 1] + 2.9 for k in (18, 37, 56, 75))  # +5 each step, +3 on completion
+    assert np.abs(r["start_orn"] - np.array([0.01, -0.01, 0.5])).max() == 0.0
+
+
+# ------------------------------------------------------------------ the mixed-wave replay's schedule (tests/rocket_lane_programs.py)
+@pytest.mark.parametrize("mode", ["off", "same_step"])
+def test_mixed_schedule_coverage(mode):
+    """The schedule is a pure function of the fixtures: every (fixture, step) and every recorded reset is visited, every lane
+    completes a pass, and there are calls on which the first wave (lanes 0..63) holds, in five different lanes at once, a lane on a
+    floor-collision step, one on a pad-contact step, one in free flight, one being reset and one that is done or idle."""
+    import rocket_lane_programs as RLP
+
+    names = RLP.MIXED_FIXTURES
+    fixtures = [RLP.load(n) for n in names]
+    S = RLP.schedule(fixtures, mode)
+    T, n = S["kind"].shape
+    assert n == RLP.N_LANES == 70 and T == int(S["delays"].max()) + int(S["period"].max()) and T < 380
+    assert len(set(S["delays"].tolist())) == n  # no two lanes in phase
+    for fi, g in enumerate(fixtures):
+        lanes = S["fix"] == fi
+        steps = S["k"][:, lanes][S["kind"][:, lanes] == RLP.STEP]
+        assert set(steps.tolist()) == set(range(len(g["action"]))), names[fi]
+        assert set(S["ri"][:, lanes][S["ri"][:, lanes] >= 0].tolist()) == set(range(len(g["reset_obs"]))), names[fi]
+    for i in range(n):  # a full pass: the program's first op to its last, in order
+        d, L = int(S["delays"][i]), int(S["period"][S["fix"][i]])
+        assert d + L <= T and (S["kind"][:d, i] == RLP.IDLE).all() and (S["kind"][d:, i] != RLP.IDLE).all()
+        assert S["kind"][d, i] == RLP.RESET and S["ri"][d, i] == 0
+        ks = S["k"][d:d + L, i][S["kind"][d:d + L, i] == RLP.STEP]
+        assert ks.tolist() == list(range(len(fixtures[S["fix"][i]]["action"])))
+    C = RLP.categories(S, fixtures, names)
+    order = ("floor", "pad", "flight", "reset", "done_or_idle")
+    full = [t for t in range(T) if RLP.distinct_witnesses([set(np.nonzero(C[c][t, :64])[0].tolist()) for c in order])]
+    print(f"mode {mode}: {T} calls, {len(full)} of them with all five situations in five lanes of the first wave (first {full[:5]})")
+    assert len(full) >= 3, full
+    # and the situations the five-way calls do not need: a lane resets inside a call while wave-mates step on (same_step), every
+    # fixture meets every other one's contact steps out of phase
+    if mode == "same_step":
+        assert ((C["reset"] & (S["kind"] == RLP.STEP))[:, :64].any(1) & C["flight"][:, :64].any(1)).sum() > 50
+    A = RLP.assemble(S, fixtures)
+    assert A["reset_mask"][S["kind"] != RLP.STEP].all() and not A["reset_mask"][S["kind"] == RLP.STEP].any()
+    assert np.isfinite(A["xi"]).all() and A["impact"].any() and (~A["impact"][S["kind"] == RLP.STEP]).any()
 
 
 # ------------------------------------------------------------------ the fp64 pad model (tests/golden/pad_bullet.py)
