@@ -5,7 +5,7 @@
 // forward exists. The backward is two kernels:
 //
 //   mlp_backward_kernel  a workgroup of four waves strides over 64-row tiles with policy_act_kernel's tile and operand layouts. Per tile:
-//                          1. the forward again (the same matrix-instruction chains): X -> TX, h0 -> TH0, h1 -> TH1; nothing was saved;
+//                          1. the forward again, by the chain function policy_act_kernel runs (mlp_tile.hpp: tile_chain): X -> TX, h0 -> TH0, h1 -> TH1; nothing was saved;
 //                          2. the rows of grad_out -> G, the rows past `rows` as exact zeros (x is clamped, the gradient is masked);
 //                          3. grad_w[last] += G^T h_last   (the rows are the contraction: wave (mt, nt) takes the rows 32 mt .. 32 mt + 31);
 //                          4. delta_last = (G WO) * act'(h_last), at most eight fmaf per element, written over h_last IN PLACE: an
@@ -21,6 +21,8 @@
 //
 // The grid is min(tiles, kMlpMaxGrid): a function of `rows` alone. No atomics. LDS: both chunks of the first layer, the second
 // layer, X (two chunks), h0, h1 and G are 118 KB of the CU's 160 KB, declared statically (gfx950 admits it): one workgroup per CU.
+// The tile constants, the barrier, the accumulator's fill, row map and activation store and the forward's matrix chain are mlp_tile.hpp's,
+// shared with policy_act_kernel; the staging and the row loads are this file's own copies (profiles/mlp_tile/nothing_moved.txt: why).
 #pragma once
 
 namespace pf {
@@ -63,14 +65,12 @@ inline int mlp_grid(int64_t rows) {
   return (int)(tiles < (int64_t)kMlpMaxGrid ? tiles : (int64_t)kMlpMaxGrid);
 }
 
-PF_DEV int mlp_row(const int r, const int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }  // the tile row of accumulator register r
-
 // delta = pre * act'(h) over the h of this lane's sixteen accumulator positions, in place; returns the sum of the sixteen
 PF_DEV float mlp_delta_store(const int activation, const act_f16v& pre, float* hcol, const int h) {
   float cs = 0.0f;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    float* p = hcol + mlp_row(r, h) * kActTS;
+    float* p = hcol + tile_row(r, h) * kActTS;
     const float hv = *p;
     const float d = activation == PF_ACT_RELU ? (hv > 0.0f ? pre[r] : 0.0f) : fmaf(-hv, hv, 1.0f) * pre[r];
     *p = d;
@@ -81,9 +81,7 @@ PF_DEV float mlp_delta_store(const int activation, const act_f16v& pre, float* h
 
 // a^T b over the 64 rows of two tiles: this wave's 32 x 32 block, columns ca .. ca + 31 of `a` by cb .. cb + 31 of `b`, from zero
 PF_DEV act_f16v mlp_outer(const float* a, const float* b, const int ca, const int cb, const int l31, const int h) {
-  act_f16v acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+  act_f16v acc = tile_fill(0.0f);
   for (int kk = 0; kk < kActRows / 2; ++kk) {
     const int row = 2 * kk + h;
     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[row * kActTS + ca + l31], b[row * kActTS + cb + l31], acc, 0, 0, 0);
@@ -111,7 +109,7 @@ __global__ void __launch_bounds__(256) mlp_backward_kernel(const MlpK K) {
   const int nchunks = (D + kPolH - 1) / kPolH;
   const int ntiles = (n + kActRows - 1) / kActRows;
 
-  // (policy_act_kernel's staging: thread t reads (unit j = 4 i + wv, input k = lane), sixteen loads in flight)
+  // (a copy of policy_act_kernel's staging, to be kept in step with it: thread t reads (unit j = 4 i + wv, input k = lane), sixteen loads in flight)
   auto stage_block = [&](float* dst, const float* w, const int stride, const int k0, const int n_in, const int n_out, const bool on) {
     float v[16];
 #pragma unroll
@@ -190,40 +188,25 @@ __global__ void __launch_bounds__(256) mlp_backward_kernel(const MlpK K) {
     }
     act_barrier();
 
-    // ---- the forward again: policy_act_kernel's chains
+    // ---- the forward again: tile_fill and tile_chain, as in policy_act_kernel
     act_f16v acc;
-    {
-      const float b = Bs[bcol];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] = b;
-    }
+    acc = tile_fill(Bs[bcol]);
     for (int ch = 0; ch < nchunks; ++ch) {
       const int np = (min(kPolH, D - ch * kPolH) + 1) >> 1;
-      const float* xa = TX + ch * kMlpTile + arow;
-      const float* wc = W0s + ch * kPolH * kPolH;
-      for (int kk = 0; kk < np; ++kk) {
-        const int k = 2 * kk + h;
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xa[k], wc[k * kPolH + ((bcol + k) & 63)], acc, 0, 0, 0);
-      }
+      acc = tile_chain(acc, TX + ch * kMlpTile + arow, W0s + ch * kPolH * kPolH, bcol, h, np);
     }
     act_store_hidden(Q.activation, acc, TH0 + hpos, h);
     act_barrier();
     if (three) {
-      const float b = Bs[kPolH + bcol];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] = b;
-      for (int kk = 0; kk < kPolH / 2; ++kk) {
-        const int k = 2 * kk + h;
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(TH0[arow + k], W1s[k * kPolH + ((bcol + k) & 63)], acc, 0, 0, 0);
-      }
+      acc = tile_fill(Bs[kPolH + bcol]);
+      acc = tile_chain(acc, TH0 + arow, W1s, bcol, h, kPolH / 2);
       act_store_hidden(Q.activation, acc, TH1 + hpos, h);
       act_barrier();
     }
 
     // ---- the output layer: grad_w = G^T h_last over this wave's half of the rows, grad_b = the column sums of G
     if (32 * nt < hl) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+      acc = tile_fill(0.0f);
       for (int kk = 0; kk < 16; ++kk) {
         const int row = 32 * mt + 2 * kk + h;
         const float a = l31 < kActMaxA ? G[row * kMlpGS + l31] : 0.0f;
@@ -247,7 +230,7 @@ __global__ void __launch_bounds__(256) mlp_backward_kernel(const MlpK K) {
       for (int c = 0; c < kActMaxA; ++c) wr[c] = WOs[bcol * kActMaxA + c];
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const float* g = G + (32 * mt + mlp_row(r, h)) * kMlpGS;
+        const float* g = G + (32 * mt + tile_row(r, h)) * kMlpGS;
         float d = g[0] * wr[0];
 #pragma unroll
         for (int c = 1; c < kActMaxA; ++c) d = fmaf(g[c], wr[c], d);
@@ -265,8 +248,7 @@ __global__ void __launch_bounds__(256) mlp_backward_kernel(const MlpK K) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) gw1[r] = gw1[r] + acc[r];
       }
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+      acc = tile_fill(0.0f);
       for (int kk = 0; kk < kPolH / 2; ++kk) {
         const int j = 2 * kk + h;  // W1[j][i = bcol] sits at row i of the staged block, rotated by i
         acc = __builtin_amdgcn_mfma_f32_32x32x2f32(TH1[arow + j], W1s[bcol * kPolH + ((j + bcol) & 63)], acc, 0, 0, 0);
@@ -294,7 +276,7 @@ __global__ void __launch_bounds__(256) mlp_backward_kernel(const MlpK K) {
   act_barrier();
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int j = 32 * mt + mlp_row(r, h);
+    const int j = 32 * mt + tile_row(r, h);
 #pragma unroll
     for (int ch = 0; ch < 2; ++ch) {
       const int i = ch * kPolH + bcol;

@@ -21,14 +21,10 @@
 //   * an odd D gets a zero last k-pair (T's column D and the weights' row D are zero): an exact term.
 //   * the output layer (4, 6 or 7 wide) is plain fmaf: lane = row, wave w the outputs 2w and 2w + 1, the weights broadcast from LDS.
 //   * nothing is kept between calls: no packed block in the context, the caller's tensors are read at every call.
+//   * the tile constants, the barrier, the accumulator's fill, row map and activation store and the matrix chain are mlp_tile.hpp's (mlp.hpp runs them too).
 #pragma once
 
 namespace pf {
-
-constexpr int kActRows = 64;       // rows of a workgroup's tile
-constexpr int kActTS = kPolH + 1;  // the tile's row stride in floats
-constexpr int kActMaxA = 8;        // the output layer's block holds eight columns (action widths 4, 6, 7)
-constexpr int kActMaxIn = 128;     // the widest observation (an eight-aircraft dogfight with six-wide actions: 123)
 
 struct ActK {
   pf_policy Q;
@@ -37,22 +33,6 @@ struct ActK {
   uint32_t seed_lo, seed_hi, step;
   uint64_t lane0;
 };
-
-typedef float act_f16v __attribute__((ext_vector_type(16)));
-
-// the 32x32 accumulator through the activation into the tile: register r of lane (h, l31) is row (r & 3) + 8 (r >> 2) + 4 h, unit l31
-PF_DEV void act_store_hidden(const int activation, const act_f16v& acc, float* trow0, const int h) {
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
-    trow0[row * kActTS] = activation == PF_ACT_RELU ? __builtin_fmaxf(acc[r], 0.0f) : pol_tanh(acc[r]);
-  }
-}
-
-// The workgroup barrier between the phases of a tile. Everything the phases exchange goes through LDS, so it waits for the LDS
-// counter only: __syncthreads() also waits for the vector-memory counter, i.e. for the next tile's observation loads, which are
-// issued one phase ahead on purpose.
-PF_DEV void act_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 __global__ void __launch_bounds__(256) policy_act_kernel(const ActK K) {
   __shared__ float Wc[kPolH * kPolH];      // the first layer's chunk [k][(unit + k) & 63]
@@ -128,29 +108,17 @@ __global__ void __launch_bounds__(256) policy_act_kernel(const ActK K) {
         if (nt_tile < ntiles) load_x(nt_tile, last ? 0 : ch + 1, xc);
       }
       act_barrier();
-      if (ch == 0) {
-        const float b = Bs[bcol];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = b;
-      }
+      if (ch == 0) acc = tile_fill(Bs[bcol]);
       const int np = (min(kPolH, D - c0) + 1) >> 1;
-      for (int kk = 0; kk < np; ++kk) {
-        const int k = 2 * kk + h;
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(arow[k], Wc[k * kPolH + ((bcol + k) & 63)], acc, 0, 0, 0);
-      }
+      acc = tile_chain(acc, arow, Wc, bcol, h, np);
     }
     first = false;
     act_barrier();
     act_store_hidden(Q.activation, acc, hcol, h);
     act_barrier();
     if (three) {
-      const float b = Bs[kPolH + bcol];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] = b;
-      for (int kk = 0; kk < kPolH / 2; ++kk) {
-        const int k = 2 * kk + h;
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(arow[k], W1s[k * kPolH + ((bcol + k) & 63)], acc, 0, 0, 0);
-      }
+      acc = tile_fill(Bs[kPolH + bcol]);
+      acc = tile_chain(acc, arow, W1s, bcol, h, kPolH / 2);
       act_barrier();
       act_store_hidden(Q.activation, acc, hcol, h);
       act_barrier();

@@ -725,6 +725,7 @@ __global__ void __launch_bounds__(256) sample_actions_kernel(const pf_params P, 
 #include "gae.hpp"
 #include "traj_stats.hpp"
 #include "ppo_loss.hpp"
+#include "mlp_tile.hpp"
 #include "policy_act.hpp"
 #include "mlp.hpp"
 #include "adam.hpp"
@@ -1221,6 +1222,70 @@ int pf_rollout(pf_ctx* ctx, const pf_buffers* b, int k_steps, uint32_t step_inde
     return fail(ctx, PF_ERR_UNSUPPORTED, "pf_rollout: needs an auto-reset mode (finished lanes would idle for the rest of the launch)");
   return launch_env(ctx, b, pf::OP_STEP, nullptr, b->actions ? 2 : 1, k_steps, step_index0, stream);
 }
+
+// ---- what the training-side entry points below share: refusals, argument tables, the policy network's checks, policy_act_kernel's launch
+// a refusal with the text "<who>: <what>"; arg_fail: the usual code
+static int who_fail(pf_ctx* ctx, int code, const char* who, const char* what) {
+  char buf[256];
+  snprintf(buf, sizeof(buf), "%s: %s", who, what);
+  return fail(ctx, code, buf);
+}
+static int arg_fail(pf_ctx* ctx, const char* who, const char* what) { return who_fail(ctx, PF_ERR_ARG, who, what); }
+// a call's required pointers, a table that ends with a null name: the first missing one is refused as "<who>: <name> is required"
+struct arg_ptr {
+  const char* name;
+  const void* p;
+};
+static int require_args(pf_ctx* ctx, const char* who, const arg_ptr* args) {
+  for (; args->name; ++args)
+    if (!args->p) {
+      char what[64];
+      snprintf(what, sizeof(what), "%s is required", args->name);
+      return arg_fail(ctx, who, what);
+    }
+  return PF_OK;
+}
+struct arg_span {
+  const char* name;
+  const void* p;
+  size_t bytes;
+};
+// the first pair of spans that share a byte, or null
+static const char* spans_overlap(const arg_span* s, int count, char* buf, size_t len) {
+  for (int i = 0; i < count; ++i)
+    for (int j = i + 1; j < count; ++j) {
+      const uintptr_t a = (uintptr_t)s[i].p, b = (uintptr_t)s[j].p;
+      if (a < b + s[j].bytes && b < a + s[i].bytes) {
+        snprintf(buf, len, "%s and %s overlap", s[i].name, s[j].name);
+        return buf;
+      }
+    }
+  return nullptr;
+}
+// what pf_rollout_policy and pf_policy_act check of the network, in this order
+static int policy_net_check(pf_ctx* ctx, const char* who, const pf_policy* q) {
+  if (q->n_layers != 2 && q->n_layers != 3) return arg_fail(ctx, who, "n_layers must be 2 or 3");
+  for (int l = 0; l + 1 < q->n_layers; ++l) {
+    if (q->width[l] > PF_POLICY_MAX_HIDDEN) return who_fail(ctx, PF_ERR_UNSUPPORTED, who, "hidden widths over PF_POLICY_MAX_HIDDEN (64) are not supported");
+    if (q->width[l] < 1) return arg_fail(ctx, who, "hidden widths must be >= 1");
+  }
+  if (q->activation != PF_ACT_TANH && q->activation != PF_ACT_RELU) return arg_fail(ctx, who, "activation must be PF_ACT_TANH or PF_ACT_RELU");
+  for (int l = 0; l < q->n_layers; ++l)
+    if (!q->w[l] || !q->b[l]) return arg_fail(ctx, who, "every layer needs w and b");
+  return PF_OK;
+}
+// the env's action width: what pf_policy_act writes per row and pf_gae's log-probabilities sum over
+static int env_action_dim(const pf_params& P) { return P.task == PF_TASK_ROCKET_LANDING ? pf::kRlActionDim : (P.task == PF_TASK_DOGFIGHT && P.df_action_dim == 6) ? 6 : 4; }
+static_assert(pf::kRlActionDim <= pf::kActMaxA, "the output layer's block holds the widest action");
+// policy_act_kernel's one launch site: workgroups stride over the 64-row tiles, two per CU at the most (all resident), so the weight staging is paid once per workgroup
+static int launch_policy_act(pf_ctx* ctx, const pf::ActK& AK, int64_t rows, void* stream) {
+  const int64_t tiles = (rows + pf::kActRows - 1) / pf::kActRows;
+  const int grid = tiles < (int64_t)ctx->act_grid_cap ? (int)tiles : ctx->act_grid_cap;
+  hipLaunchKernelGGL(pf::policy_act_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, AK);
+  PF_HIP(ctx, hipGetLastError());
+  return PF_OK;
+}
+
 int pf_rollout_policy(pf_ctx* ctx, const pf_buffers* b, const pf_policy* q, int k_steps, uint32_t step_index0, void* stream) {
   if (!ctx || !b || !q || !b->state || !b->obs || !b->reward || !b->terminated || !b->truncated)
     return fail(ctx, PF_ERR_ARG, "pf_rollout_policy: policy, state, obs, reward, terminated and truncated buffers are required");
@@ -1240,14 +1305,7 @@ int pf_rollout_policy(pf_ctx* ctx, const pf_buffers* b, const pf_policy* q, int 
   // (the contact response with every vertex in the manifold runs the out-of-line solve, whose argument block is stack: no zero-scratch instantiation)
   if (c.cr && P.contact_manifold_points >= 8)
     return fail(ctx, PF_ERR_UNSUPPORTED, "pf_rollout_policy: contact_response with contact_manifold_points = 8 is not supported (the in-register floor solve holds the 4-point manifold)");
-  if (q->n_layers != 2 && q->n_layers != 3) return fail(ctx, PF_ERR_ARG, "pf_rollout_policy: n_layers must be 2 or 3");
-  for (int l = 0; l + 1 < q->n_layers; ++l) {
-    if (q->width[l] > PF_POLICY_MAX_HIDDEN) return fail(ctx, PF_ERR_UNSUPPORTED, "pf_rollout_policy: hidden widths over PF_POLICY_MAX_HIDDEN (64) are not supported");
-    if (q->width[l] < 1) return fail(ctx, PF_ERR_ARG, "pf_rollout_policy: hidden widths must be >= 1");
-  }
-  if (q->activation != PF_ACT_TANH && q->activation != PF_ACT_RELU) return fail(ctx, PF_ERR_ARG, "pf_rollout_policy: activation must be PF_ACT_TANH or PF_ACT_RELU");
-  for (int l = 0; l < q->n_layers; ++l)
-    if (!q->w[l] || !q->b[l]) return fail(ctx, PF_ERR_ARG, "pf_rollout_policy: every layer needs w and b");
+  if (int rc = policy_net_check(ctx, "pf_rollout_policy", q)) return rc;
   if (!q->obs0) return fail(ctx, PF_ERR_ARG, "pf_rollout_policy: obs0 (the observation the previous call left) is required");
   const int D = pf_obs_dim(ctx);
   if (D > pf::kPolMaxIn) return fail(ctx, PF_ERR_UNSUPPORTED, "pf_rollout_policy: observation wider than the first layer's block");
@@ -1271,39 +1329,22 @@ int pf_policy_act(pf_ctx* ctx, const pf_policy* q, float* actions_out, uint32_t 
   if (P.task == PF_TASK_NONE) return fail(ctx, PF_ERR_UNSUPPORTED, "pf_policy_act: needs a context with an env task (this one drives the Aviary level only)");
   if (!actions_out) return fail(ctx, PF_ERR_ARG, "pf_policy_act: actions_out is required");
   if (!q->obs0) return fail(ctx, PF_ERR_ARG, "pf_policy_act: obs0 (the [n][pf_obs_dim()] input rows) is required");
-  if (q->n_layers != 2 && q->n_layers != 3) return fail(ctx, PF_ERR_ARG, "pf_policy_act: n_layers must be 2 or 3");
-  for (int l = 0; l + 1 < q->n_layers; ++l) {
-    if (q->width[l] > PF_POLICY_MAX_HIDDEN) return fail(ctx, PF_ERR_UNSUPPORTED, "pf_policy_act: hidden widths over PF_POLICY_MAX_HIDDEN (64) are not supported");
-    if (q->width[l] < 1) return fail(ctx, PF_ERR_ARG, "pf_policy_act: hidden widths must be >= 1");
-  }
-  if (q->activation != PF_ACT_TANH && q->activation != PF_ACT_RELU) return fail(ctx, PF_ERR_ARG, "pf_policy_act: activation must be PF_ACT_TANH or PF_ACT_RELU");
-  for (int l = 0; l < q->n_layers; ++l)
-    if (!q->w[l] || !q->b[l]) return fail(ctx, PF_ERR_ARG, "pf_policy_act: every layer needs w and b");
+  if (int rc = policy_net_check(ctx, "pf_policy_act", q)) return rc;
   const int D = pf_obs_dim(ctx);
   if (D > pf::kActMaxIn) return fail(ctx, PF_ERR_UNSUPPORTED, "pf_policy_act: observation wider than 128");
-  const int A = P.task == PF_TASK_ROCKET_LANDING ? pf::kRlActionDim : (P.task == PF_TASK_DOGFIGHT && P.df_action_dim == 6) ? 6 : 4;
-  static_assert(pf::kRlActionDim <= pf::kActMaxA, "the output layer's block holds the widest action");
   int rc = ensure_device(ctx);
   if (rc) return rc;
-  const pf::ActK AK{*q, actions_out, ctx->n, D, A, (uint32_t)P.seed, (uint32_t)(P.seed >> 32), step_index, ctx->lane0};
-  // workgroups stride over the 64-row tiles, two per CU at the most (all resident): the weight staging is paid once per workgroup
-  const int tiles = (ctx->n + pf::kActRows - 1) / pf::kActRows;
-  const int grid = tiles < ctx->act_grid_cap ? tiles : ctx->act_grid_cap;
-  hipLaunchKernelGGL(pf::policy_act_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, AK);
-  PF_HIP(ctx, hipGetLastError());
-  return PF_OK;
+  const pf::ActK AK{*q, actions_out, ctx->n, D, env_action_dim(P), (uint32_t)P.seed, (uint32_t)(P.seed >> 32), step_index, ctx->lane0};
+  return launch_policy_act(ctx, AK, ctx->n, stream);
 }
 int pf_gae(pf_ctx* ctx, const pf_gae_args* a, int k_steps, void* stream) {
   if (!ctx || !a) return fail(ctx, PF_ERR_ARG, "pf_gae: ctx and the argument block are required");
   const pf_params& P = ctx->P;
   if (P.task == PF_TASK_NONE) return fail(ctx, PF_ERR_UNSUPPORTED, "pf_gae: needs a context with an env task (this one drives the Aviary level only)");
   if (k_steps < 1) return fail(ctx, PF_ERR_ARG, "pf_gae: k_steps must be >= 1");
-  if (!a->reward) return fail(ctx, PF_ERR_ARG, "pf_gae: reward is required");
-  if (!a->terminated) return fail(ctx, PF_ERR_ARG, "pf_gae: terminated is required");
-  if (!a->truncated) return fail(ctx, PF_ERR_ARG, "pf_gae: truncated is required");
-  if (!a->values) return fail(ctx, PF_ERR_ARG, "pf_gae: values is required");
-  if (!a->advantages) return fail(ctx, PF_ERR_ARG, "pf_gae: advantages is required");
-  if (!a->returns) return fail(ctx, PF_ERR_ARG, "pf_gae: returns is required");
+  const arg_ptr required[] = {{"reward", a->reward}, {"terminated", a->terminated}, {"truncated", a->truncated}, {"values", a->values},
+                              {"advantages", a->advantages}, {"returns", a->returns}, {nullptr, nullptr}};
+  if (int rc = require_args(ctx, "pf_gae", required)) return rc;
   if (!(a->gamma >= 0.0f && a->gamma <= 1.0f)) return fail(ctx, PF_ERR_ARG, "pf_gae: gamma must be finite and in [0, 1]");
   if (!(a->lambda >= 0.0f && a->lambda <= 1.0f)) return fail(ctx, PF_ERR_ARG, "pf_gae: lambda must be finite and in [0, 1]");
   if (P.autoreset == PF_AUTORESET_SAME_STEP && !a->final_values)
@@ -1325,7 +1366,7 @@ int pf_gae(pf_ctx* ctx, const pf_gae_args* a, int k_steps, void* stream) {
                                                             : pf::gae_scan_kernel<PF_AUTORESET_OFF>;
   hipLaunchKernelGGL(scan, dim3((ctx->n + 63) / 64), dim3(64), 0, s, K, ctx->n, k_steps);
   if (n_logp) {
-    const int width = P.task == PF_TASK_ROCKET_LANDING ? pf::kRlActionDim : (P.task == PF_TASK_DOGFIGHT && P.df_action_dim == 6) ? 6 : 4;
+    const int width = env_action_dim(P);
     const size_t rows = (size_t)k_steps * (size_t)ctx->n;
     const size_t blocks = (rows + pf::kGaeLogpBlock - 1) / pf::kGaeLogpBlock;
     const dim3 grid((unsigned)(blocks < (size_t)pf::kGaeLogpMaxGrid ? blocks : (size_t)pf::kGaeLogpMaxGrid));
@@ -1342,13 +1383,9 @@ int pf_traj_stats(pf_ctx* ctx, const pf_traj_stats_args* a, int k_steps, void* s
   const pf_params& P = ctx->P;
   if (P.task == PF_TASK_NONE) return fail(ctx, PF_ERR_UNSUPPORTED, "pf_traj_stats: needs a context with an env task (this one drives the Aviary level only)");
   if (k_steps < 1) return fail(ctx, PF_ERR_ARG, "pf_traj_stats: k_steps must be >= 1");
-  if (!a->reward) return fail(ctx, PF_ERR_ARG, "pf_traj_stats: reward is required");
-  if (!a->terminated) return fail(ctx, PF_ERR_ARG, "pf_traj_stats: terminated is required");
-  if (!a->truncated) return fail(ctx, PF_ERR_ARG, "pf_traj_stats: truncated is required");
-  if (!a->summary) return fail(ctx, PF_ERR_ARG, "pf_traj_stats: summary is required");
-  if (!a->carry_return) return fail(ctx, PF_ERR_ARG, "pf_traj_stats: carry_return is required");
-  if (!a->carry_length) return fail(ctx, PF_ERR_ARG, "pf_traj_stats: carry_length is required");
-  if (!a->carry_disc) return fail(ctx, PF_ERR_ARG, "pf_traj_stats: carry_disc is required");
+  const arg_ptr required[] = {{"reward", a->reward}, {"terminated", a->terminated}, {"truncated", a->truncated}, {"summary", a->summary},
+                              {"carry_return", a->carry_return}, {"carry_length", a->carry_length}, {"carry_disc", a->carry_disc}, {nullptr, nullptr}};
+  if (int rc = require_args(ctx, "pf_traj_stats", required)) return rc;
   if (!(a->gamma >= 0.0f && a->gamma <= 1.0f)) return fail(ctx, PF_ERR_ARG, "pf_traj_stats: gamma must be finite and in [0, 1]");
   if (P.autoreset != PF_AUTORESET_NEXT_STEP && a->episode_start)
     return fail(ctx, PF_ERR_ARG, "pf_traj_stats: episode_start must be NULL outside NEXT_STEP (no other mode has reset steps)");
@@ -1382,17 +1419,10 @@ int pf_ppo_loss(pf_ctx* ctx, const pf_ppo_loss_args* a, size_t rows, int width, 
   if (!ctx || !a) return fail(ctx, PF_ERR_ARG, "pf_ppo_loss: ctx and the argument block are required");
   if (rows < 1) return fail(ctx, PF_ERR_ARG, "pf_ppo_loss: rows must be >= 1");
   if (width < 1 || width > pf::kPpoMaxA) return fail(ctx, PF_ERR_ARG, "pf_ppo_loss: width must be in 1..8");
-  if (!a->mean) return fail(ctx, PF_ERR_ARG, "pf_ppo_loss: mean is required");
-  if (!a->log_std) return fail(ctx, PF_ERR_ARG, "pf_ppo_loss: log_std is required");
-  if (!a->actions) return fail(ctx, PF_ERR_ARG, "pf_ppo_loss: actions is required");
-  if (!a->logp_old) return fail(ctx, PF_ERR_ARG, "pf_ppo_loss: logp_old is required");
-  if (!a->advantages) return fail(ctx, PF_ERR_ARG, "pf_ppo_loss: advantages is required");
-  if (!a->returns) return fail(ctx, PF_ERR_ARG, "pf_ppo_loss: returns is required");
-  if (!a->value) return fail(ctx, PF_ERR_ARG, "pf_ppo_loss: value is required");
-  if (!a->grad_mean) return fail(ctx, PF_ERR_ARG, "pf_ppo_loss: grad_mean is required");
-  if (!a->grad_value) return fail(ctx, PF_ERR_ARG, "pf_ppo_loss: grad_value is required");
-  if (!a->grad_log_std) return fail(ctx, PF_ERR_ARG, "pf_ppo_loss: grad_log_std is required");
-  if (!a->stats) return fail(ctx, PF_ERR_ARG, "pf_ppo_loss: stats is required");
+  const arg_ptr required[] = {{"mean", a->mean}, {"log_std", a->log_std}, {"actions", a->actions}, {"logp_old", a->logp_old},
+                              {"advantages", a->advantages}, {"returns", a->returns}, {"value", a->value}, {"grad_mean", a->grad_mean},
+                              {"grad_value", a->grad_value}, {"grad_log_std", a->grad_log_std}, {"stats", a->stats}, {nullptr, nullptr}};
+  if (int rc = require_args(ctx, "pf_ppo_loss", required)) return rc;
   if (!(a->clip > 0.0f && a->clip < INFINITY)) return fail(ctx, PF_ERR_ARG, "pf_ppo_loss: clip must be finite and > 0");
   if (!(a->vf_coef >= 0.0f && a->vf_coef < INFINITY)) return fail(ctx, PF_ERR_ARG, "pf_ppo_loss: vf_coef must be finite and >= 0");
   if (!(a->ent_coef >= 0.0f && a->ent_coef < INFINITY)) return fail(ctx, PF_ERR_ARG, "pf_ppo_loss: ent_coef must be finite and >= 0");
@@ -1440,47 +1470,25 @@ static const char* mlp_shape_error(const pf_mlp* q) {
   if (q->out_dim < 1 || q->out_dim > pf::kActMaxA) return "out_dim must be in 1..8";
   return nullptr;
 }
-static int mlp_fail(pf_ctx* ctx, const char* who, const char* what) {
-  char buf[256];
-  snprintf(buf, sizeof(buf), "%s: %s", who, what);
-  return fail(ctx, PF_ERR_ARG, buf);
-}
 static int mlp_check(pf_ctx* ctx, const char* who, const pf_mlp* q, int64_t rows) {
-  if (!q) return mlp_fail(ctx, who, "mlp is required");
-  if (const char* e = mlp_shape_error(q)) return mlp_fail(ctx, who, e);
+  if (!q) return arg_fail(ctx, who, "mlp is required");
+  if (const char* e = mlp_shape_error(q)) return arg_fail(ctx, who, e);
   for (int l = 0; l < q->n_layers; ++l)
-    if (!q->w[l] || !q->b[l]) return mlp_fail(ctx, who, "w / b: every layer needs w and b");
-  if (rows < 1) return mlp_fail(ctx, who, "rows must be >= 1");
-  if (rows > (int64_t)INT32_MAX - pf::kActRows) return mlp_fail(ctx, who, "rows must be below 2^31 - 64 (the kernels index rows with 32 bits)");
+    if (!q->w[l] || !q->b[l]) return arg_fail(ctx, who, "w / b: every layer needs w and b");
+  if (rows < 1) return arg_fail(ctx, who, "rows must be >= 1");
+  if (rows > (int64_t)INT32_MAX - pf::kActRows) return arg_fail(ctx, who, "rows must be below 2^31 - 64 (the kernels index rows with 32 bits)");
   return PF_OK;
-}
-struct mlp_span {
-  const char* name;
-  const void* p;
-  size_t bytes;
-};
-// the first pair of spans that share a byte, or null
-static const char* mlp_overlap(const mlp_span* s, int count, char* buf, size_t len) {
-  for (int i = 0; i < count; ++i)
-    for (int j = i + 1; j < count; ++j) {
-      const uintptr_t a = (uintptr_t)s[i].p, b = (uintptr_t)s[j].p;
-      if (a < b + s[j].bytes && b < a + s[i].bytes) {
-        snprintf(buf, len, "%s and %s overlap", s[i].name, s[j].name);
-        return buf;
-      }
-    }
-  return nullptr;
 }
 int pf_mlp_forward(pf_ctx* ctx, const pf_mlp* q, const float* x, int64_t rows, float* out, void* stream) {
   static const char* who = "pf_mlp_forward";
-  if (!ctx) return mlp_fail(ctx, who, "ctx is required");
+  if (!ctx) return arg_fail(ctx, who, "ctx is required");
   int rc = mlp_check(ctx, who, q, rows);
   if (rc) return rc;
-  if (!x) return mlp_fail(ctx, who, "x is required");
-  if (!out) return mlp_fail(ctx, who, "out is required");
+  if (!x) return arg_fail(ctx, who, "x is required");
+  if (!out) return arg_fail(ctx, who, "out is required");
   char buf[128];
-  const mlp_span spans[2] = {{"x", x, sizeof(float) * (size_t)rows * q->in_dim}, {"out", out, sizeof(float) * (size_t)rows * q->out_dim}};
-  if (const char* e = mlp_overlap(spans, 2, buf, sizeof(buf))) return mlp_fail(ctx, who, e);
+  const arg_span spans[2] = {{"x", x, sizeof(float) * (size_t)rows * q->in_dim}, {"out", out, sizeof(float) * (size_t)rows * q->out_dim}};
+  if (const char* e = spans_overlap(spans, 2, buf, sizeof(buf))) return arg_fail(ctx, who, e);
   rc = ensure_device(ctx);
   if (rc) return rc;
   // policy_act_kernel itself, the draw off (no log_std), the caller's rows as its observations and out_dim as its action width
@@ -1497,11 +1505,7 @@ int pf_mlp_forward(pf_ctx* ctx, const pf_mlp* q, const float* x, int64_t rows, f
   P.obs0 = x;
   P.mean_out = nullptr;
   const pf::ActK AK{P, out, (int)rows, q->in_dim, q->out_dim, 0u, 0u, 0u, 0ull};
-  const int64_t tiles = (rows + pf::kActRows - 1) / pf::kActRows;
-  const int grid = tiles < (int64_t)ctx->act_grid_cap ? (int)tiles : ctx->act_grid_cap;
-  hipLaunchKernelGGL(pf::policy_act_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, AK);
-  PF_HIP(ctx, hipGetLastError());
-  return PF_OK;
+  return launch_policy_act(ctx, AK, rows, stream);
 }
 size_t pf_mlp_backward_workspace_bytes(const pf_mlp* q, int64_t rows) {
   if (!q || mlp_shape_error(q) || rows < 1) return 0;
@@ -1510,23 +1514,23 @@ size_t pf_mlp_backward_workspace_bytes(const pf_mlp* q, int64_t rows) {
 int pf_mlp_backward(pf_ctx* ctx, const pf_mlp* q, const float* x, const float* grad_out, int64_t rows, float* const grad_w[3], float* const grad_b[3],
                     void* workspace, size_t workspace_bytes, void* stream) {
   static const char* who = "pf_mlp_backward";
-  if (!ctx) return mlp_fail(ctx, who, "ctx is required");
+  if (!ctx) return arg_fail(ctx, who, "ctx is required");
   int rc = mlp_check(ctx, who, q, rows);
   if (rc) return rc;
-  if (!x) return mlp_fail(ctx, who, "x is required");
-  if (!grad_out) return mlp_fail(ctx, who, "grad_out is required");
-  if (!grad_w) return mlp_fail(ctx, who, "grad_w is required");
-  if (!grad_b) return mlp_fail(ctx, who, "grad_b is required");
+  if (!x) return arg_fail(ctx, who, "x is required");
+  if (!grad_out) return arg_fail(ctx, who, "grad_out is required");
+  if (!grad_w) return arg_fail(ctx, who, "grad_w is required");
+  if (!grad_b) return arg_fail(ctx, who, "grad_b is required");
   for (int l = 0; l < q->n_layers; ++l) {
-    if (!grad_w[l]) return mlp_fail(ctx, who, "grad_w: every layer needs its output");
-    if (!grad_b[l]) return mlp_fail(ctx, who, "grad_b: every layer needs its output");
+    if (!grad_w[l]) return arg_fail(ctx, who, "grad_w: every layer needs its output");
+    if (!grad_b[l]) return arg_fail(ctx, who, "grad_b: every layer needs its output");
   }
-  if (!workspace) return mlp_fail(ctx, who, "workspace is required");
+  if (!workspace) return arg_fail(ctx, who, "workspace is required");
   const size_t need = pf_mlp_backward_workspace_bytes(q, rows);
-  if (workspace_bytes < need) return mlp_fail(ctx, who, "workspace_bytes is below pf_mlp_backward_workspace_bytes(mlp, rows)");
+  if (workspace_bytes < need) return arg_fail(ctx, who, "workspace_bytes is below pf_mlp_backward_workspace_bytes(mlp, rows)");
   static const char* const wn[3] = {"grad_w[0]", "grad_w[1]", "grad_w[2]"};
   static const char* const bn[3] = {"grad_b[0]", "grad_b[1]", "grad_b[2]"};
-  mlp_span spans[9];
+  arg_span spans[9];
   int ns = 0;
   spans[ns++] = {"x", x, sizeof(float) * (size_t)rows * q->in_dim};
   spans[ns++] = {"grad_out", grad_out, sizeof(float) * (size_t)rows * q->out_dim};
@@ -1537,7 +1541,7 @@ int pf_mlp_backward(pf_ctx* ctx, const pf_mlp* q, const float* x, const float* g
     spans[ns++] = {bn[l], grad_b[l], sizeof(float) * n_out};
   }
   char buf[128];
-  if (const char* e = mlp_overlap(spans, ns, buf, sizeof(buf))) return mlp_fail(ctx, who, e);
+  if (const char* e = spans_overlap(spans, ns, buf, sizeof(buf))) return arg_fail(ctx, who, e);
   rc = ensure_device(ctx);
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
@@ -1572,7 +1576,7 @@ static const char* adam_error(const pf_adam_args* a, const void* workspace, size
   if (!a->state) return "state is required";
   if (!workspace) return "workspace is required";
   static const char* const kinds[4] = {"param", "grad", "exp_avg", "exp_avg_sq"};
-  mlp_span spans[4 * PF_ADAM_MAX_TENSORS + 3];
+  arg_span spans[4 * PF_ADAM_MAX_TENSORS + 3];
   char names[4 * PF_ADAM_MAX_TENSORS][16];
   int ns = 0;
   int64_t total = 0;
@@ -1599,13 +1603,13 @@ static const char* adam_error(const pf_adam_args* a, const void* workspace, size
   spans[ns++] = {"state", a->state, sizeof(double) * 8};
   spans[ns++] = {"workspace", workspace, need};
   if (a->lr_dev) spans[ns++] = {"lr_dev", a->lr_dev, sizeof(float)};
-  return mlp_overlap(spans, ns, buf, len);
+  return spans_overlap(spans, ns, buf, len);
 }
 int pf_adam_step(pf_ctx* ctx, const pf_adam_args* a, void* workspace, size_t workspace_bytes, void* stream) {
   static const char* who = "pf_adam_step";
-  if (!ctx) return mlp_fail(ctx, who, "ctx is required");
+  if (!ctx) return arg_fail(ctx, who, "ctx is required");
   char buf[128];
-  if (const char* e = adam_error(a, workspace, workspace_bytes, buf, sizeof(buf))) return mlp_fail(ctx, who, e);
+  if (const char* e = adam_error(a, workspace, workspace_bytes, buf, sizeof(buf))) return arg_fail(ctx, who, e);
   int rc = ensure_device(ctx);
   if (rc) return rc;
   pf::AdamK K;

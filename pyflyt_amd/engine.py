@@ -268,16 +268,7 @@ class BatchEngine:
         bit-identical to k x (sample_actions(step_index0 + s) + env_step). `actions`: an open-loop sequence
         [k, n, 4] instead of on-device sampling."""
         k = int(k_steps)
-        t = getattr(self, "_traj", None)
-        if t is None or t["k"] != k:
-            f32 = dict(dtype=torch.float32, device=self.device)
-            t = dict(k=k, obs=torch.empty(k, self.n, self.obs_dim, **f32), reward=torch.empty(k, self.n, **f32),
-                     terminated=torch.empty(k, self.n, dtype=torch.bool, device=self.device),
-                     truncated=torch.empty(k, self.n, dtype=torch.bool, device=self.device),
-                     actions=torch.empty(k, self.n, 7 if self.params.task == L.TASK_ROCKET_LANDING else 4, **f32),
-                     final_obs=torch.zeros(k, self.n, self.obs_dim, **f32) if self.final_obs is not None else None,
-                     final_info=torch.zeros(k, self.n, 2, dtype=torch.int32, device=self.device) if self.final_info is not None else None)
-            self._traj = t
+        t = self._traj_tensors(k)
         self._check_f32(actions, (k, self.n, self.action_dim), "actions")
         keep = store_actions and actions is None  # (the kernels sample in registers; the draws are written out only on request)
         b = self._buffers(actions=actions, actions_out=t["actions"] if keep else None)
@@ -288,22 +279,10 @@ class BatchEngine:
         self._cur_obs = t["obs"][k - 1]
         return t["obs"], t["reward"], t["terminated"], t["truncated"], (t["actions"] if actions is None and store_actions else actions)
 
-    def rollout_policy(self, policy, k_steps: int, step_index0: int = 0, store_mean: bool = False):
-        """pf_rollout_policy: `k_steps` env steps in one launch with every action computed on the device by `policy` (an MLPPolicy)
-        from the observation the env has just written -- the closed loop of an on-policy collector. The first step acts on the
-        engine's current observation (self.obs after a reset or a step, the last row of the previous rollout). Returns
-        (obs [k, n, D], reward [k, n], terminated [k, n], truncated [k, n], actions [k, n, 4]) -- the same tensors as rollout(),
-        overwritten by the next call -- and, with store_mean, the policy's means [k, n, 4] as a sixth. `step_index0` keys the
-        exploration noise: advance it by k between calls. QuadX-Hover / QuadX-Waypoints on the specialised kernel; everything else
-        raises PyFlytAmdError with the library's message -- rollout_policy_steps is the same loop on every env."""
-        from .policy import MLPPolicy
-
-        if not isinstance(policy, MLPPolicy):
-            raise ValueError(f"policy must be a pyflyt_amd.MLPPolicy, got {type(policy).__name__}")
-        k = int(k_steps)
-        q = policy.fill(L.PfPolicy(), self)
+    def _traj_tensors(self, k):
+        """The trajectory tensors rollout(), rollout_policy() and rollout_policy_steps() share: the cached ones for this k, or new ones."""
         t = getattr(self, "_traj", None)
-        if t is None or t["k"] != k:  # (rollout()'s trajectory tensors, shared with it)
+        if t is None or t["k"] != k or t["actions"].shape[-1] != self.action_dim:
             f32 = dict(dtype=torch.float32, device=self.device)
             t = dict(k=k, obs=torch.empty(k, self.n, self.obs_dim, **f32), reward=torch.empty(k, self.n, **f32),
                      terminated=torch.empty(k, self.n, dtype=torch.bool, device=self.device),
@@ -312,6 +291,31 @@ class BatchEngine:
                      final_obs=torch.zeros(k, self.n, self.obs_dim, **f32) if self.final_obs is not None else None,
                      final_info=torch.zeros(k, self.n, 2, dtype=torch.int32, device=self.device) if self.final_info is not None else None)
             self._traj = t
+        return t
+
+    @staticmethod
+    def _check_policy(policy):
+        from .policy import MLPPolicy
+
+        if not isinstance(policy, MLPPolicy):
+            raise ValueError(f"policy must be a pyflyt_amd.MLPPolicy, got {type(policy).__name__}")
+
+    def _policy_block(self, policy):
+        """The pf_policy block of `policy` for this engine (MLPPolicy.fill checks its widths and device)."""
+        self._check_policy(policy)
+        return policy.fill(L.PfPolicy(), self)
+
+    def rollout_policy(self, policy, k_steps: int, step_index0: int = 0, store_mean: bool = False):
+        """pf_rollout_policy: `k_steps` env steps in one launch with every action computed on the device by `policy` (an MLPPolicy)
+        from the observation the env has just written -- the closed loop of an on-policy collector. The first step acts on the
+        engine's current observation (self.obs after a reset or a step, the last row of the previous rollout). Returns
+        (obs [k, n, D], reward [k, n], terminated [k, n], truncated [k, n], actions [k, n, 4]) -- the same tensors as rollout(),
+        overwritten by the next call -- and, with store_mean, the policy's means [k, n, 4] as a sixth. `step_index0` keys the
+        exploration noise: advance it by k between calls. QuadX-Hover / QuadX-Waypoints on the specialised kernel; everything else
+        raises PyFlytAmdError with the library's message -- rollout_policy_steps is the same loop on every env."""
+        q = self._policy_block(policy)
+        k = int(k_steps)
+        t = self._traj_tensors(k)
         mean = None
         if store_mean:
             mean = t.get("mean")
@@ -326,11 +330,7 @@ class BatchEngine:
         engine with an env task. Returns the actions [n, action_dim] (`out`, or a new tensor), and with `mean_out` [n, action_dim]
         the pair (actions, mean_out). The same network arithmetic and the same draw as rollout_policy's step `step_index`:
         k x (policy_act(step_index0 + s), env_step) is rollout_policy(k, step_index0) bit for bit where that exists."""
-        from .policy import MLPPolicy
-
-        if not isinstance(policy, MLPPolicy):
-            raise ValueError(f"policy must be a pyflyt_amd.MLPPolicy, got {type(policy).__name__}")
-        q = policy.fill(L.PfPolicy(), self)
+        q = self._policy_block(policy)
         obs = self._cur_obs if obs is None else self._check_f32(obs, (self.n, self.obs_dim), "obs")
         if out is None:
             out = torch.empty(self.n, self.action_dim, dtype=torch.float32, device=self.device)
@@ -350,25 +350,13 @@ class BatchEngine:
         results are bit-identical. Needs an auto-reset mode and PF_NOISE_OFF / PF_NOISE_PHILOX (ValueError otherwise) -- so the
         multi-agent tasks (dogfight, multi-agent hover), which exist with auto-reset OFF only, are refused here: their loop is
         policy_act and env_step, with the culling of finished agents in between."""
-        from .policy import MLPPolicy
-
-        if not isinstance(policy, MLPPolicy):
-            raise ValueError(f"policy must be a pyflyt_amd.MLPPolicy, got {type(policy).__name__}")
+        self._check_policy(policy)
         k = int(k_steps)
         if k < 1:
             raise ValueError(f"k_steps must be >= 1, got {k_steps}")
         self._check_stepwise()
         q = policy.fill(L.PfPolicy(), self)
-        t = getattr(self, "_traj", None)
-        if t is None or t["k"] != k or t["actions"].shape[-1] != self.action_dim:  # (rollout()'s trajectory tensors, shared with it)
-            f32 = dict(dtype=torch.float32, device=self.device)
-            t = dict(k=k, obs=torch.empty(k, self.n, self.obs_dim, **f32), reward=torch.empty(k, self.n, **f32),
-                     terminated=torch.empty(k, self.n, dtype=torch.bool, device=self.device),
-                     truncated=torch.empty(k, self.n, dtype=torch.bool, device=self.device),
-                     actions=torch.empty(k, self.n, self.action_dim, **f32),
-                     final_obs=torch.zeros(k, self.n, self.obs_dim, **f32) if self.final_obs is not None else None,
-                     final_info=torch.zeros(k, self.n, 2, dtype=torch.int32, device=self.device) if self.final_info is not None else None)
-            self._traj = t
+        t = self._traj_tensors(k)
         mean = None
         if store_mean:
             mean = t.get("mean")
@@ -446,10 +434,7 @@ class BatchEngine:
         the launch writes rows 1 .. k: obs_all[:-1] are the policy's inputs and obs_all[1:] the next observations, both views -- the
         trajectory is never copied. Returns the dict of tensors (obs_all, obs = obs_all[1:], reward, terminated, truncated, actions,
         mean, final_obs / final_info under SAME_STEP), overwritten by the next call with the same k_steps."""
-        from .policy import MLPPolicy
-
-        if not isinstance(policy, MLPPolicy):
-            raise ValueError(f"policy must be a pyflyt_amd.MLPPolicy, got {type(policy).__name__}")
+        self._check_policy(policy)
         k = int(k_steps)
         if k < 1:
             raise ValueError(f"k_steps must be >= 1, got {k_steps}")
