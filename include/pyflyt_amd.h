@@ -330,6 +330,10 @@ int pf_n_lanes(const pf_ctx* ctx);
 /* which env kernel pf_env_step / pf_env_reset launch for this context: 0 the generic env_kernel, 1 the
  * specialised QuadX mode-0 kernel (Hover / Waypoints / MA-Hover), 2 the specialised Fixedwing-Waypoints kernel */
 int pf_ctx_is_specialised(const pf_ctx* ctx);
+/* 1 when this context's pf_env_step launches (no mask; pf_env_reset never) run the specialised QuadX kernel with the call shape fixed
+ * at compile time: Hover / Waypoints, flight mode 0, contact response on, PF_NOISE_OFF or PF_NOISE_PHILOX, NEXT_STEP auto-reset,
+ * the task's default env_step_ratio (Hover 3, Waypoints 4), quaternion observations, dense reward. Same state, same results bit for bit; 0 everywhere else. */
+int pf_ctx_step_is_fixed(const pf_ctx* ctx);
 
 /* env.reset(): gym_envs/quadx_envs/quadx_base_env.py:149-212 (begin_reset + end_reset incl. the
  * 10 settle Aviary steps), quadx_hover_env.py:70-83, quadx_waypoints_env.py:112-125,

@@ -745,6 +745,7 @@ struct env_choice {
   env_family family;
   bool cr, md, sh;  // quadx: quadx_m0_env_kernel's CR / MD / SH, as K implies them
   bool wps1;        // quadx, fixedwing_wp: the one-wave-per-SIMD instantiation (WPS = 1, 512 registers)
+  bool fixed;       // quadx: pf_env_step without a mask runs the instantiation with the call shape pinned (quadx_fast.hpp: FIXED)
 };
 
 struct pf_ctx {
@@ -785,9 +786,10 @@ static int hip_fail(pf_ctx* ctx, hipError_t e, const char* where) {
 
 // Which env kernel a context runs, and its launch-invariant template arguments; fills K, FK and fsurf for the specialised kernels.
 // The only reader of the environment overrides, which exist for the tests: PF_DISABLE_FAST forces the generic kernels,
-// PF_NO_LEAN_KERNEL the two-wave instantiations, PF_NO_CALM_PATH turns the specialised QuadX kernel's calm-wave ticks off.
+// PF_NO_LEAN_KERNEL the two-wave instantiations, PF_NO_CALM_PATH turns the specialised QuadX kernel's calm-wave ticks off,
+// PF_NO_FIXED_STEP keeps pf_env_step on the general one-step instantiation.
 static env_choice select_env_kernel(const pf_params& P, int n_lanes, int device, pf::QuadK& K, pf::FwK& FK, pf::FwTable& fsurf) {
-  env_choice c{env_family::generic, false, false, false, false};
+  env_choice c{env_family::generic, false, false, false, false, false};
   const bool fast = getenv("PF_DISABLE_FAST") == nullptr;
   int cus = 0;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) cus = 0;
@@ -811,6 +813,12 @@ static env_choice select_env_kernel(const pf_params& P, int n_lanes, int device,
     //  independent lanes as well; since round 5 the cascaded flight modes: their fp64 controller needs the 512 registers -- 408 B of
     //  stack per lane under 256. It solves floor contacts in registers, four slots = the incident face: quad_floor_solve)
     c.wps1 = one_wave && P.contact_manifold_points < 8 && c.cr && !c.sh;
+    // (the fixed call shape -- quadx_fast.hpp, FIXED -- is instantiated for what the training loops run: Hover / Waypoints with the contact
+    //  response on, noise drawn on the device or off, and exactly the values it pins)
+    const int fixed_ratio = P.task == PF_TASK_HOVER ? pf::kQuadFixedRatio<PF_TASK_HOVER> : pf::kQuadFixedRatio<PF_TASK_WAYPOINTS>;
+    c.fixed = (P.task == PF_TASK_HOVER || P.task == PF_TASK_WAYPOINTS) && c.cr && !c.md && !c.sh && P.noise_mode != PF_NOISE_INJECT &&
+              P.autoreset == PF_AUTORESET_NEXT_STEP && P.env_step_ratio == fixed_ratio && P.angle_repr == 1 && P.sparse_reward == 0 &&
+              getenv("PF_NO_FIXED_STEP") == nullptr;
   } else if (fast && pf::fwk_from_params(P, FK, fsurf)) {
     c.family = env_family::fixedwing_wp;
     c.wps1 = one_wave;
@@ -841,10 +849,14 @@ static auto by_noise_roll(int noise, int roll, Pick pick) {
   return philox ? pick(int_c<PF_NOISE_PHILOX>{}, int_c<0>{}) : pick(int_c<PF_NOISE_OFF>{}, int_c<0>{});
 }
 
+// fixed_call: a pf_env_step without a mask of a context inside the fixed shape's envelope (c.fixed: CR, mode 0, independent lanes)
 template <int TASK, int NZ, int R>
-static auto quadx_m0_kernel(const env_choice& c) {
+static auto quadx_m0_kernel(const env_choice& c, bool fixed_call) {
   constexpr bool MA = TASK == PF_TASK_MA_HOVER;  // (c.sh: a shared world, the PettingZoo task only)
   using namespace pf;
+  if constexpr (R == 0 && NZ != PF_NOISE_INJECT && !MA)
+    if (fixed_call)
+      return c.wps1 ? quadx_m0_env_kernel<TASK, NZ, 64, 0, true, false, false, 1, true> : quadx_m0_env_kernel<TASK, NZ, 64, 0, true, false, false, 2, true>;
   if (c.md)
     return c.sh ? quadx_m0_env_kernel<TASK, NZ, 64, R, true, true, MA, 2>
                 : c.wps1 ? quadx_m0_env_kernel<TASK, NZ, 64, R, true, true, false, 1> : quadx_m0_env_kernel<TASK, NZ, 64, R, true, true, false, 2>;
@@ -894,10 +906,11 @@ static int launch_env(pf_ctx* ctx, const pf_buffers* b, int op, const uint8_t* m
   hipStream_t s = (hipStream_t)stream;
   switch (c.family) {
     case env_family::quadx: {
+      const bool fixed_call = c.fixed && roll == 0 && op == pf::OP_STEP && mask == nullptr;
       const auto kernel = by_noise_roll(P.noise_mode, roll, [&](auto NZ, auto R) {
-        if (P.task == PF_TASK_HOVER) return quadx_m0_kernel<PF_TASK_HOVER, NZ, R>(c);
-        if (P.task == PF_TASK_MA_HOVER) return quadx_m0_kernel<PF_TASK_MA_HOVER, NZ, R>(c);
-        return quadx_m0_kernel<PF_TASK_WAYPOINTS, NZ, R>(c);
+        if (P.task == PF_TASK_HOVER) return quadx_m0_kernel<PF_TASK_HOVER, NZ, R>(c, fixed_call);
+        if (P.task == PF_TASK_MA_HOVER) return quadx_m0_kernel<PF_TASK_MA_HOVER, NZ, R>(c, fixed_call);
+        return quadx_m0_kernel<PF_TASK_WAYPOINTS, NZ, R>(c, fixed_call);
       });
       const int grid = (ctx->n + 64 * pf::kQuadWPB - 1) / (64 * pf::kQuadWPB);
       hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * pf::kQuadWPB), 0, s, ctx->K, *b, ctx->P_dev, ctx->n, ctx->lane0, op, mask, k_steps, step0,
@@ -1114,6 +1127,7 @@ int pf_ctx_is_specialised(const pf_ctx* ctx) {
   const env_family f = ctx->ek.family;
   return f == env_family::quadx ? 1 : ((f == env_family::fixedwing_wp || f == env_family::dogfight_fast) ? 2 : 0);
 }
+int pf_ctx_step_is_fixed(const pf_ctx* ctx) { return ctx->ek.family == env_family::quadx && ctx->ek.fixed ? 1 : 0; }
 
 static int env_reset_or_step(pf_ctx* ctx, const pf_buffers* b, int op, const uint8_t* mask, void* stream) {
   if (!ctx || !b || !b->state || !b->obs) return fail(ctx, PF_ERR_ARG, "pf_env_*: state and obs buffers are required");

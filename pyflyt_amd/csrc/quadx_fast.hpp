@@ -1278,6 +1278,10 @@ struct QuadSpare {
 // One wavefront per workgroup: no barrier, no inter-wave traffic. (Multi-wave workgroups were measured in round 3 and dropped --
 // profiles/r06/experiments/ab_switches.patch has the switch; the index arithmetic below keeps the general form.)
 constexpr int kQuadWPB = 1;
+// The Aviary steps per env step the fixed call shape (FIXED, below) pins: the task's default agent rate under the 120 Hz control loop --
+// QuadX-Hover 40 Hz, QuadX-Waypoints 30 Hz (quadx_hover_env.py:32-37, quadx_waypoints_env.py:38-47).
+template <int TASK>
+constexpr int kQuadFixedRatio = TASK == PF_TASK_WAYPOINTS ? 4 : 3;
 // MODES: false = flight mode 0 only; true = the flight mode is K.mode, -1 .. 7 (cascaded PIDs; their memories in state groups
 // 7-11 and, at reset, the z PIDs inside the settle recurrence).
 // SHARED (PF_TASK_MA_HOVER only): the K.apw agents of an env share one world (pose / contact exchange before every tick).
@@ -1286,12 +1290,24 @@ constexpr int kQuadWPB = 1;
 // nothing to run -- 11.6 -> 11.2 us per hover step at 65 536 lanes; at 524 288 lanes, 71 us against 57 us with two waves resident.
 // (the shared-world instantiations need more than 256 registers whatever they are asked for -- the compiler's "desired occupancy
 //  was 2, final occupancy is 1" in rounds 4 / 5 --: their budget says so)
-template <int TASK, int NOISE, int LPW, int ROLL, bool CR, bool MODES = false, bool SHARED = false, int WPS = 2>
+// FIXED (ROLL == 0, flight mode 0, independent lanes, noise drawn on device or off): the call shape of every training loop's hot call,
+// pinned at compile time -- pf_env_step without a mask, NEXT_STEP auto-reset, the task's own number of Aviary steps per env step
+// (kQuadFixedRatio), quaternion observations, dense reward. The launcher (pyflyt_amd.hip: launch_env) picks it for exactly that call of exactly such a context; the body is the
+// general one with those six wave-uniform values constant, so the reset op, the SAME_STEP block, the Euler branch and the loop bound's
+// reads fold away -- the arithmetic and its order are untouched, and the state layout is the same: the two interleave freely.
+template <int TASK, int NOISE, int LPW, int ROLL, bool CR, bool MODES = false, bool SHARED = false, int WPS = 2, bool FIXED = false>
 __global__ void __launch_bounds__(64 * kQuadWPB, SHARED ? 1 : WPS) quadx_m0_env_kernel(const QuadK K, const pf_buffers B, const pf_params* __restrict__ Pfull,
-                                                             const int n, const uint64_t lane0, const int op,
-                                                             const uint8_t* __restrict__ mask, const int k_steps, const uint32_t step0,
+                                                             const int n, const uint64_t lane0, const int op_arg,
+                                                             const uint8_t* __restrict__ mask_arg, const int k_steps, const uint32_t step0,
                                                              uint32_t* launch_ctr, const PolicyK PK) {
   constexpr bool ROLLOUT = ROLL != 0;
+  static_assert(!FIXED || (ROLL == 0 && !MODES && !SHARED && NOISE != PF_NOISE_INJECT), "the fixed call shape exists for the one-step, mode-0, independent-lane kernels");
+  const int op = FIXED ? (int)OP_STEP : op_arg;
+  const uint8_t* const mask = FIXED ? nullptr : mask_arg;
+  const int k_autoreset = FIXED ? (int)PF_AUTORESET_NEXT_STEP : K.autoreset;
+  const int k_step_ratio = FIXED ? kQuadFixedRatio<TASK> : K.env_step_ratio;
+  const bool k_quat = FIXED || K.angle_repr != 0;
+  const bool k_sparse = !FIXED && K.task_sparse != 0;
   // (see QuadSpare) REKEY: a reset's draws are keyed by the counter at the previous reset; SPARE: ... and prepared ahead. launch_ctr: one
   // word per workgroup (kCtrStride apart) in device memory, the env steps this context has taken -- the refill cadence is a function of that count alone.
   // It is DEVICE state (round 5 passed the host's count as a kernel argument, which a HIP-graph capture bakes in: a captured
@@ -1403,7 +1419,7 @@ __global__ void __launch_bounds__(64 * kQuadWPB, SHARED ? 1 : WPS) quadx_m0_env_
       // (SPARE: every lane, every launch -- 16 B a lane in Hover, 80 B in Waypoints that only the restarting lanes use. Requested
       //  by those lanes alone, once their flags are here, the words came from HBM and not from the cache the state groups of the
       //  previous launch still sit in: 2.8 us in front of the reset, as long as generating them had taken -- profiles/r05)
-      const bool need_sp = SPARE || ROLLOUT || in11 || op == OP_RESET || K.autoreset == PF_AUTORESET_SAME_STEP ||
+      const bool need_sp = SPARE || ROLLOUT || in11 || op == OP_RESET || k_autoreset == PF_AUTORESET_SAME_STEP ||
                            (__float_as_int(gi.y) & (PF_F_TERMINATED | PF_F_TRUNCATED)) != 0;
       if (need_sp) {
         const float4 gk = SPARE ? gs7 : (in11 ? cm4 : (MODES ? cm0 : Sin[(size_t)7 * N + li]));
@@ -1507,7 +1523,7 @@ __global__ void __launch_bounds__(64 * kQuadWPB, SHARED ? 1 : WPS) quadx_m0_env_
   float reward = 0.0f;
   bool pop_pending = false;
   bool was_reset = false;
-  const int D = (K.angle_repr ? 13 : 12) + 8 + (TASK == PF_TASK_WAYPOINTS ? (kYaw ? 4 : 3) * K.num_targets : (TASK == PF_TASK_MA_HOVER ? 3 : 0));
+  const int D = (k_quat ? 13 : 12) + 8 + (TASK == PF_TASK_WAYPOINTS ? (kYaw ? 4 : 3) * K.num_targets : (TASK == PF_TASK_MA_HOVER ? 3 : 0));
   const int settle_ticks = K.settle_steps * 2;
 
   auto pop_target = [&]() {
@@ -1901,11 +1917,11 @@ __global__ void __launch_bounds__(64 * kQuadWPB, SHARED ? 1 : WPS) quadx_m0_env_
       quat t = quat_from_half_angles(cr, sr, cp, sp, cy, sy);
       float inv = frsq(fmaf(t.x, t.x, fmaf(t.y, t.y, fmaf(t.z, t.z, t.w * t.w))));
       qe = quat{t.x * inv, t.y * inv, t.z * inv, t.w * inv};
-      if (!K.angle_repr) rpy = v3{fast_atan2(ar, br), fast_asin(sarg), fast_atan2(ay, by)};
+      if (!k_quat) rpy = v3{fast_atan2(ar, br), fast_asin(sarg), fast_atan2(ay, by)};
     }
     int k = 0;
     row[k++] = V.wb.x; row[k++] = V.wb.y; row[k++] = V.wb.z;
-    if (K.angle_repr) { row[k++] = qe.x; row[k++] = qe.y; row[k++] = qe.z; row[k++] = qe.w; }
+    if (k_quat) { row[k++] = qe.x; row[k++] = qe.y; row[k++] = qe.z; row[k++] = qe.w; }
     else { row[k++] = rpy.x; row[k++] = rpy.y; row[k++] = rpy.z; }
     row[k++] = V.vb.x; row[k++] = V.vb.y; row[k++] = V.vb.z;
     row[k++] = V.p.x; row[k++] = V.p.y; row[k++] = V.p.z;
@@ -1983,7 +1999,7 @@ __global__ void __launch_bounds__(64 * kQuadWPB, SHARED ? 1 : WPS) quadx_m0_env_
   // ---------------------------------------------------------------- reset (NEXT_STEP / explicit)
   bool do_reset;
   if (op == OP_RESET) do_reset = active;
-  else do_reset = (K.autoreset == PF_AUTORESET_NEXT_STEP) && (term || trunc) && active;
+  else do_reset = (k_autoreset == PF_AUTORESET_NEXT_STEP) && (term || trunc) && active;
   act0 = act1 = act2 = act3 = 0.f;
   reward = 0.0f;
   was_reset = false;
@@ -2064,7 +2080,7 @@ __global__ void __launch_bounds__(64 * kQuadWPB, SHARED ? 1 : WPS) quadx_m0_env_
     if (!calm && tid == 0) trace_add(&g_calm_trace[0], 1ull);  // waves that keep the call site this step (rare: no contention)
 #endif
   }
-  for (int s = 0; s < K.env_step_ratio; ++s) {
+  for (int s = 0; s < k_step_ratio; ++s) {
     if (!__any(go)) break;
     // a wave that is not calm over the whole env step (some lane is low) still is over most of its Aviary steps: the same bound
     // over the two ticks ahead (a lane sinks a few millimetres in them) -- evaluated in those waves only
@@ -2127,7 +2143,7 @@ __global__ void __launch_bounds__(64 * kQuadWPB, SHARED ? 1 : WPS) quadx_m0_env_
       if (TASK == PF_TASK_MA_HOVER) {  // ma_quadx_hover_env.py:168-205: additive penalties, no early exit
         if (!NFX && V.contact_step) { reward -= 100.0f; flags |= PF_F_INFO_COLLISION; term = true; }
         if (dot(V.p, V.p) > K.dome2) { reward -= 100.0f; flags |= PF_F_INFO_OOB; term = true; }
-        if (!K.task_sparse) {
+        if (!k_sparse) {
           float dx = V.p.x - tgt[0][0], dy = V.p.y - tgt[0][1], dz = V.p.z - tgt[0][2];
           float lin = fsqrt(fmaf(dx, dx, fmaf(dy, dy, dz * dz)));
           // roll, pitch of getEulerFromQuaternion from the rotation matrix derive() just built (unit q):
@@ -2145,7 +2161,7 @@ __global__ void __launch_bounds__(64 * kQuadWPB, SHARED ? 1 : WPS) quadx_m0_env_
       if (dot(V.p, V.p) > K.dome2) { reward = -100.0f; flags |= PF_F_INFO_OOB; term = true; } // :264-267
       }
       if (TASK == PF_TASK_HOVER) {
-        if (!K.task_sparse) {  // quadx_hover_env.py:120-138
+        if (!k_sparse) {  // quadx_hover_env.py:120-138
           float dz = V.p.z - 1.0f;
           float lin = fsqrt(fmaf(V.p.x, V.p.x, fmaf(V.p.y, V.p.y, dz * dz)));
           // roll, pitch of getEulerFromQuaternion (gimbal branch: roll = 0, |pitch| = pi/2)
@@ -2161,7 +2177,7 @@ __global__ void __launch_bounds__(64 * kQuadWPB, SHARED ? 1 : WPS) quadx_m0_env_
           reward += 1.0f;
         }
       } else if (TASK == PF_TASK_WAYPOINTS) {
-        if (!K.task_sparse) {  // quadx_waypoints_env.py:183-192
+        if (!k_sparse) {  // quadx_waypoints_env.py:183-192
           float progress = (isinf(old_dist + new_dist)) ? 0.0f : old_dist - new_dist;
           reward += __builtin_fmaxf(3.0f * progress, 0.0f);
           reward = fmaf(K.wp_dist_reward, frcp(new_dist), reward);
@@ -2190,7 +2206,7 @@ __global__ void __launch_bounds__(64 * kQuadWPB, SHARED ? 1 : WPS) quadx_m0_env_
   }
 
   // ---------------------------------------------------------------- SAME_STEP auto-reset
-  if (K.autoreset == PF_AUTORESET_SAME_STEP) {
+  if (k_autoreset == PF_AUTORESET_SAME_STEP) {
     const bool same = stepping && (term || trunc);
     if (__any(same)) {
       if (B.final_obs != nullptr) {  // terminal observation, before the state is re-initialised

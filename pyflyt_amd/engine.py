@@ -50,6 +50,8 @@ class BatchEngine:
         L.check(self.lib.pf_ctx_create(C.byref(params), self.n, index, self.lane_offset, C.byref(self._ctx)))
         self.groups = self.lib.pf_state_groups(self._ctx)
         self.obs_dim = self.lib.pf_obs_dim(self._ctx)
+        # env_step without a mask runs the kernel with its call shape fixed at compile time (include/pyflyt_amd.h: pf_ctx_step_is_fixed)
+        self.step_is_fixed = bool(self.lib.pf_ctx_step_is_fixed(self._ctx))
         f32 = dict(dtype=torch.float32, device=self.device)
         self.state = torch.zeros(self.groups, self.n, 4, **f32)
         self.obs = torch.zeros(self.n, self.obs_dim, **f32)
