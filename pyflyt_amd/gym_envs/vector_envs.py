@@ -25,6 +25,7 @@ from typing import Any
 import numpy as np
 import torch
 
+from .. import _checks as K
 from .. import _lib as L
 from ..engine import BatchEngine
 from ..params import build_params
@@ -143,12 +144,12 @@ class _VecEnvBase:
             if mask is not None:
                 raise ValueError("cannot re-seed and partially reset in one call")
             self._seed = int(seed)
-            moments = getattr(self.engine, "_ts", None)  # (traj_stats' running moments outlive the engine; its carries do not)
+            moments = self.engine.made_moments()  # (traj_stats' running moments outlive the engine; its carries do not)
             self.engine.close()
             self._build(self._seed)
             if moments is not None:
-                self.engine.obs_moments.copy_(moments["obs_moments"])
-                self.engine.ret_moments.copy_(moments["ret_moments"])
+                self.engine.obs_moments.copy_(moments[0])
+                self.engine.ret_moments.copy_(moments[1])
         elif seed is not None and mask is None:
             # same seed: restart the event counters so that the rollout repeats exactly
             self.engine.state.zero_()
@@ -246,19 +247,14 @@ class _VecEnvBase:
         and the first episode_return / episode_length after it would lack those steps -- reset() the env before switching."""
         if self._needs_reset:
             raise RuntimeError("call reset() before collect()")
-        for name, x in (("stats", stats), ("normalize_reward", normalize_reward)):
-            if not isinstance(x, bool):
-                raise ValueError(f"{name} must be a bool, got {type(x).__name__}")
+        K.boolean(stats, "stats")
+        K.boolean(normalize_reward, "normalize_reward")
         stats = stats or normalize_reward
-        from ..policy import MLPPolicy
-
-        if not isinstance(policy, MLPPolicy):
-            raise ValueError(f"policy must be a pyflyt_amd.MLPPolicy, got {type(policy).__name__}")
+        BatchEngine._check_policy(policy)
         if not callable(value_fn):
             raise ValueError(f"value_fn must be callable (a float32 [M, D] tensor -> [M] or [M, 1]), got {type(value_fn).__name__}")
-        for name, x in (("gamma", gamma), ("lam", lam)):
-            if not 0.0 <= float(x) <= 1.0:
-                raise ValueError(f"{name} must be finite and in [0, 1], got {x}")
+        K.unit_interval(gamma, "gamma")
+        K.unit_interval(lam, "lam")
         eng, k = self.engine, int(k_steps)
         if not eng._fused_policy(fused):  # (refused before the flags are read or anything is launched)
             eng._check_stepwise()

@@ -1,0 +1,380 @@
+"""The training operations of a BatchEngine -- pf_gae, pf_traj_stats, pf_ppo_loss, pf_mlp_forward / pf_mlp_backward, pf_adam_step --
+and the plumbing they share with the env level in engine.py: the tensor check bound to the engine's device, the launch wrapper and
+the state an engine makes at first use. A base class without __init__: everything here works on an engine that has only `n`,
+`device`, `params` and `_ctx` (and `obs_dim` for traj_stats), which is how the CPU tests reach the refusals.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import torch
+
+from . import _checks as K
+from . import _lib as L
+
+
+def _ptr(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+try:  # the raw handle of torch's current stream without building a torch.cuda.Stream object (0.2 us against 1.5 us per call)
+    _raw_stream = torch._C._cuda_getCurrentRawStream
+except AttributeError:  # pragma: no cover
+    def _raw_stream(index):
+        return torch.cuda.current_stream(index).cuda_stream
+
+
+class TrainOps:
+    # state made at first use, by _lazy only: None until then (class attributes, so an engine made without __init__ has them too)
+    _traj = None      # dict: the trajectory tensors rollout(), rollout_policy() and rollout_policy_steps() share, for the last k
+    _ctraj = None     # dict: collect_rollout()'s trajectory tensors (observations in one [k + 1, n, D] buffer), for the last k
+    _gae_out = None   # dict: gae()'s advantages / returns / logp / valid, for the last k
+    _ts = None        # dict: traj_stats()'s per-lane carries, summary, the two running moment blocks, the per-step outputs of the last k
+    _ppo_out = None   # dict: ppo_loss()'s gradients for the last (M, A), stats, and the count of calls
+    _mlp_fwd = None   # {(rows, out_dim): mlp_forward()'s output}
+    _mlp_bwd = None   # {(rows, layer shapes): mlp_backward()'s gradients, pointer arrays and workspace}
+    _adam = None      # {addresses: adam_step()'s filled argument block}, the 64 most recent
+    _adam_ws = None   # {total elements: adam_step()'s workspace}
+
+    def _lazy(self, name, make, keep=None):
+        """self.<name> of the list above: made by make() at first use, and again when keep(it) is false (tensors of another size)."""
+        v = getattr(self, name)
+        if v is None or (keep is not None and not keep(v)):
+            v = make()
+            setattr(self, name, v)
+        return v
+
+    # ------------------------------------------------------------------ helpers
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _launch(self, fn, *args):
+        """fn(ctx, *args, stream) on the engine's device and torch's current stream; a refusal raises with the context's message."""
+        with torch.cuda.device(self.device):
+            L.check(fn(self._ctx, *args, self._stream()), self._ctx)
+
+    def _traj_args(self, reward, terminated, truncated):
+        """What gae and traj_stats ask of a trajectory before anything else: reward [k, n] float32 with k >= 1, terminated and
+        truncated [k, n] bool / uint8. Returns k."""
+        K.ranked(reward, "reward", f"{{name}} must be a float32 tensor of shape (k, {self.n})", 2)
+        k = int(reward.shape[0])
+        if k < 1:
+            raise ValueError("reward must hold at least one step")
+        K.tensor(self.device, reward, "reward", (k, self.n))
+        for name, x in (("terminated", terminated), ("truncated", truncated)):
+            if x is None:
+                raise ValueError(f"{name} is required")
+            K.tensor(self.device, x, name, (k, self.n), K.FLAGS)
+        return k
+
+    def _episode_start(self, episode_start):
+        """The rest of that preamble, which comes after the scalars in both: episode_start [n] bool / uint8, NEXT_STEP only."""
+        if self.params.autoreset != L.AUTORESET_NEXT_STEP and episode_start is not None:
+            raise ValueError("episode_start must be None outside NEXT_STEP auto-reset (no other mode has reset steps)")
+        K.tensor(self.device, episode_start, "episode_start", (self.n,), K.FLAGS)
+
+    # ------------------------------------------------------------------ advantages and episode statistics
+    def gae(self, reward, terminated, truncated, values, gamma: float = 0.99, lam: float = 0.95, final_values=None, episode_start=None,
+            actions=None, mean=None, log_std=None):
+        """pf_gae: which steps of a trajectory are real transitions, their advantages and returns by generalised advantage
+        estimation, and the log-probabilities of the actions (include/pyflyt_amd.h has the semantics). reward / terminated /
+        truncated [k, n] as a rollout wrote them; values [k + 1, n]: row s the value of the observation the policy saw at step s,
+        row k that of the last observation; final_values [k, n]: the value of final_obs, SAME_STEP only (and required there);
+        episode_start [n]: NEXT_STEP only, lanes that were waiting for their reset when the rollout began; actions, mean [k, n, A]
+        and log_std [A] together, or none of them (then logp is None). Returns (advantages [k, n], returns [k, n], logp [k, n] or
+        None, valid [k, n] bool): tensors the engine owns, overwritten by the next call with the same k."""
+        k, A = self._traj_args(reward, terminated, truncated), self.action_dim
+        if values is None:
+            raise ValueError("values is required")
+        K.tensor(self.device, values, "values", (k + 1, self.n))
+        K.unit_interval(gamma, "gamma")
+        K.unit_interval(lam, "lam")
+        same = self.params.autoreset == L.AUTORESET_SAME_STEP
+        if same and final_values is None:
+            raise ValueError("final_values is required under SAME_STEP auto-reset (the value of the terminal observation in final_obs)")
+        if not same and final_values is not None:
+            raise ValueError("final_values must be None outside SAME_STEP auto-reset (there is no final_obs)")
+        self._episode_start(episode_start)
+        K.tensor(self.device, final_values, "final_values", (k, self.n))
+        given = [x is not None for x in (actions, mean, log_std)]
+        if any(given) and not all(given):
+            raise ValueError("actions, mean and log_std come together or not at all")
+        K.tensor(self.device, actions, "actions", (k, self.n, A))
+        K.tensor(self.device, mean, "mean", (k, self.n, A))
+        K.tensor(self.device, log_std, "log_std", (A,))
+        o = self._lazy("_gae_out", lambda: dict(k=k, valid=torch.empty(k, self.n, dtype=torch.bool, device=self.device),
+                                                **{name: torch.empty(k, self.n, dtype=torch.float32, device=self.device) for name in ("advantages", "returns", "logp")}),
+                       keep=lambda o: o["k"] == k)
+        a = L.PfGae()
+        a.gamma = float(gamma)
+        setattr(a, "lambda", float(lam))
+        a.reward, a.terminated, a.truncated, a.values = _ptr(reward), _ptr(terminated), _ptr(truncated), _ptr(values)
+        a.final_values, a.episode_start = _ptr(final_values), _ptr(episode_start)
+        a.actions, a.mean, a.log_std = _ptr(actions), _ptr(mean), _ptr(log_std)
+        a.advantages, a.returns, a.valid_out = _ptr(o["advantages"]), _ptr(o["returns"]), _ptr(o["valid"])
+        a.logp_out = _ptr(o["logp"]) if all(given) else None
+        self._launch(self.lib.pf_gae, C.byref(a), k)
+        return o["advantages"], o["returns"], (o["logp"] if all(given) else None), o["valid"]
+
+    def _traj_state(self):
+        """What traj_stats keeps between calls, made at its first use: the per-lane carries, summary and the two running moment blocks."""
+        def make(zeros=torch.zeros, f32=torch.float32, f64=torch.float64):
+            return dict(carry_return=zeros(self.n, dtype=f32, device=self.device), carry_length=zeros(self.n, dtype=torch.int32, device=self.device),
+                        carry_disc=zeros(self.n, dtype=f32, device=self.device), summary=zeros(8, dtype=f64, device=self.device),
+                        obs_moments=zeros(1 + 2 * self.obs_dim, dtype=f64, device=self.device), ret_moments=zeros(3, dtype=f64, device=self.device), k=0)
+        return self._ts or self._lazy("_ts", make)
+
+    @property
+    def obs_moments(self):
+        """[1 + 2 D] float64 (count, mean[D], M2[D]): the running moments of the observation columns (traj_stats with obs=)."""
+        return self._traj_state()["obs_moments"]
+
+    @property
+    def ret_moments(self):
+        """[3] float64 (count, mean, M2): the running moments of the discounted return G (traj_stats)."""
+        return self._traj_state()["ret_moments"]
+
+    def made_moments(self):
+        """(obs_moments, ret_moments) if traj_stats' state has been made, else None -- without making it: what a re-seeded env carries
+        over to its next engine."""
+        return None if self._ts is None else (self._ts["obs_moments"], self._ts["ret_moments"])
+
+    def reset_moments(self):
+        """Zero the running moments of traj_stats (the empty state). The carries of the open episodes stay."""
+        ts = self._traj_state()
+        ts["obs_moments"].zero_()
+        ts["ret_moments"].zero_()
+
+    def traj_stats(self, reward, terminated, truncated, gamma: float = 0.99, episode_start=None, obs=None, store_steps: bool = True):
+        """pf_traj_stats: the return and length of every episode that finished inside a trajectory, and the running moments of a
+        reward and an observation normaliser (include/pyflyt_amd.h has the semantics). reward / terminated / truncated [k, n] as a
+        rollout wrote them; episode_start [n]: NEXT_STEP only, as for gae(); obs [k, n, D]: the observations the policy saw (collect's
+        obs), or None for no observation moments; store_steps=False skips the two per-step outputs. The engine owns the per-lane
+        carries (a trajectory may be split over calls; env_reset zeroes the lanes it resets), summary and the running moments
+        (self.obs_moments, self.ret_moments; reset_moments() empties them). The carries describe the lanes' open episodes only if
+        EVERY env step since the last reset goes through traj_stats, in order: steps taken by env_step, rollout or a collect without
+        stats in between are not seen, and the next finished episode's return and length would miss them -- reset the lanes (or
+        zero the carries) before mixing the two. Returns (episode_return [k, n], episode_length [k, n]
+        int32 -- both None without store_steps --, summary [8] float64): overwritten by the next call with the same k."""
+        k = self._traj_args(reward, terminated, truncated)
+        K.unit_interval(gamma, "gamma")
+        self._episode_start(episode_start)
+        if obs is not None:
+            K.tensor(self.device, obs, "obs", (k, self.n, self.obs_dim), required=f"{{name}} must be a float32 tensor of shape (k, {self.n}, D)")
+        ts = self._traj_state()
+        if store_steps and ts["k"] != k:
+            ts.update(k=k, episode_return=torch.empty(k, self.n, dtype=torch.float32, device=self.device),
+                      episode_length=torch.empty(k, self.n, dtype=torch.int32, device=self.device))
+        a = L.PfTrajStats()
+        a.gamma = float(gamma)
+        a.reward, a.terminated, a.truncated, a.episode_start = _ptr(reward), _ptr(terminated), _ptr(truncated), _ptr(episode_start)
+        a.obs, a.obs_moments = _ptr(obs), (_ptr(ts["obs_moments"]) if obs is not None else None)
+        a.carry_return, a.carry_length, a.carry_disc = _ptr(ts["carry_return"]), _ptr(ts["carry_length"]), _ptr(ts["carry_disc"])
+        a.ep_return_out = _ptr(ts["episode_return"]) if store_steps else None
+        a.ep_length_out = _ptr(ts["episode_length"]) if store_steps else None
+        a.summary, a.ret_moments = _ptr(ts["summary"]), _ptr(ts["ret_moments"])
+        self._launch(self.lib.pf_traj_stats, C.byref(a), k)
+        return (ts["episode_return"] if store_steps else None), (ts["episode_length"] if store_steps else None), ts["summary"]
+
+    # ------------------------------------------------------------------ the loss
+    def ppo_loss(self, mean, log_std, value, actions, logp_old, advantages, returns, valid=None, clip: float = 0.2, vf_coef: float = 0.5,
+                 ent_coef: float = 0.0, normalize_advantage: bool = True):
+        """pf_ppo_loss: the clipped PPO objective of a diagonal-Gaussian policy, its statistics and its gradients with respect to
+        mean, value and log_std (include/pyflyt_amd.h has the semantics). mean, actions [..., A] of one shape, A in 1..8; value,
+        logp_old, advantages, returns [...] (a trailing axis of 1 is accepted: a critic's output); valid [...] bool / uint8 or None
+        (every row valid); all flattened to M = the product of the leading axes, which need not be k n: a gathered minibatch is a
+        valid input. Returns (grad_mean [M, A], grad_value [M], grad_log_std [A], stats [16] float64): tensors the engine owns,
+        overwritten by the next call with the same M and A (stats and grad_log_std by every call)."""
+        K.ranked(mean, "mean", "{name} must be a float32 tensor of shape (..., A)")
+        A = int(mean.shape[-1])
+        if not 1 <= A <= 8:
+            raise ValueError(f"mean's last axis (the action width) must be in 1..8, got {A}")
+        lead, M = tuple(mean.shape[:-1]), mean.numel() // A
+        if M < 1:
+            raise ValueError(f"mean must hold at least one row, got shape {tuple(mean.shape)}")
+        f32, rows, full = (torch.float32,), (lead, lead + (1,)), (tuple(mean.shape),)  # (this call names its dtypes as torch spells them)
+        for name, x, shapes, dtypes in (("mean", mean, full, f32), ("actions", actions, full, f32), ("log_std", log_std, ((A,),), f32),
+                                        ("value", value, rows, f32), ("logp_old", logp_old, rows, f32), ("advantages", advantages, rows, f32),
+                                        ("returns", returns, rows, f32), ("valid", valid, rows, K.FLAGS)):
+            if name != "valid" or x is not None:
+                K.tensor(self.device, x, name, shapes, dtypes, required="{name} is required: a tensor of shape {shape}")
+        for name, x in (("clip", clip), ("vf_coef", vf_coef), ("ent_coef", ent_coef)):
+            K.number(x, name)
+        K.boolean(normalize_advantage, "normalize_advantage")
+        K.positive(clip, "clip")
+        K.non_negative(vf_coef, "vf_coef")
+        K.non_negative(ent_coef, "ent_coef")
+        o = self._lazy("_ppo_out", lambda: dict(M=0, A=0, stats=torch.zeros(16, dtype=torch.float64, device=self.device), calls=0))
+        if o["M"] != M or o["A"] != A:
+            kw = dict(dtype=torch.float32, device=self.device)
+            o.update(M=M, A=A, grad_mean=torch.empty(M, A, **kw), grad_value=torch.empty(M, **kw), grad_log_std=torch.empty(A, **kw))
+        o["calls"] += 1  # (pyflyt_amd.ppo_loss's backward checks that its gradients are still the ones this call wrote)
+        a = L.PfPpoLoss()
+        a.clip, a.vf_coef, a.ent_coef, a.normalize_advantage = float(clip), float(vf_coef), float(ent_coef), int(normalize_advantage)
+        a.mean, a.log_std, a.actions, a.logp_old = _ptr(mean), _ptr(log_std), _ptr(actions), _ptr(logp_old)
+        a.advantages, a.returns, a.value, a.valid = _ptr(advantages), _ptr(returns), _ptr(value), _ptr(valid)
+        a.grad_mean, a.grad_value, a.grad_log_std, a.stats = _ptr(o["grad_mean"]), _ptr(o["grad_value"]), _ptr(o["grad_log_std"]), _ptr(o["stats"])
+        self._launch(self.lib.pf_ppo_loss, C.byref(a), M, A)
+        return o["grad_mean"], o["grad_value"], o["grad_log_std"], o["stats"]
+
+    # ------------------------------------------------------------------ the networks
+    def _mlp_block(self, x, layers, activation):
+        """The pf_mlp block of `layers` [(weight, bias), ...] for the rows of x [..., in_dim], every tensor checked; returns
+        (block, rows, [(out, in), ...])."""
+        from .policy import _ACTIVATIONS, MAX_HIDDEN
+
+        if activation not in _ACTIVATIONS:
+            raise ValueError(f"activation must be 'tanh' or 'relu', got {activation!r}")
+        layers = [tuple(l) for l in layers]
+        if len(layers) not in (2, 3):
+            raise ValueError(f"layers: 2 or 3 (weight, bias) pairs (1 or 2 hidden layers), got {len(layers)}")
+        K.ranked(x, "x", "{name} must be a float32 tensor of shape (..., in_dim)")
+        dims = []
+        for l, (w, b) in enumerate(layers):
+            K.ranked(w, f"layers[{l}].weight", "{name} must be a float32 tensor of shape (out, in)", 2)
+            n_out, n_in = int(w.shape[0]), int(w.shape[1])
+            want_in = int(x.shape[-1]) if l == 0 else dims[-1][0]
+            K.tensor(self.device, w, f"layers[{l}].weight", (n_out, want_in))
+            K.tensor(self.device, b, f"layers[{l}].bias", (n_out,), required=K.NO_F32)
+            if l + 1 < len(layers) and not 1 <= n_out <= MAX_HIDDEN:
+                raise ValueError(f"layers[{l}].weight: hidden width {n_out} is outside 1..{MAX_HIDDEN} (PF_POLICY_MAX_HIDDEN)")
+            dims.append((n_out, n_in))
+        in_dim, out_dim = dims[0][1], dims[-1][0]
+        if not 1 <= in_dim <= 128:
+            raise ValueError(f"x's last axis (in_dim) must be in 1..128, got {in_dim}")
+        if not 1 <= out_dim <= 8:
+            raise ValueError(f"the last layer's width (out_dim) must be in 1..8, got {out_dim}")
+        K.tensor(self.device, x, "x", tuple(x.shape))
+        rows = x.numel() // in_dim
+        if rows < 1:
+            raise ValueError(f"x must hold at least one row, got shape {tuple(x.shape)}")
+        q = L.PfMlp()
+        q.n_layers, q.activation, q.in_dim, q.out_dim = len(layers), _ACTIVATIONS[activation], in_dim, out_dim
+        for l in range(2):
+            q.width[l] = dims[l][0] if l + 1 < len(layers) else 0
+        for l in range(3):
+            q.w[l] = layers[l][0].data_ptr() if l < len(layers) else None
+            q.b[l] = layers[l][1].data_ptr() if l < len(layers) else None
+        return q, rows, dims
+
+    def mlp_forward(self, x, layers, activation="tanh", out=None):
+        """pf_mlp_forward: the MLP `layers` [(weight, bias), ...] (torch.nn.Linear's layout; 2 or 3 of them, hidden widths 1..64, the
+        last 1..8 wide) on the rows of x [..., in_dim], in_dim 1..128, with policy_act's arithmetic bit for bit. Any engine. Returns
+        `out` [rows, out_dim]; without `out`, a tensor the engine owns, overwritten by the next call of the same shape."""
+        q, rows, dims = self._mlp_block(x, layers, activation)
+        out_dim = dims[-1][0]
+        if out is None:
+            cache = self._lazy("_mlp_fwd", dict)
+            out = cache.get((rows, out_dim))
+            if out is None:
+                out = cache[(rows, out_dim)] = torch.empty(rows, out_dim, dtype=torch.float32, device=self.device)
+        else:
+            K.tensor(self.device, out, "out", (rows, out_dim), required=K.NO_F32)
+        self._launch(self.lib.pf_mlp_forward, C.byref(q), _ptr(x), rows, _ptr(out))
+        return out
+
+    def mlp_backward(self, x, grad_out, layers, activation="tanh"):
+        """pf_mlp_backward: [(grad_weight, grad_bias), ...] of the MLP `layers` on the rows of x [..., in_dim] under the
+        output-gradients grad_out [rows, out_dim] (a [rows] tensor is accepted for out_dim 1). The hidden activations are computed
+        again from x; x gets no gradient. The gradients and the workspace are tensors the engine owns, reused by the next call with
+        the same rows and layer shapes. Deterministic: the same call gives the same bits on any stream."""
+        q, rows, dims = self._mlp_block(x, layers, activation)
+        out_dim = dims[-1][0]
+        K.tensor(self.device, grad_out, "grad_out", ((rows, out_dim), (rows,)) if out_dim == 1 else (rows, out_dim), required=K.NO_F32)
+        cache = self._lazy("_mlp_bwd", dict)
+        key = (rows, tuple(dims))
+        o = cache.get(key)
+        if o is None:
+            kw = dict(dtype=torch.float32, device=self.device)
+            nbytes = int(self.lib.pf_mlp_backward_workspace_bytes(C.byref(q), rows))
+            if nbytes < 1:
+                raise L.PyFlytAmdError("pf_mlp_backward_workspace_bytes refused the network's shape")
+            grads = [(torch.empty(n_out, n_in, **kw), torch.empty(n_out, **kw)) for n_out, n_in in dims]
+            gw, gb = (C.c_void_p * 3)(), (C.c_void_p * 3)()
+            for l, (w, b) in enumerate(grads):
+                gw[l], gb[l] = w.data_ptr(), b.data_ptr()
+            o = cache[key] = dict(grads=grads, gw=gw, gb=gb, bytes=nbytes, workspace=torch.empty((nbytes + 3) // 4, **kw))
+        self._launch(self.lib.pf_mlp_backward, C.byref(q), _ptr(x), _ptr(grad_out), rows, o["gw"], o["gb"], _ptr(o["workspace"]), o["bytes"])
+        return o["grads"]
+
+    # ------------------------------------------------------------------ the optimiser
+    def adam_step(self, params, grads, exp_avg, exp_avg_sq, state, *, lr=3e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
+                  max_grad_norm=None, skip_nonfinite: bool = False):
+        """pf_adam_step: one Adam / AdamW step with global gradient-norm clipping over the tensors `params` (1..32 of them), in
+        place, in two launches (include/pyflyt_amd.h has the semantics). grads, exp_avg and exp_avg_sq are lists of tensors shaped
+        like the parameters; state is the [8] float64 block (steps, norm, clip coefficient, learning rate, skipped calls), read
+        and overwritten. lr is a Python number or a one-element float32 device tensor, read by the kernel at every call.
+        max_grad_norm None = no clipping. The hyperparameters reach the kernel as float32. The workspace (one per total size) and
+        the filled argument block (one per set of addresses) are the engine's. Returns `state`; nothing synchronises."""
+        lists = dict(params=params, grads=grads, exp_avg=exp_avg, exp_avg_sq=exp_avg_sq)
+        for name, ts in lists.items():
+            if not isinstance(ts, (list, tuple)):
+                raise ValueError(f"{name} must be a list of tensors, got {type(ts).__name__}")
+        n = len(params)
+        if not 1 <= n <= L.PF_ADAM_MAX_TENSORS:
+            raise ValueError(f"params: 1..{L.PF_ADAM_MAX_TENSORS} tensors (PF_ADAM_MAX_TENSORS), got {n}")
+        for name, ts in lists.items():
+            if len(ts) != n:
+                raise ValueError(f"{name} must hold one tensor per parameter ({n}), got {len(ts)}")
+        lr_dev = lr if torch.is_tensor(lr) else None
+        for i, (p, g) in enumerate(zip(params, grads)):  # (the gradients are checked at every call: autograd makes new ones)
+            if not torch.is_tensor(p) or not torch.is_tensor(g):  # (one refusal names both: the shape asked of g is p's)
+                raise ValueError(f"params[{i}] and grads[{i}] must be tensors, got {type(p).__name__} and {type(g).__name__}")
+            K.tensor(self.device, g, f"grads[{i}]", tuple(p.shape))
+        key = tuple(t.data_ptr() for ts in lists.values() for t in ts) + (state.data_ptr() if torch.is_tensor(state) else None,
+                                                                          None if lr_dev is None else lr_dev.data_ptr())
+        cache = self._lazy("_adam", dict)
+        o = cache.get(key)
+        if o is None:
+            for i, p in enumerate(params):
+                K.tensor(self.device, p, f"params[{i}]", tuple(p.shape))
+                for name in ("exp_avg", "exp_avg_sq"):
+                    K.tensor(self.device, lists[name][i], f"{name}[{i}]", tuple(p.shape), required="{name} must be a tensor")
+                if p.numel() < 1:
+                    raise ValueError(f"params[{i}] must hold at least one element, got shape {tuple(p.shape)}")
+            K.tensor(self.device, state, "state", (8,), (torch.float64,), required="{name} must be a float64 tensor of shape {shape}")
+            if lr_dev is not None:
+                K.tensor(self.device, lr_dev, "lr", tuple(lr_dev.shape) if lr_dev.numel() == 1 else (1,))
+            total = sum(p.numel() for p in params)
+            nbytes = int(self.lib.pf_adam_workspace_bytes(total))
+            if nbytes < 1:
+                raise ValueError(f"params: the total number of elements must be below 2^31, got {total}")
+            spaces = self._lazy("_adam_ws", dict)
+            if total not in spaces:
+                spaces[total] = torch.empty(nbytes // 8, dtype=torch.float64, device=self.device)
+            a = L.PfAdam()
+            a.n_tensors, a.state, a.lr_dev = n, _ptr(state), _ptr(lr_dev)
+            for i in range(n):
+                a.numel[i] = params[i].numel()
+                a.param[i], a.grad[i] = params[i].data_ptr(), grads[i].data_ptr()
+                a.exp_avg[i], a.exp_avg_sq[i] = exp_avg[i].data_ptr(), exp_avg_sq[i].data_ptr()
+            # (the tensors ride along: an address in the key stays theirs for as long as the entry lives)
+            o = cache[key] = dict(args=a, ref=C.byref(a), workspace=_ptr(spaces[total]), bytes=nbytes, keep=(list(params), list(exp_avg), list(exp_avg_sq), state, lr_dev))
+            if len(cache) > 64:
+                cache.pop(next(iter(cache)))
+        K.number(eps, "eps")
+        K.number(weight_decay, "weight_decay")
+        if lr_dev is None:
+            K.number(lr, "lr", " or a one-element float32 device tensor")
+        if max_grad_norm is not None:
+            K.number(max_grad_norm, "max_grad_norm")
+        try:
+            b1, b2 = betas
+            b1, b2 = float(b1), float(b2)
+        except (TypeError, ValueError):
+            raise ValueError(f"betas must be a pair of numbers, got {betas!r}") from None
+        if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+            raise ValueError(f"betas must lie in [0, 1), got {betas!r}")
+        if lr_dev is None:
+            K.non_negative(lr, "lr")
+        K.positive(eps, "eps")
+        K.non_negative(weight_decay, "weight_decay")
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError(f"max_grad_norm must be > 0 or None (no clipping), got {max_grad_norm}")
+        K.boolean(skip_nonfinite, "skip_nonfinite")
+        a = o["args"]
+        a.lr, a.beta1, a.beta2, a.eps, a.weight_decay = (0.0 if lr_dev is not None else float(lr)), b1, b2, float(eps), float(weight_decay)
+        a.max_grad_norm, a.skip_nonfinite = (float("inf") if max_grad_norm is None else float(max_grad_norm)), int(skip_nonfinite)
+        with torch.cuda.device(self.device):  # (its own launch code: the raw stream handle, for the host cost of a step)
+            L.check(self.lib.pf_adam_step(self._ctx, o["ref"], o["workspace"], o["bytes"], C.c_void_p(_raw_stream(self._index))), self._ctx)
+        return state

@@ -7,10 +7,9 @@ import re
 import pytest
 import torch
 
+from bare_engine import bare_engine
 import pyflyt_amd
 from pyflyt_amd import _lib as L
-from pyflyt_amd import build_params
-from pyflyt_amd.engine import BatchEngine
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("pf_sizeof_adam", "pf_adam_workspace_bytes", "pf_adam_step")
@@ -69,13 +68,6 @@ def test_workspace_bytes_on_the_host():
         assert size(total) == top
     for total in (0, -1, -(1 << 40), 1 << 31, (1 << 31) + 5, 1 << 40):
         assert size(total) == 0
-
-
-def bare_engine():
-    """A BatchEngine without a context: what the Adam class checks before it reaches the library needs the device only."""
-    eng = object.__new__(BatchEngine)
-    eng.n, eng.device, eng.params, eng._ctx = 8, torch.device("cpu"), build_params("quadx", "hover"), None
-    return eng
 
 
 def test_class_refusals_name_the_parameter():

@@ -6,9 +6,9 @@ import re
 import pytest
 import torch
 
-from pyflyt_amd import MLPPolicy, build_params
+from bare_engine import bare_engine
+from pyflyt_amd import MLPPolicy
 from pyflyt_amd import _lib as L
-from pyflyt_amd.engine import BatchEngine
 from pyflyt_amd.gym_envs.vector_envs import QuadXHoverVecEnv
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -34,14 +34,6 @@ def test_sizeof_gae_matches_the_parsed_mirror():
     lib.pf_sizeof_gae.restype = C.c_size_t
     assert lib.pf_sizeof_gae() == C.sizeof(L.PfGae)
     assert hasattr(lib, "pf_gae")
-
-
-def bare_engine(autoreset="next_step"):
-    """A BatchEngine without a context: what gae() checks before it reaches the library needs the lane count, the device and the
-    parameters only."""
-    eng = object.__new__(BatchEngine)
-    eng.n, eng.device, eng.params, eng._ctx = N, torch.device("cpu"), build_params("quadx", "hover", autoreset=autoreset), None
-    return eng
 
 
 def good(autoreset="next_step"):

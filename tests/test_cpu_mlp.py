@@ -7,10 +7,9 @@ import re
 import pytest
 import torch
 
+from bare_engine import bare_engine
 import pyflyt_amd
 from pyflyt_amd import _lib as L
-from pyflyt_amd import build_params
-from pyflyt_amd.engine import BatchEngine
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("pf_sizeof_mlp", "pf_mlp_forward", "pf_mlp_backward_workspace_bytes", "pf_mlp_backward")
@@ -92,13 +91,6 @@ def test_workspace_bytes_on_the_host():
     assert lib.pf_mlp_backward_workspace_bytes(C.byref(bad), 100) == 0
     assert lib.pf_mlp_backward_workspace_bytes(C.byref(block()), 0) == 0
     assert lib.pf_mlp_backward_workspace_bytes(None, 100) == 0
-
-
-def bare_engine():
-    """A BatchEngine without a context: what the mlp calls check before they reach the library needs the device only."""
-    eng = object.__new__(BatchEngine)
-    eng.n, eng.device, eng.params, eng._ctx = 8, torch.device("cpu"), build_params("quadx", "hover"), None
-    return eng
 
 
 def layers(in_dim=5, hidden=(6, 7), out_dim=2):

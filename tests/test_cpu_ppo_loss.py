@@ -6,10 +6,9 @@ import re
 import pytest
 import torch
 
+from bare_engine import bare_engine
 import pyflyt_amd
 from pyflyt_amd import _lib as L
-from pyflyt_amd import build_params
-from pyflyt_amd.engine import BatchEngine
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 M, A = 12, 4
@@ -42,13 +41,6 @@ def test_the_package_exports_the_wrapper():
     d = pyflyt_amd.ppo_stats_dict(stats)
     assert d["valid_rows"] == 0 and d["loss"] == 1.0 and d["approx_kl"] == 5.0 and d["explained_variance"] == 9.0 and d["ratio_max"] == 11.0
     assert len(d) == 12
-
-
-def bare_engine():
-    """A BatchEngine without a context: what ppo_loss() checks before it reaches the library needs the device only."""
-    eng = object.__new__(BatchEngine)
-    eng.n, eng.device, eng.params, eng._ctx = 8, torch.device("cpu"), build_params("quadx", "hover"), None
-    return eng
 
 
 def good():

@@ -7,9 +7,9 @@ import re
 import pytest
 import torch
 
-from pyflyt_amd import MLPPolicy, RunningMoments, build_params
+from bare_engine import bare_engine
+from pyflyt_amd import MLPPolicy, RunningMoments
 from pyflyt_amd import _lib as L
-from pyflyt_amd.engine import BatchEngine
 from pyflyt_amd.gym_envs.vector_envs import QuadXHoverVecEnv
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -36,14 +36,6 @@ def test_sizeof_traj_stats_matches_the_parsed_mirror():
     lib.pf_sizeof_traj_stats.restype = C.c_size_t
     assert lib.pf_sizeof_traj_stats() == C.sizeof(L.PfTrajStats)
     assert hasattr(lib, "pf_traj_stats")
-
-
-def bare_engine(autoreset="next_step"):
-    """A BatchEngine without a context: what traj_stats() checks before it reaches the library needs the lane count, the observation
-    width, the device and the parameters only."""
-    eng = object.__new__(BatchEngine)
-    eng.n, eng.obs_dim, eng.device, eng.params, eng._ctx = N, D, torch.device("cpu"), build_params("quadx", "hover", autoreset=autoreset), None
-    return eng
 
 
 def good():
