@@ -1,6 +1,7 @@
 """Writes profiles/r07/pmc_summary.json and profiles/pmc_latest.json (what bench.py replays as roofline.traffic / roofline.issue,
 keyed by the source hash of the kernels the counters were collected on) from SRC/pmc_<vehicle>_<task>_<FETCH_SIZE |
-WRITE_SIZE | sq>/ (usage: summarize_profiles_r07.py SRC, the directory the collection wrote) -- the counter passes of
+WRITE_SIZE | sq>/ (usage: summarize_profiles_r07.py SRC [NAME]: the directory the collection wrote, and the directory under profiles/ for the
+summary, r07 unless given) -- the counter passes of
 profiles/tools/collect_profiles_r06.sh, each in a run of its own without a tracing flag.
 The first ten launches of a run are dropped (prof_cfg.py's pf_env_reset among them: with the fixed call shape it is another
 instantiation than the steps)."""
@@ -13,7 +14,8 @@ import sys
 
 R = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, R)
-src, dst = os.path.abspath(sys.argv[1]), os.path.join(R, "profiles", "r07")
+name = sys.argv[2] if len(sys.argv) > 2 else "r07"  # (the directory under profiles/ the summary goes to)
+src, dst = os.path.abspath(sys.argv[1]), os.path.join(R, "profiles", name)
 os.makedirs(dst, exist_ok=True)
 
 
@@ -56,6 +58,6 @@ if len(latest) == 3:
     json.dump(summary, open(os.path.join(dst, "pmc_summary.json"), "w"), indent=1)
     import bench  # noqa: E402
 
-    json.dump({"source_hash": bench.source_hash(), "source": "profiles/r07/pmc_summary.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE / SQ_*, separate passes, FETCH doubled per guide)",
+    json.dump({"source_hash": bench.source_hash(), "source": f"profiles/{name}/pmc_summary.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE / SQ_*, separate passes, FETCH doubled per guide)",
                "envs": latest}, open(os.path.join(R, "profiles", "pmc_latest.json"), "w"), indent=1)
 print(json.dumps(latest, indent=1))

@@ -1363,6 +1363,10 @@ __global__ void __launch_bounds__(64 * kQuadWPB, SHARED ? 1 : WPS) quadx_m0_env_
   constexpr bool CALM = CR && !SHARED && !MODES && NOISE != PF_NOISE_INJECT;
   QuadKV KV{};
   if (CALM) KV = quadkv_from(K);
+  // PKREW: roll and pitch of Hover's dense reward as one packed chain (uav_device.hpp: fast_atan2_x2), its coefficients in ten of the
+  // registers the one-wave-per-SIMD budget leaves free (the fixed Hover kernel uses 270 of 512)
+  constexpr bool PKREW = FIXED && WPS == 1 && TASK == PF_TASK_HOVER;
+  Atan2C AC{};  // (dead unless PKREW)
   float tgt[4][3];
   float new_dist, old_dist;
   int step_count, flags, n_left;
@@ -1408,6 +1412,15 @@ __global__ void __launch_bounds__(64 * kQuadWPB, SHARED ? 1 : WPS) quadx_m0_env_
       cm0 = Sin[7 * N + li]; cm1 = Sin[8 * N + li]; cm2 = Sin[9 * N + li]; cm3 = Sin[10 * N + li]; cm4 = Sin[11 * N + li];
       if (DSTATE) { cm5 = Sin[22 * N + li]; cm6 = Sin[23 * N + li]; cm7 = Sin[24 * N + li]; cm8 = Sin[25 * N + li]; cm9 = Sin[26 * N + li]; }
     }
+    // PHX: the half of the step's Philox call that depends on the seed and the lane alone -- four quarter-rate multiplies -- in front
+    // of the wait for the int group, which brings the event counter the rest needs (uav_device.hpp: philox4x32_pre / _post)
+    constexpr bool PHX = FIXED && WPS == 1 && NOISE == PF_NOISE_PHILOX;
+    PhiloxPre zpre{};  // (dead unless PHX)
+    if constexpr (PHX) {
+      zpre = philox4x32_pre(K.seed_hi, (uint32_t)(lane0 + li));
+      asm volatile("" : "+v"(zpre.lo0), "+v"(zpre.hi1), "+v"(zpre.lo1));  // (computed HERE: left alone, the compiler sinks the products to the call's place behind the resets)
+    }
+    if constexpr (PKREW) AC = atan2_consts();  // (ten register writes between the state loads' issue and their first wait)
     if (CR && blockIdx.x < kRareTextPrefetchBlocks) rare_text_prefetch(tid);  // (behind the state loads: one wait for both)
     rng_ctr = (uint32_t)__float_as_int(gi.z);
     PF_STAMP(1);  // (the int group has arrived)
@@ -1450,7 +1463,8 @@ __global__ void __launch_bounds__(64 * kQuadWPB, SHARED ? 1 : WPS) quadx_m0_env_
       }
     }
     if (NOISE == PF_NOISE_PHILOX) {
-      if (op == OP_STEP) zn = normal8(philox4x32(K.seed_lo, K.seed_hi, (uint32_t)(lane0 + li), rng_ctr, 0u, 0u));
+      if constexpr (PHX) zn = normal8(philox4x32_post(K.seed_lo, K.seed_hi, zpre, rng_ctr));
+      else if (op == OP_STEP) zn = normal8(philox4x32(K.seed_lo, K.seed_hi, (uint32_t)(lane0 + li), rng_ctr, 0u, 0u));
     }
     PF_STAMP(2);  // (the step's Philox call done)
     V.p = v3{g0.x, g0.y, g0.z}; new_dist = g0.w;
@@ -1506,6 +1520,28 @@ __global__ void __launch_bounds__(64 * kQuadWPB, SHARED ? 1 : WPS) quadx_m0_env_
   };
   V.contact_now = (flags & PF_F_CONTACT) != 0;
   V.contact_step = false;
+  // SEL (the fixed call shape sized for one wave per SIMD): a lane that restarts from a valid spare -- the common restart, one lane in
+  // thirty per step, so nearly every wave has one -- takes what reset_lane(true, ..) gives it by selects: its pose, velocities, motor
+  // states and zeroed memories HERE, in front of the one derive() every wave runs (the same function of the same inputs as the second
+  // derive() of the divergent block this replaces), its counters and key word where the resets stand (below). The lanes without a
+  // valid spare keep the cooperative path.
+  // (Hover only: in Waypoints, with the spare's twelve target words and the first distance selected the same way, the launch went from
+  //  15.21 to 15.84 us at 65 536 lanes -- profiles/straight_step/ab_same_box.txt)
+  constexpr bool SEL = FIXED && SPARE && WPS == 1 && TASK == PF_TASK_HOVER;
+  bool sel = false;
+  if constexpr (SEL) {
+    sel = valid && (flags & (PF_F_TERMINATED | PF_F_TRUNCATED)) != 0 && (rkw & kSpareValid) != 0u;
+    V.p = v3{sel ? K.start_pos[0] : V.p.x, sel ? K.start_pos[1] : V.p.y, sel ? spv.z : V.p.z};
+    V.q = quat{sel ? K.start_quat[0] : V.q.x, sel ? K.start_quat[1] : V.q.y, sel ? K.start_quat[2] : V.q.z, sel ? K.start_quat[3] : V.q.w};
+    V.wvx = f2{sel ? 0.0f : V.wvx.x, sel ? 0.0f : V.wvx.y};
+    V.wvy = f2{sel ? 0.0f : V.wvy.x, sel ? 0.0f : V.wvy.y};
+    V.wvz = f2{sel ? 0.0f : V.wvz.x, sel ? spv.vz : V.wvz.y};
+    V.t01 = f2{sel ? spv.thr : V.t01.x, sel ? spv.thr : V.t01.y};
+    V.t23 = f2{sel ? spv.thr : V.t23.x, sel ? spv.thr : V.t23.y};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { V.I[k] = sel ? 0.0f : V.I[k]; V.E[k] = sel ? 0.0f : V.E[k]; }
+    V.contact_now = V.contact_now && !sel;
+  }
   V.derive();
 #ifdef PF_PHASE_TRACE
   asm volatile("" ::"v"(V.wb.x), "v"(V.vb.z));
@@ -1872,7 +1908,7 @@ __global__ void __launch_bounds__(64 * kQuadWPB, SHARED ? 1 : WPS) quadx_m0_env_
   };
   // A wave's resets: the lanes with a valid spare copy it, the others generate (cooperatively) from their key. Wave-uniform call.
   auto do_resets = [&](const bool r) {
-    const bool have = SPARE && r && (rkw & kSpareValid) != 0u;
+    const bool have = SPARE && !SEL && r && (rkw & kSpareValid) != 0u;  // (SEL: the lanes with a valid spare have restarted by selects and are not in r)
     reset_key_now = REKEY ? (rkw & ~kSpareValid) : rng_ctr;
     prepare_reset_draws(r && !have, reset_key_now);
     // (MODES: behind a wave-uniform guard -- the fp64 state a reset writes otherwise meets the flying lanes' at this block's join, and
@@ -2003,7 +2039,17 @@ __global__ void __launch_bounds__(64 * kQuadWPB, SHARED ? 1 : WPS) quadx_m0_env_
   act0 = act1 = act2 = act3 = 0.f;
   reward = 0.0f;
   was_reset = false;
-  do_resets(do_reset);
+  if constexpr (SEL) {
+    // (see SEL above) what reset_lane(true, ..) leaves besides the flight state: the episode's counters and flags, the event counter
+    // advanced, the next reset's key word without a spare
+    step_count = sel ? 0 : step_count; flags = sel ? 0 : flags;
+    term = term && !sel; trunc = trunc && !sel;
+    rng_ctr += sel ? 1u : 0u;
+    rkw = sel ? (rng_ctr & ~kSpareValid) : rkw;
+    sp_dirty = sp_dirty || sel;
+    was_reset = sel;
+  }
+  do_resets(SEL ? (do_reset && !sel) : do_reset);
   // (the counter word is first needed HERE, behind the resets: read where the loop starts, its wait sat in front of them -- the load is
   //  the last of the prologue's, and a lone wave of a 4 096-lane batch waited 0.45 us for it. The same word in every lane: made
   //  wave-uniform for the control flow below)
@@ -2080,8 +2126,12 @@ __global__ void __launch_bounds__(64 * kQuadWPB, SHARED ? 1 : WPS) quadx_m0_env_
     if (!calm && tid == 0) trace_add(&g_calm_trace[0], 1ull);  // waves that keep the call site this step (rare: no contention)
 #endif
   }
-  for (int s = 0; s < k_step_ratio; ++s) {
-    if (!__any(go)) break;
+  // One Aviary step of the env step (control, two ticks, the task's logic and reward) for the lanes still going. `s_c`: the step's index,
+  // `calm_c`: the wave's calm verdict -- each a run-time value or a std::integral_constant, so that the one body below serves the
+  // run-time loop and, with both constant, the straight-line calm path of the fixed call shape (behind this lambda).
+  auto aviary_step = [&](const auto s_c, const auto calm_c) __attribute__((always_inline)) {
+    const int s = s_c;
+    const bool calm = calm_c;
     // a wave that is not calm over the whole env step (some lane is low) still is over most of its Aviary steps: the same bound
     // over the two ticks ahead (a lane sinks a few millimetres in them) -- evaluated in those waves only
     bool calm_s = calm;
@@ -2169,8 +2219,15 @@ __global__ void __launch_bounds__(64 * kQuadWPB, SHARED ? 1 : WPS) quadx_m0_env_
           //  w^2 - x^2 - y^2 + z^2 = R22)
           float sarg = -V.R.m20;
           bool gim = __builtin_fabsf(sarg) >= 0.99999f;
-          float roll = gim ? 0.0f : fast_atan2(V.R.m21, V.R.m22);
-          float pitch = gim ? __builtin_copysignf(0.5f * kPi, sarg) : fast_asin(sarg);
+          float roll, pitch;
+          if constexpr (PKREW) {  // (atan2(R21, R22), asin(sarg) = atan2(sarg, sqrt((1 - sarg)(1 + sarg)))) as a pair, one gimbal select each
+            const f2 rp = fast_atan2_x2(f2{V.R.m21, sarg}, f2{V.R.m22, fsqrt(__builtin_fmaxf((1.0f - sarg) * (1.0f + sarg), 0.0f))}, AC);
+            roll = gim ? 0.0f : rp.x;
+            pitch = gim ? __builtin_copysignf(0.5f * kPi, sarg) : rp.y;
+          } else {
+            roll = gim ? 0.0f : fast_atan2(V.R.m21, V.R.m22);
+            pitch = gim ? __builtin_copysignf(0.5f * kPi, sarg) : fast_asin(sarg);
+          }
           float ang = fsqrt(fmaf(roll, roll, pitch * pitch));
           reward = fmaf(-0.01f * V.wb.z, V.wb.z, reward);
           reward -= lin + ang;
@@ -2190,6 +2247,34 @@ __global__ void __launch_bounds__(64 * kQuadWPB, SHARED ? 1 : WPS) quadx_m0_env_
         }
       }
       if (TASK != PF_TASK_MA_HOVER) go = !(term || trunc);
+    }
+  };
+  // FIXED, a calm wave: the trip count is a constant and no lane can meet the floor, so the Aviary steps are straight-line code -- no
+  // counter, no exit mask, no back-edge copies, `go` stays a lane mask, pick8 reads a register, and the calm bound over two ticks and
+  // the ticks with the floor code are not in it. Every other wave and instantiation: the run-time loop, which holds the floor code once.
+  // (the one-wave-per-SIMD budget only: under two waves' 256 registers the second copy of the steps added 16 B of scratch to Hover's.
+  //  Hover only: four straight Waypoints steps, whose calm ticks keep the floor detection, measured 15.33 us against the loop's 15.21)
+  constexpr bool STRAIGHT = FIXED && CALM && WPS == 1 && TASK == PF_TASK_HOVER;
+  if (STRAIGHT && calm) {
+    if constexpr (STRAIGHT) {
+      typedef std::integral_constant<bool, true> calm_t;
+      do {
+        if (!__any(go)) break;
+        aviary_step(std::integral_constant<int, 0>{}, calm_t{});
+        if (!__any(go)) break;
+        aviary_step(std::integral_constant<int, 1>{}, calm_t{});
+        if (!__any(go)) break;
+        aviary_step(std::integral_constant<int, 2>{}, calm_t{});
+        if constexpr (kQuadFixedRatio<TASK> == 4) {
+          if (!__any(go)) break;
+          aviary_step(std::integral_constant<int, 3>{}, calm_t{});
+        }
+      } while (false);
+    }
+  } else {
+    for (int s = 0; s < k_step_ratio; ++s) {
+      if (!__any(go)) break;
+      aviary_step(s, calm);
     }
   }
   PF_STAMP(5);  // (the env step's Aviary steps done)

@@ -118,6 +118,44 @@ PF_DEV float fast_atan2(float y, float x) {
 PF_DEV float fast_asin(float x) {  // asin(x) = atan2(x, sqrt((1-x)(1+x)))
   return fast_atan2(x, fsqrt(__builtin_fmaxf((1.0f - x) * (1.0f + x), 0.0f)));
 }
+// Two fast_atan2 of the same shape as one chain: the same operations in the same order per element, the products and the Horner
+// steps packed (each element rounds as the scalar instruction does, so both results equal fast_atan2's bit for bit). A packed
+// instruction takes no literal, so the coefficients come from vector registers the kernel sets up once (atan2_consts: a scalar
+// Horner step with its literal is an 8-byte encoding, five clocks of a lone wave instead of four).
+struct Atan2C {
+  float c[8];  // highest degree first; the ninth, 1.0f, is an inline constant
+  float half_pi, pi;
+};
+PF_DEV Atan2C atan2_consts() {
+  Atan2C k{{0.0029035410843789577f, -0.016282962635159492f, 0.04303929582238197f, -0.07533670216798782f, 0.10654674470424652f,
+            -0.14207133650779724f, 0.19993053376674652f, -0.3333309292793274f}, 0.5f * kPi, kPi};
+#pragma unroll
+  for (int i = 0; i < 8; ++i) asm volatile("" : "+v"(k.c[i]));  // (opaque: held in registers, not rematerialised as literals)
+  asm volatile("" : "+v"(k.half_pi), "+v"(k.pi));
+  return k;
+}
+PF_DEV f2 fast_atan2_x2(f2 y, f2 x, const Atan2C& k) {
+  const float ax0 = __builtin_fabsf(x.x), ay0 = __builtin_fabsf(y.x), ax1 = __builtin_fabsf(x.y), ay1 = __builtin_fabsf(y.y);
+  const float mx0 = __builtin_fmaxf(ax0, ay0), mn0 = __builtin_fminf(ax0, ay0);
+  const float mx1 = __builtin_fmaxf(ax1, ay1), mn1 = __builtin_fminf(ax1, ay1);
+  f2 t = f2{mn0, mn1} * f2{frcp(mx0), frcp(mx1)};
+  t = f2{(mx0 == 0.0f) ? 0.0f : t.x, (mx1 == 0.0f) ? 0.0f : t.y};
+  const f2 s = t * t;
+  f2 p = fma2(s, sp2(k.c[0]), sp2(k.c[1]));
+  p = fma2(s, p, sp2(k.c[2]));
+  p = fma2(s, p, sp2(k.c[3]));
+  p = fma2(s, p, sp2(k.c[4]));
+  p = fma2(s, p, sp2(k.c[5]));
+  p = fma2(s, p, sp2(k.c[6]));
+  p = fma2(s, p, sp2(k.c[7]));
+  p = fma2(s, p, sp2(1.0f));
+  f2 r = p * t;
+  const f2 h = sp2(k.half_pi) - r;
+  r = f2{(ay0 > ax0) ? h.x : r.x, (ay1 > ax1) ? h.y : r.y};
+  const f2 g = sp2(k.pi) - r;
+  r = f2{(x.x < 0.0f) ? g.x : r.x, (x.y < 0.0f) ? g.y : r.y};
+  return f2{__builtin_copysignf(r.x, y.x), __builtin_copysignf(r.y, y.y)};
+}
 // getQuaternionFromEuler's product (x, y, z, w) from the half-angle cosines / sines, shared factors hoisted
 PF_DEV quat quat_from_half_angles(float cr, float sr, float cp, float sp, float cy, float sy) {
   const float a = sr * cp, b = cr * sp, c = cr * cp, d = sr * sp;
@@ -328,6 +366,34 @@ PF_DEV u32x4 philox4x32(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint
     k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
   }
   return u32x4{c0, c1, c2, c3};
+}
+// philox4x32(k0, k1, c0, c1, 0, 0) split where its inputs arrive: philox4x32_post(k0, k1, philox4x32_pre(k1, c0), c1) returns the same
+// words. With counter words (c0, c1, 0, 0) round 1 multiplies c0 and zero, and the word its high product becomes, hi(M0 c0) ^ k1, is
+// one of the two round 2 multiplies: those four products depend on the key and c0 alone (an env step: the seed and the lane) and can
+// be taken while c1 (the lane's event counter) is still on its way from memory. The round function is philox4x32's.
+struct PhiloxPre {
+  uint32_t lo0, hi1, lo1;  // round 1: lo(M0 c0); round 2: hi / lo(M1 (hi(M0 c0) ^ k1))
+};
+PF_DEV PhiloxPre philox4x32_pre(uint32_t k1, uint32_t c0) {
+  const uint32_t c2 = __umulhi(0xD2511F53u, c0) ^ k1;
+  return PhiloxPre{0xD2511F53u * c0, __umulhi(0xCD9E8D57u, c2), 0xCD9E8D57u * c2};
+}
+PF_DEV u32x4 philox4x32_post(uint32_t k0, uint32_t k1, PhiloxPre h, uint32_t c1) {
+  static_assert(PF_PHILOX_ROUNDS >= 2, "the split takes the first two rounds apart");
+  const uint32_t a = c1 ^ k0;  // round 1: c0 <- hi(M1 0) ^ c1 ^ k0, c1 <- lo(M1 0) = 0, c2 <- hi(M0 c0) ^ 0 ^ k1, c3 <- lo(M0 c0)
+  k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  const uint32_t hi0 = __umulhi(0xD2511F53u, a), lo0 = 0xD2511F53u * a;  // round 2
+  uint32_t c0 = h.hi1 ^ k0, c1n = h.lo1, c2 = hi0 ^ h.lo0 ^ k1, c3 = lo0;
+  k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+#pragma unroll
+  for (int r = 2; r < PF_PHILOX_ROUNDS; ++r) {
+    uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+    uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+    uint32_t n0 = h1 ^ c1n ^ k0, n2 = h0 ^ c3 ^ k1;
+    c0 = n0; c1n = l1; c2 = n2; c3 = l0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  return u32x4{c0, c1n, c2, c3};
 }
 // 23-bit uniform in (0,1), exact in fp32
 PF_DEV float u01(uint32_t x) { return ((float)(x >> 9) + 0.5f) * (1.0f / 8388608.0f); }
