@@ -733,6 +733,47 @@ size_t pf_sizeof_adam(void);
 size_t pf_adam_workspace_bytes(int64_t total_numel);
 int pf_adam_step(pf_ctx* ctx, const pf_adam_args* a, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The world-level auto-reset of the multi-agent envs (PF_TASK_DOGFIGHT, PF_TASK_MA_HOVER), which exist with auto-reset OFF only: run
+ * between two env steps, it tells which lanes of the step just taken were real transitions, blanks the rows of the agents that had
+ * finished before it, keeps the per-lane latch "this agent's episode has ended and its world has not been reset yet", and names
+ * the worlds to reset -- NEXT_STEP's contract one level up, where the unit that is reset is the world and not the lane. (Added
+ * without a new PF_ABI_VERSION: a new function, every existing struct as it was.) Worlds are groups of A = agents_per_world adjacent
+ * lanes, lane = world * A + agent. Below, for lane i of world w:
+ *   - was = done[i] != 0; waiting = every lane of w has done != 0 -- both as the latch was when the call began.
+ *   - VALID. valid_out[i] = !was && !(exclude && exclude[i]): a lane whose agent had finished flies on with zero commands and is no
+ *     transition; `exclude` takes lanes out for good (an opponent's, whose actions come from a policy that is not being trained).
+ *   - ROWS. Where was: reward[i] = +0.0f, terminated[i] = truncated[i] = 0; every other lane's entries stay as pf_env_step wrote them.
+ *   - LATCH. ended = !was && (terminated[i] | truncated[i]); done[i] = waiting ? 0 : (was | ended).
+ *   - RESET MASK. reset_out[i] = waiting: whole worlds, every lane of them.
+ *   - SELECTS. Every `?` and `where` above is a selection: a NaN in the reward of a latched lane reaches nothing.
+ *   - CONSEQUENCE. A world whose every agent had finished before this step spends the step as its reset step: all its lanes are
+ *     invalid, the mask names the world, its latch is cleared. The caller then runs pf_env_reset(mask = reset_out) with b->obs
+ *     pointing at THIS step's observation row: the reset observation replaces what the wasted step wrote, the terminal observation
+ *     of the last agent to finish stays in the previous row, and a truncated agent bootstraps from that row under pf_gae's OFF rule
+ *     (nv[s] = values[s + 1]). One closed-loop step is four launches and one copy: pf_policy_act, pf_env_step, pf_world_sync with its
+ *     n-byte device copy, pf_env_reset.
+ *   - THE LATCH IS READ BY THE WHOLE WORLD AND REWRITTEN, and two lanes of a world may run in different workgroups (A need not
+ *     divide the workgroup). The kernel therefore writes the new latch to a staging buffer of n bytes that the context owns, never
+ *     to the latch it reads, and the call copies the staging buffer over `done` behind the kernel on the same stream (a
+ *     device-to-device copy node). The caller sees one latch, in and out. Calls on one context share that buffer: they must be
+ *     ordered (one stream, or events between streams).
+ *   - ANY CONTEXT: it supplies n, the device and the error string; vehicle, task and auto-reset mode are not looked at.
+ *   - ERRORS. PF_ERR_ARG, pf_last_error naming the argument: a NULL ctx or argument block; a NULL terminated, truncated, reward,
+ *     done, valid_out or reset_out; agents_per_world outside 1..64; n not a multiple of agents_per_world.
+ *   - Enqueued on `stream`: one launch and one n-byte device copy, no host synchronisation, no allocation -- capturable in a HIP graph.
+ *     One thread per lane; each reads the A latch bytes of its world itself, with plain loads. */
+typedef struct pf_world_sync_args {
+  uint8_t* terminated;      /* [n] this step's row, read and rewritten */
+  uint8_t* truncated;       /* [n] this step's row, read and rewritten */
+  float*   reward;          /* [n] this step's row, read and rewritten */
+  uint8_t* done;            /* [n] the latch, read and rewritten: 1 = this lane's episode has ended and its world has not been reset yet */
+  const uint8_t* exclude;   /* [n] or NULL: lanes that are never valid (an opponent's) */
+  uint8_t* valid_out;       /* [n] */
+  uint8_t* reset_out;       /* [n] the mask to hand to pf_env_reset */
+} pf_world_sync_args;
+size_t pf_sizeof_world_sync(void);
+int pf_world_sync(pf_ctx* ctx, const pf_world_sync_args* a, int agents_per_world, void* stream);
+
 /* The reference's LOWER boundary for one drone: applyExternalForce / applyExternalTorque on the base link in
  * LINK_FRAME followed by stepSimulation (core/drones/quadx.py:502-510, core/aviary.py:516), n_ticks times with
  * the wrench b->wrench held: the free-body tick alone (collision detection, gyroscopic term, +-max_coord_vel

@@ -79,6 +79,7 @@ PfPid, PfBox, PfSurface, PfRocket = _STRUCTS["pf_pid"], _STRUCTS["pf_box"], _STR
 PfParams, PfBuffers, PfPolicy, PfGae = _STRUCTS["pf_params"], _STRUCTS["pf_buffers"], _STRUCTS["pf_policy"], _STRUCTS["pf_gae_args"]
 PfTrajStats, PfPpoLoss, PfMlp = _STRUCTS["pf_traj_stats_args"], _STRUCTS["pf_ppo_loss_args"], _STRUCTS["pf_mlp"]
 PfAdam, PF_ADAM_MAX_TENSORS = _STRUCTS["pf_adam_args"], _DEFINES["PF_ADAM_MAX_TENSORS"]
+PfWorldSync = _STRUCTS["pf_world_sync_args"]
 for _k, _v in _ENUMS.items():  # PF_F_TERMINATED -> F_TERMINATED etc. stay spelled out above; expose the rest as PF_*
     globals().setdefault(_k, _v)
 
@@ -152,11 +153,14 @@ def lib():
     L.pf_adam_workspace_bytes.argtypes = [C.c_int64]
     L.pf_adam_workspace_bytes.restype = C.c_size_t
     L.pf_adam_step.argtypes = [C.c_void_p, C.POINTER(PfAdam), C.c_void_p, C.c_size_t, C.c_void_p]
+    L.pf_sizeof_world_sync.restype = C.c_size_t
+    L.pf_world_sync.argtypes = [C.c_void_p, C.POINTER(PfWorldSync), C.c_int, C.c_void_p]
     L.pf_sizeof_params.restype = C.c_size_t
     L.pf_sizeof_buffers.restype = C.c_size_t
     if L.pf_sizeof_params() != C.sizeof(PfParams) or L.pf_sizeof_buffers() != C.sizeof(PfBuffers) or L.pf_sizeof_policy() != C.sizeof(PfPolicy) \
             or L.pf_sizeof_gae() != C.sizeof(PfGae) or L.pf_sizeof_traj_stats() != C.sizeof(PfTrajStats) \
-            or L.pf_sizeof_ppo_loss() != C.sizeof(PfPpoLoss) or L.pf_sizeof_mlp() != C.sizeof(PfMlp) or L.pf_sizeof_adam() != C.sizeof(PfAdam):
+            or L.pf_sizeof_ppo_loss() != C.sizeof(PfPpoLoss) or L.pf_sizeof_mlp() != C.sizeof(PfMlp) or L.pf_sizeof_adam() != C.sizeof(PfAdam) \
+            or L.pf_sizeof_world_sync() != C.sizeof(PfWorldSync):
         raise PyFlytAmdError("struct layout mismatch between pyflyt_amd/_lib.py and include/pyflyt_amd.h")
     if L.pf_abi_version() != PF_ABI_VERSION:
         raise PyFlytAmdError("ABI version mismatch between pyflyt_amd/_lib.py and libpyflyt_amd.so")

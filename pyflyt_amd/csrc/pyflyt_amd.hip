@@ -729,6 +729,7 @@ __global__ void __launch_bounds__(256) sample_actions_kernel(const pf_params P, 
 #include "policy_act.hpp"
 #include "mlp.hpp"
 #include "adam.hpp"
+#include "world_sync.hpp"
 
 // ====================================================================== C ABI
 // The env kernel a context runs, chosen once at pf_ctx_create (select_env_kernel).
@@ -764,6 +765,7 @@ struct pf_ctx {
   float* policy_dev;      // the specialised QuadX kernel: pf_rollout_policy's packed weights (policy_mlp.hpp), rewritten by every call
   double* ts_scratch;     // contexts with an env task: pf_traj_stats's partial sums between its launches (traj_stats.hpp: ts_scratch_words)
   double* ppo_scratch;    // every context: pf_ppo_loss's partial sums between its launches (ppo_loss.hpp: kPpoScratchWords)
+  uint8_t* sync_latch;    // every context: pf_world_sync's staging buffer, n bytes -- the new latch, copied over the caller's behind the kernel (world_sync.hpp)
   int act_grid_cap;       // pf_policy_act: the most workgroups a launch takes, two per CU of the device: what its registers admit (two waves per SIMD; profiles/policy_act/resources.txt) (policy_act.hpp)
 };
 static thread_local char g_err[256] = "";
@@ -969,6 +971,7 @@ size_t pf_sizeof_traj_stats(void) { return sizeof(pf_traj_stats_args); }
 size_t pf_sizeof_ppo_loss(void) { return sizeof(pf_ppo_loss_args); }
 size_t pf_sizeof_mlp(void) { return sizeof(pf_mlp); }
 size_t pf_sizeof_adam(void) { return sizeof(pf_adam_args); }
+size_t pf_sizeof_world_sync(void) { return sizeof(pf_world_sync_args); }
 const char* pf_last_error(const pf_ctx* ctx) { return ctx ? ctx->err : g_err; }
 
 int pf_ctx_create(const pf_params* params, int n_lanes, int device, uint64_t lane_offset, pf_ctx** out) {
@@ -1031,7 +1034,7 @@ int pf_ctx_create(const pf_params* params, int n_lanes, int device, uint64_t lan
     return fail(nullptr, PF_ERR_ARG, "the contact model's distances, threshold, erp, friction and restitution must be >= 0");
   pf_ctx* c = new (std::nothrow) pf_ctx;
   if (!c) return fail(nullptr, PF_ERR_ARG, "out of host memory");
-  c->P = P; c->n = n_lanes; c->device = device; c->lane0 = lane_offset; c->err[0] = 0; c->launch_ctr = nullptr; c->policy_dev = nullptr; c->ts_scratch = nullptr; c->ppo_scratch = nullptr;
+  c->P = P; c->n = n_lanes; c->device = device; c->lane0 = lane_offset; c->err[0] = 0; c->launch_ctr = nullptr; c->policy_dev = nullptr; c->ts_scratch = nullptr; c->ppo_scratch = nullptr; c->sync_latch = nullptr;
   {  // the airframe's worst-case contact count (collider vertices), see pf_params.contact_max_points
     int pts = 0;
     for (int k = 0; k < P.n_boxes; ++k) pts += P.boxes[k].kind == 1 ? 16 : (P.contact_manifold_points >= 8 ? 8 : 4);
@@ -1071,8 +1074,9 @@ int pf_ctx_create(const pf_params* params, int n_lanes, int device, uint64_t lan
     if (e == hipSuccess && fam != env_family::none)
       e = hipMalloc((void**)&c->ts_scratch, sizeof(double) * pf::ts_scratch_words(n_lanes, pf_obs_dim(c)));
     if (e == hipSuccess) e = hipMalloc((void**)&c->ppo_scratch, sizeof(double) * pf::kPpoScratchWords);
+    if (e == hipSuccess) e = hipMalloc((void**)&c->sync_latch, (size_t)n_lanes);
     if (cur >= 0) (void)hipSetDevice(cur);
-    if (e != hipSuccess) { if (c->P_dev) hipFree(c->P_dev); if (c->launch_ctr) hipFree(c->launch_ctr); if (c->policy_dev) hipFree(c->policy_dev); if (c->surf_dev) hipFree(c->surf_dev); if (c->ts_scratch) hipFree(c->ts_scratch); if (c->ppo_scratch) hipFree(c->ppo_scratch); delete c; return hip_fail(nullptr, e, "pf_ctx_create: device parameter block"); }
+    if (e != hipSuccess) { if (c->P_dev) hipFree(c->P_dev); if (c->launch_ctr) hipFree(c->launch_ctr); if (c->policy_dev) hipFree(c->policy_dev); if (c->surf_dev) hipFree(c->surf_dev); if (c->ts_scratch) hipFree(c->ts_scratch); if (c->ppo_scratch) hipFree(c->ppo_scratch); if (c->sync_latch) hipFree(c->sync_latch); delete c; return hip_fail(nullptr, e, "pf_ctx_create: device parameter block"); }
   }
   if ((fam == env_family::fixedwing_wp || fam == env_family::generic) && (P.task == PF_TASK_HOVER || P.task == PF_TASK_WAYPOINTS) &&
       (P.vehicle == PF_FIXEDWING || P.noise_mode == PF_NOISE_OFF)) {
@@ -1090,7 +1094,7 @@ int pf_ctx_create(const pf_params* params, int n_lanes, int device, uint64_t lan
       e = hipDeviceSynchronize();
     }
     if (cur >= 0) hipSetDevice(cur);
-    if (e != hipSuccess) { if (c->tmpl) hipFree(c->tmpl); if (c->surf_dev) hipFree(c->surf_dev); if (c->ts_scratch) hipFree(c->ts_scratch); if (c->ppo_scratch) hipFree(c->ppo_scratch); hipFree(c->P_dev); delete c; return hip_fail(nullptr, e, "pf_ctx_create: settle template"); }
+    if (e != hipSuccess) { if (c->tmpl) hipFree(c->tmpl); if (c->surf_dev) hipFree(c->surf_dev); if (c->ts_scratch) hipFree(c->ts_scratch); if (c->ppo_scratch) hipFree(c->ppo_scratch); if (c->sync_latch) hipFree(c->sync_latch); hipFree(c->P_dev); delete c; return hip_fail(nullptr, e, "pf_ctx_create: settle template"); }
   }
   *out = c;
   return PF_OK;
@@ -1104,6 +1108,7 @@ void pf_ctx_destroy(pf_ctx* ctx) {
   if (ctx->surf_dev) hipFree(ctx->surf_dev);
   if (ctx->ts_scratch) hipFree(ctx->ts_scratch);
   if (ctx->ppo_scratch) hipFree(ctx->ppo_scratch);
+  if (ctx->sync_latch) hipFree(ctx->sync_latch);
   delete ctx;
 }
 int pf_state_groups(const pf_ctx* ctx) {
@@ -1652,6 +1657,26 @@ int pf_adam_step(pf_ctx* ctx, const pf_adam_args* a, void* workspace, size_t wor
   hipLaunchKernelGGL(pf::adam_norm_kernel, dim3(grid), dim3(pf::kAdamBlock), 0, s, K);
   hipLaunchKernelGGL(pf::adam_update_kernel, dim3(grid), dim3(pf::kAdamBlock), 0, s, K);
   PF_HIP(ctx, hipGetLastError());
+  return PF_OK;
+}
+int pf_world_sync(pf_ctx* ctx, const pf_world_sync_args* a, int agents_per_world, void* stream) {
+  static const char* who = "pf_world_sync";
+  if (!ctx) return arg_fail(ctx, who, "ctx is required");
+  if (!a) return arg_fail(ctx, who, "the argument block is required");
+  const arg_ptr required[] = {{"terminated", a->terminated}, {"truncated", a->truncated}, {"reward", a->reward}, {"done", a->done},
+                              {"valid_out", a->valid_out}, {"reset_out", a->reset_out}, {nullptr, nullptr}};
+  if (int rc = require_args(ctx, who, required)) return rc;
+  if (agents_per_world < 1 || agents_per_world > pf::kWorldSyncMaxA) return arg_fail(ctx, who, "agents_per_world must be in 1..64");
+  if (ctx->n % agents_per_world != 0) return arg_fail(ctx, who, "agents_per_world must divide the context's lane count n");
+  int rc = ensure_device(ctx);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  // (the new latch goes to the context's staging buffer and is copied over the caller's behind the kernel: world_sync.hpp)
+  const pf::WorldSyncK K{a->terminated, a->truncated, a->reward, a->done, a->exclude, a->valid_out, a->reset_out, ctx->sync_latch};
+  hipLaunchKernelGGL(pf::world_sync_kernel, dim3((ctx->n + pf::kWorldSyncBlock - 1) / pf::kWorldSyncBlock), dim3(pf::kWorldSyncBlock), 0, s, K, ctx->n,
+                     agents_per_world);
+  PF_HIP(ctx, hipGetLastError());
+  PF_HIP(ctx, hipMemcpyAsync(a->done, ctx->sync_latch, (size_t)ctx->n, hipMemcpyDeviceToDevice, s));
   return PF_OK;
 }
 int pf_body_tick(pf_ctx* ctx, const pf_buffers* b, int n_ticks, void* stream) {

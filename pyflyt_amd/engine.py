@@ -67,8 +67,9 @@ class BatchEngine(TrainOps):
         # env_step's hot path: {id(action tensor): (the tensor, its filled pf_buffers block)} -- see env_step
         self._prepared: dict[int, tuple] = {}
         self._step_fn = self.lib.pf_env_step
-        # the tensor that holds every lane's CURRENT observation: self.obs after a reset or a step, the last trajectory row after a
-        # rollout of either kind -- what rollout_policy's first step acts on (pf_policy.obs0)
+        # the tensor that holds every lane's CURRENT observation: self.obs after a reset or a step (and after a world rollout, which
+        # copies its last row there), the last trajectory row after a rollout of either other kind -- what rollout_policy's first step
+        # acts on (pf_policy.obs0)
         self._cur_obs = self.obs
 
     def close(self):
@@ -151,6 +152,9 @@ class BatchEngine(TrainOps):
         if ts is not None:  # (traj_stats' carries: the open episodes of the lanes that were reset are gone)
             for name in ("carry_return", "carry_length", "carry_disc"):
                 ts[name].zero_() if mask is None else ts[name].masked_fill_(mask.bool(), 0)
+        wd = self._world_done
+        if wd is not None:  # (world_sync's latch: the lanes that were reset have an open episode again)
+            wd.zero_() if mask is None else wd.masked_fill_(mask.bool(), 0)
         return self.obs
 
     @property
@@ -321,7 +325,7 @@ class BatchEngine(TrainOps):
         trajectory rows (final_obs / final_info rows included under SAME_STEP): nothing is copied. Where rollout_policy runs, the
         results are bit-identical. Needs an auto-reset mode and PF_NOISE_OFF / PF_NOISE_PHILOX (ValueError otherwise) -- so the
         multi-agent tasks (dogfight, multi-agent hover), which exist with auto-reset OFF only, are refused here: their loop is
-        policy_act and env_step, with the culling of finished agents in between."""
+        rollout_policy_worlds (whole worlds reset on the device), or policy_act and env_step with the culling by hand."""
         q, k, _ = self._closed_loop(policy, k_steps, False)
         return self._rollout_with(self._launch_policy_steps, q, k, step_index0, store_mean)
 
@@ -423,6 +427,157 @@ class BatchEngine(TrainOps):
             self._cur_obs = cur
             raise
         return t
+
+    # ------------------------------------------------------------------ multi-agent worlds
+    @property
+    def world_done(self):
+        """[n] uint8, made at first use: world_sync's latch as rollout_policy_worlds keeps it -- 1 = this lane's episode has ended and
+        its world has not been reset yet. env_reset() zeroes it, env_reset(mask=...) the masked lanes."""
+        return self._lazy("_world_done", lambda: torch.zeros(self.n, dtype=torch.uint8, device=self.device))
+
+    def _check_world(self, agents_per_world):
+        A = int(agents_per_world)
+        if not 1 <= A <= 64 or self.n % A != 0:
+            raise ValueError(f"agents_per_world must be in 1..64 and divide the lane count {self.n}, got {agents_per_world}")
+        return A
+
+    def world_sync(self, terminated, truncated, reward, done, agents_per_world, exclude=None, valid_out=None, reset_out=None):
+        """pf_world_sync: the world-level auto-reset between two env steps (include/pyflyt_amd.h has the rules). terminated, truncated
+        [n] bool / uint8 and reward [n] float32: the row the env step has just written, rewritten in place (zeros where the lane's
+        agent had finished before the step); done [n] bool / uint8: the latch, read and rewritten; worlds are `agents_per_world`
+        adjacent lanes; exclude [n] bool / uint8 or None: lanes that are never valid. Returns (valid [n], reset mask [n]) --
+        `valid_out` / `reset_out`, or bool tensors the engine owns, overwritten by the next call. The mask goes to
+        env_reset(mask=...) or pf_env_reset. Any engine; nothing synchronises."""
+        A, n = self._check_world(agents_per_world), (self.n,)
+        need = "{name} is required: a tensor of shape {shape}"
+        K.tensor(self.device, terminated, "terminated", n, K.FLAGS, required=need)
+        K.tensor(self.device, truncated, "truncated", n, K.FLAGS, required=need)
+        K.tensor(self.device, reward, "reward", n, required=need)
+        K.tensor(self.device, done, "done", n, K.FLAGS, required=need)
+        K.tensor(self.device, exclude, "exclude", n, K.FLAGS)
+        if valid_out is None or reset_out is None:
+            o = self._lazy("_world_out", lambda: dict(valid=torch.empty(self.n, dtype=torch.bool, device=self.device),
+                                                      reset=torch.empty(self.n, dtype=torch.bool, device=self.device)))
+            valid_out, reset_out = (o["valid"] if valid_out is None else valid_out), (o["reset"] if reset_out is None else reset_out)
+        K.tensor(self.device, valid_out, "valid_out", n, K.FLAGS, required=need)
+        K.tensor(self.device, reset_out, "reset_out", n, K.FLAGS, required=need)
+        a = L.PfWorldSync()
+        a.terminated, a.truncated, a.reward, a.done = _ptr(terminated), _ptr(truncated), _ptr(reward), _ptr(done)
+        a.exclude, a.valid_out, a.reset_out = _ptr(exclude), _ptr(valid_out), _ptr(reset_out)
+        self._launch(self.lib.pf_world_sync, C.byref(a), A)
+        return valid_out, reset_out
+
+    def _closed_loop_worlds(self, policy, k_steps, agents_per_world, opponent, opponent_lanes):
+        """What rollout_policy_worlds and collect_rollout_worlds refuse before they touch a tensor; returns (the policy's pf_policy
+        block, the opponent's or None, k, A)."""
+        if self.params.task == L.TASK_NONE:
+            raise ValueError("the world rollout needs an engine with an env task")
+        if self.params.autoreset != L.AUTORESET_OFF:
+            raise ValueError("the world rollout runs under auto-reset OFF (the multi-agent envs; pf_world_sync resets whole worlds): "
+                             "an env with an auto-reset mode of its own goes through rollout_policy_steps")
+        if self.params.noise_mode == L.NOISE_INJECT:
+            raise ValueError("the world rollout runs under PF_NOISE_OFF / PF_NOISE_PHILOX (PF_NOISE_INJECT passes per-step noise tensors; use policy_act and env_step)")
+        k = int(k_steps)
+        if k < 1:
+            raise ValueError(f"k_steps must be >= 1, got {k_steps}")
+        A = self._check_world(agents_per_world)
+        if (opponent is None) != (opponent_lanes is None):
+            raise ValueError("opponent and opponent_lanes come together or not at all")
+        q = self._policy_block(policy)
+        qo = None
+        if opponent is not None:
+            qo = self._policy_block(opponent)
+            K.tensor(self.device, opponent_lanes, "opponent_lanes", (self.n,), K.FLAGS, required="{name} must be a bool / uint8 tensor of shape {shape}")
+        return q, qo, k, A
+
+    def rollout_policy_worlds(self, policy, k_steps: int, agents_per_world: int, step_index0: int = 0, opponent=None, opponent_lanes=None,
+                              store_mean: bool = False):
+        """The closed loop of the multi-agent envs (dogfight, multi-agent hover: auto-reset OFF), with worlds of `agents_per_world`
+        adjacent lanes reset on the device once every agent of them has finished. Step s enqueues pf_policy_act(policy,
+        step_index0 + s) on the current observation into actions[s] (and mean[s]); pf_env_step into row s; pf_world_sync on row s,
+        which writes valid[s], blanks the rows of the lanes that had finished before and names the worlds that were waiting; and
+        pf_env_reset of those worlds with row s as the observation buffer: four launches and pf_world_sync's n-byte device copy; nothing
+        synchronises with the host.
+        With `opponent` (an MLPPolicy) and `opponent_lanes` ([n] bool / uint8) a second pf_policy_act with the same step index
+        and one merge put the opponent's actions on those lanes, which are never valid: six launches and the copy. The last observation row is copied into self.obs, which is the engine's
+        current observation afterwards: env_step and a masked env_reset go on from it as after a step. Returns (obs [k, n, D],
+        reward, terminated, truncated [k, n], actions [k, n, action width], valid [k, n] bool) and, with store_mean, the policy's
+        means as a seventh: tensors the engine owns, overwritten by the next call with the same k. The latch is world_done."""
+        q, qo, k, A = self._closed_loop_worlds(policy, k_steps, agents_per_world, opponent, opponent_lanes)
+        t = self._lazy("_wtraj", lambda: self._new_world_traj(k, k), keep=lambda t: t["k"] == k)
+        mean = self._traj_mean(t) if store_mean else None
+        self._launch_policy_worlds(q, qo, opponent_lanes, t, k, A, step_index0, mean)
+        out = (t["obs"], t["reward"], t["terminated"], t["truncated"], t["actions"], t["valid"])
+        return out + (mean,) if store_mean else out
+
+    def collect_rollout_worlds(self, policy, k_steps: int, agents_per_world: int, step_index0: int = 0, opponent=None, opponent_lanes=None):
+        """rollout_policy_worlds for a learner, as collect_rollout is rollout_policy_steps': the same loop into trajectory tensors of
+        its own whose observations live in ONE buffer obs_all [k + 1, n, D] -- row 0 a copy of the engine's current observation,
+        rows 1 .. k written by the env steps (and, on reset steps, by the resets). Returns collect_rollout's dict (obs_all, obs =
+        obs_all[1:], reward, terminated, truncated, actions, mean) plus valid [k, n] bool."""
+        q, qo, k, A = self._closed_loop_worlds(policy, k_steps, agents_per_world, opponent, opponent_lanes)
+        t = self._lazy("_wctraj", lambda: self._new_world_traj(k, k + 1), keep=lambda t: t["k"] == k)
+        cur = self._cur_obs
+        t["obs_all"][0].copy_(cur)
+        self._cur_obs = t["obs_all"][0]
+        try:
+            self._launch_policy_worlds(q, qo, opponent_lanes, t, k, A, step_index0, self._traj_mean(t))
+        except L.PyFlytAmdError:  # (refused: the engine's current observation is where it was)
+            self._cur_obs = cur
+            raise
+        return t
+
+    def _new_world_traj(self, k, obs_rows):
+        t = self._new_traj(k, obs_rows, mean=False)
+        t["valid"] = torch.empty(k, self.n, dtype=torch.bool, device=self.device)
+        t["reset"] = torch.empty(self.n, dtype=torch.uint8, device=self.device)  # (this step's reset mask: world_sync writes it, the reset reads it)
+        return t
+
+    def _launch_policy_worlds(self, q, qo, opp_lanes, t, k, A, step_index0, mean):
+        """k x (pf_policy_act [, the opponent's and the merge], pf_env_step, pf_world_sync, pf_env_reset) into the trajectory tensors
+        `t`, acting first on the engine's current observation. The reset's buffer block points at the observation row of the step."""
+        b = L.PfBuffers()
+        C.memmove(C.byref(b), C.byref(self._buffers()), C.sizeof(L.PfBuffers))
+        br = L.PfBuffers()
+        C.memmove(C.byref(br), C.byref(b), C.sizeof(L.PfBuffers))
+        w = L.PfWorldSync()
+        lib, ctx, qref, bref, brref, wref = self.lib, self._ctx, C.byref(q), C.byref(b), C.byref(br), C.byref(w)
+        n, D, W = self.n, self.obs_dim, self.action_dim
+        p_obs, p_act, p_rew = t["obs"].data_ptr(), t["actions"].data_ptr(), t["reward"].data_ptr()
+        p_term, p_trunc, p_valid = t["terminated"].data_ptr(), t["truncated"].data_ptr(), t["valid"].data_ptr()
+        p_mean = mean.data_ptr() if mean is not None else None
+        w.done, w.reset_out, w.exclude = self.world_done.data_ptr(), t["reset"].data_ptr(), _ptr(opp_lanes)
+        p_mask = C.c_void_p(t["reset"].data_ptr())
+        opp = None
+        if qo is not None:
+            opp = self._lazy("_opp_act", lambda: torch.empty(n, W, dtype=torch.float32, device=self.device), keep=lambda o: o.shape[1] == W)
+            qo.mean_out, p_opp, oref, pick = None, C.c_void_p(opp.data_ptr()), C.byref(qo), opp_lanes.bool().view(n, 1)
+        cur = self._cur_obs.data_ptr()
+        with torch.cuda.device(self.device):
+            stream = self._stream()
+            for s in range(k):
+                step_index = (int(step_index0) + s) & 0xFFFFFFFF
+                q.obs0 = cur
+                q.mean_out = p_mean + 4 * n * W * s if p_mean is not None else None
+                a = p_act + 4 * n * W * s
+                L.check(lib.pf_policy_act(ctx, qref, a, step_index, stream), ctx)
+                if opp is not None:
+                    qo.obs0 = cur
+                    L.check(lib.pf_policy_act(ctx, oref, p_opp, step_index, stream), ctx)
+                    row = t["actions"][s]
+                    torch.where(pick, opp, row, out=row)  # (the merge: one launch on the same stream)
+                cur = p_obs + 4 * n * D * s
+                b.actions, b.obs, b.reward = a, cur, p_rew + 4 * n * s
+                b.terminated, b.truncated = p_term + n * s, p_trunc + n * s
+                L.check(lib.pf_env_step(ctx, bref, stream), ctx)
+                w.terminated, w.truncated, w.reward, w.valid_out = b.terminated, b.truncated, b.reward, p_valid + n * s
+                L.check(lib.pf_world_sync(ctx, wref, A, stream), ctx)
+                br.obs = cur
+                L.check(lib.pf_env_reset(ctx, brref, p_mask, stream), ctx)
+        # the last row becomes self.obs: a masked env_reset (reset_envs) writes the lanes it resets THERE and leaves the others, so the
+        # tensor it writes must hold every lane's current observation -- as after an env_step, not k steps old
+        self.obs.copy_(t["obs"][k - 1])
+        self._cur_obs = self.obs
 
     def body_tick(self, wrench, n_ticks: int = 1):
         """pf_body_tick: the free-body tick alone under a held body-frame wrench [n, 6] (force, torque)."""

@@ -35,11 +35,12 @@ from .. import _lib as L
 from ..engine import BatchEngine
 from ..params import build_params
 from ..spaces import Box
+from ._world_rollout import WorldRollout
 
 _DF_ALIVE, _DF_DEAD, _DF_COLLISION, _DF_OOB, _DF_TEAM_WIN = 1, 16, 32, 64, 128  # dogfight.hpp, state group 6 word 3
 
 
-class MAFixedwingDogfightEnv:
+class MAFixedwingDogfightEnv(WorldRollout):
     metadata = {"render_modes": [], "name": "ma_fixedwing_team_dogfight"}
 
     def __init__(self, team_size: int = 2, spawn_min_radius: float = 10.0, spawn_max_radius: float = 50.0,
@@ -140,10 +141,13 @@ class MAFixedwingDogfightEnv:
             # a seeded reset replays the seed's stream from its start (np.random.RandomState(seed) in the reference, :187):
             # the counter RNG's event counters go back to zero; reset(seed=None) continues the stream
             self.engine.state[5, :, 2] = 0.0
+            self._policy_step = 0
         self.step_count = 0
         self.agents = self.possible_agents[:]
         self.engine.env_reset()
-        self._done = torch.zeros(self.num_envs, self.num_possible_agents, dtype=torch.bool, device=self.device)
+        # the latch is the engine's (world_done, zeroed by the reset): step(), reset_envs() and rollout() / collect() keep ONE copy of it
+        self._done = self.engine.world_done.view(torch.bool).view(self.num_envs, self.num_possible_agents)
+        self._needs_reset = False
         obs = self._split(self.engine.obs)
         return {ag: self._obs_out(obs[i]) for i, ag in enumerate(self.possible_agents)}, {ag: dict() for ag in self.agents}
 
@@ -165,6 +169,52 @@ class MAFixedwingDogfightEnv:
         until that copy is reset. With num_envs > 1 the per-step `terminations` / `truncations` report the ending step only;
         this is what a caller culls by."""
         return self._done
+
+    # ------------------------------------------------------------------ closed-loop rollouts (pz_envs/_world_rollout.py)
+    _team1 = None  # [n] bool: the lanes of team 1 (agent index >= team_size), made when an opponent first flies them
+
+    def _world_args(self, opponent):
+        if opponent is None:
+            return None, None
+        if self._team1 is None:
+            self._team1 = torch.as_tensor(self.team_flag, device=self.device).repeat(self.num_envs).contiguous()
+        return opponent, self._team1
+
+    def _flat_infos(self):
+        side = self.engine.state[6]
+        bits = lambda: side[:, 3].view(torch.int32)
+        return {"health": lambda: side[:, 0], "received_hits": lambda: side[:, 2].view(torch.int32), "dead": lambda: (bits() & _DF_DEAD) != 0,
+                "collision": lambda: (bits() & _DF_COLLISION) != 0, "out_of_bounds": lambda: (bits() & _DF_OOB) != 0,
+                "team_win": lambda: (bits() & _DF_TEAM_WIN) != 0}
+
+    def rollout(self, policy, k_steps: int, opponent=None, store_mean: bool = False):
+        """`k_steps` closed-loop env steps of every copy, every action computed on the device by `policy` (a pyflyt_amd.MLPPolicy over
+        the flattened observation) -- the loop of policy_act, step(), culling and reset_envs() without the host: a copy whose
+        aircraft have ALL finished is reset on the device in the next step, which is no transition for any of them
+        (BatchEngine.rollout_policy_worlds; four launches and one n-byte device copy per step, six and the copy with an opponent). Returns (obs [k, n, D], reward,
+        terminated, truncated [k, n], actions [k, n, action width], valid [k, n] bool) and with store_mean the policy's means as a
+        seventh: flat tensors with n = num_envs * agents, lane = copy * agents + agent -- t.view(k, num_envs, agents, ...) reads
+        them per copy and aircraft. They belong to the engine and are overwritten by the next call with the same k_steps.
+        `valid` is False where an aircraft sat the step out (finished before it: it flies on with zero commands, its reward and
+        flags read 0), on the step that reset its copy, and on an opponent's lanes.
+        `opponent`: a second MLPPolicy, frozen as far as this env is concerned, that flies team 1 (agent index >= team_size) from
+        the same observations with the same noise keys; team 1's lanes are then never valid.
+        The exploration noise's step index advances by k_steps per call and restarts with reset(seed=...). Afterwards `done` is
+        the latch as the last step left it, `agents` the full list (as after reset_envs), and step() / reset_envs() go on from there."""
+        return self._world_rollout(policy, k_steps, opponent, store_mean)
+
+    def collect(self, policy, value_fn, k_steps: int, gamma: float = 0.99, lam: float = 0.95, opponent=None):
+        """One PPO batch from rollout()'s loop, as the vector envs' collect(): `value_fn` (a float32 [M, D] tensor -> [M] or [M, 1])
+        runs under torch.no_grad() on all k + 1 observation rows, pf_gae (BatchEngine.gae) supplies advantages, returns and logp.
+        Returns a dict with the vector envs' keys: obs [k, n, D] the policy's inputs, actions, mean, logp (None without a log_std),
+        values, advantages, returns, valid, reward, terminated, truncated [k, n], last_value [n], infos (of the last step, lazy,
+        over the flat lanes). Flat as in rollout(): t.view(k, num_envs, agents, ...). `valid` is rollout()'s (pf_world_sync's; pf_gae's
+        own is all ones without an auto-reset mode): mask the losses with it -- pyflyt_amd.ppo_loss(env, ..., batch) does. A valid step's
+        advantage depends on valid steps only: an episode's last step cuts the recursion, and a truncated aircraft bootstraps from
+        its terminal observation, which the reset never overwrites (it lands in the row of the reset step).
+        `stats=` and `normalize_reward=` do not exist here: pf_traj_stats under auto-reset OFF counts every step, so the steps a
+        finished aircraft sits out would be counted into its next episode's return and length."""
+        return self._world_collect(policy, value_fn, k_steps, gamma, lam, opponent)
 
     # ------------------------------------------------------------------ ma_fixedwing_base_env.py:272-334
     def step(self, actions: dict):

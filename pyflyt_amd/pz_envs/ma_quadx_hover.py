@@ -36,9 +36,10 @@ from ..engine import BatchEngine
 from ..gym_envs.vector_envs import LazyInfos
 from ..params import build_params, quat_from_euler
 from ..spaces import Box
+from ._world_rollout import WorldRollout
 
 
-class MAQuadXHoverEnv:
+class MAQuadXHoverEnv(WorldRollout):
     metadata = {"render_modes": [], "name": "ma_quadx_hover"}
 
     def __init__(self, start_pos=np.array([[-1.0, -1.0, 1.0], [1.0, -1.0, 1.0], [-1.0, 1.0, 1.0], [1.0, 1.0, 1.0]]),
@@ -137,11 +138,40 @@ class MAQuadXHoverEnv:
             self.engine.close()
             self._build(self._seed)
             self.engine.state[12:16] = keep
+        if seed is not None:
+            self._policy_step = 0
+        self._needs_reset = False
         self.step_count = 0
         self.agents = self.possible_agents[:]
         self.engine.env_reset()
         obs = self._split(self.engine.obs)
         return {ag: obs[i] for i, ag in enumerate(self.possible_agents)}, {ag: dict() for ag in self.agents}
+
+    # ------------------------------------------------------------------ closed-loop rollouts (pz_envs/_world_rollout.py)
+    def _flat_infos(self):
+        f = self.engine.flags()
+        return {"collision": lambda: (f & L.F_INFO_COLLISION) != 0, "out_of_bounds": lambda: (f & L.F_INFO_OOB) != 0}
+
+    def rollout(self, policy, k_steps: int, store_mean: bool = False):
+        """`k_steps` closed-loop env steps of every copy, every action computed on the device by `policy` (a pyflyt_amd.MLPPolicy) --
+        the loop of policy_act and step() without the host, for shared_world False and True alike: a copy whose drones have ALL
+        finished is reset on the device in the next step, which is no transition for any of them (BatchEngine.rollout_policy_worlds,
+        four launches and one n-byte device copy per step). Returns (obs [k, n, D], reward, terminated, truncated [k, n], actions [k, n, 4], valid [k, n]
+        bool) and with store_mean the policy's means as a seventh: flat tensors with n = num_envs * agents, lane = copy * agents +
+        agent -- t.view(k, num_envs, agents, ...) reads them per copy and drone. They belong to the engine and are overwritten by
+        the next call with the same k_steps. `valid` is False where a drone sat the step out (finished before it; its reward and
+        flags read 0) and on the step that reset its copy; engine.world_done is the latch. The exploration noise's step index
+        advances by k_steps per call and restarts with reset(seed=...). Afterwards `agents` is the full list."""
+        return self._world_rollout(policy, k_steps, None, store_mean)
+
+    def collect(self, policy, value_fn, k_steps: int, gamma: float = 0.99, lam: float = 0.95):
+        """One PPO batch from rollout()'s loop, as the vector envs' collect(): `value_fn` (a float32 [M, D] tensor -> [M] or [M, 1])
+        runs under torch.no_grad() on all k + 1 observation rows, pf_gae (BatchEngine.gae) supplies advantages, returns and logp.
+        Returns a dict with the vector envs' keys (obs, actions, mean, logp, values, advantages, returns, valid, reward, terminated,
+        truncated, last_value, infos), flat as in rollout(): t.view(k, num_envs, agents, ...). `valid` is rollout()'s
+        (pf_world_sync's): mask the losses with it. `stats=` and `normalize_reward=` do not exist here: pf_traj_stats under
+        auto-reset OFF counts every step, so the steps a finished drone sits out would be counted into its next episode."""
+        return self._world_collect(policy, value_fn, k_steps, gamma, lam, None)
 
     # ------------------------------------------------------------------ ma_quadx_base_env.py:309-371
     def step(self, actions: dict):

@@ -35,6 +35,11 @@ class TrainOps:
     _mlp_bwd = None   # {(rows, layer shapes): mlp_backward()'s gradients, pointer arrays and workspace}
     _adam = None      # {addresses: adam_step()'s filled argument block}, the 64 most recent
     _adam_ws = None   # {total elements: adam_step()'s workspace}
+    _world_done = None  # [n] uint8: world_sync's latch as the world rollouts keep it (BatchEngine.world_done)
+    _world_out = None   # dict: world_sync()'s valid / reset mask when the caller passes none
+    _wtraj = None     # dict: rollout_policy_worlds()'s trajectory tensors, for the last k
+    _wctraj = None    # dict: collect_rollout_worlds()'s (observations in one [k + 1, n, D] buffer), for the last k
+    _opp_act = None   # [n, action width] float32: rollout_policy_worlds()'s opponent actions before the merge
 
     def _lazy(self, name, make, keep=None):
         """self.<name> of the list above: made by make() at first use, and again when keep(it) is false (tensors of another size)."""
