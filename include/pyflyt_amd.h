@@ -669,6 +669,53 @@ size_t pf_mlp_backward_workspace_bytes(const pf_mlp* mlp, int64_t rows);
 int pf_mlp_backward(pf_ctx* ctx, const pf_mlp* mlp, const float* x, const float* grad_out, int64_t rows, float* const grad_w[3],
                     float* const grad_b[3], void* workspace, size_t workspace_bytes, void* stream);
 
+/* A PPO epoch's parameter gradients from x in one call. By definition the semantics are those of the composition
+ * pf_mlp_forward(actor), pf_mlp_forward(critic), pf_ppo_loss, pf_mlp_backward(actor, grad_mean), pf_mlp_backward(critic, grad_value) on
+ * the same inputs, rows = M and width = actor->out_dim: every clause of pf_ppo_loss and of pf_mlp_forward / pf_mlp_backward above
+ * holds, ZERO ROWS included (an invalid row's x must be finite), and every weight and bias gradient has the bits the composition
+ * gives. Any context. (Added without a new PF_ABI_VERSION: new functions, every existing struct as it was.) What differs:
+ *   - NO mean, value, grad_mean or grad_value tensor exists: a tile's 64 rows of them live in the workgroup's LDS.
+ *   - LAUNCHES. Seven: pf_ppo_loss's two advantage kernels; the backward's tile kernel once per network, with the output layer and
+ *     pf_ppo_loss's per-row float32 sequence in the place of its load of grad_out; the backward's reduction once per network;
+ *     pf_ppo_loss's finish kernel. Enqueued on `stream`, no host synchronisation, no allocation, no copy -- capturable in a HIP graph.
+ *     The advantage block is the context's, shared with pf_ppo_loss: calls of either on one context must not overlap on different
+ *     streams.
+ *   - WORKSPACE. The caller's, 8-byte aligned, at least pf_ppo_grad_workspace_bytes(actor, critic, rows) bytes (a pure host function
+ *     of the two shapes and of rows: it grows with rows up to the grid's cap and is constant from there; 0 for what the call
+ *     refuses). It holds both networks' blocks of partial sums and the rows of double partials behind stats and grad_log_std.
+ *   - THE DOUBLE SUMS behind stats and grad_log_std take the same per-row terms in another order than pf_ppo_loss's (one row of
+ *     partials per workgroup of the tile kernel, at most 256, instead of one per 256-row block, at most 1024): those two outputs
+ *     agree with pf_ppo_loss's within the reordering of a double sum; slots 0, 7, 8, 10 and 11 are the same bits. The order is a
+ *     function of (rows, the two shapes) alone and there are no atomics: the same call gives the same bits on any stream.
+ *   - ERRORS. PF_ERR_ARG, pf_last_error naming the argument: a NULL ctx, argument block, actor, critic, layer's w / b, or any pointer
+ *     other than valid; rows < 1 (or 2^31 - 64 and more); a network shape pf_mlp_backward refuses, in its words after "actor: " or
+ *     "critic: "; critic->out_dim != 1; critic->in_dim != actor->in_dim; pf_ppo_loss's coefficient checks; workspace_bytes too small
+ *     (refused by size, before any launch) or workspace not 8-byte aligned; the workspace or an output overlapping an input or
+ *     one another. */
+typedef struct pf_ppo_grad_args {
+  float clip;                      /* > 0 */
+  float vf_coef, ent_coef;         /* >= 0 */
+  int32_t normalize_advantage;     /* 0 / 1 */
+  const pf_mlp* actor;             /* host pointer; out_dim = A in 1..8 */
+  const pf_mlp* critic;            /* host pointer; out_dim = 1, in_dim = actor->in_dim */
+  const float*   x;                /* [M][in_dim] */
+  const float*   log_std;          /* [A] */
+  const float*   actions;          /* [M][A] */
+  const float*   logp_old;         /* [M] */
+  const float*   advantages;       /* [M] */
+  const float*   returns;          /* [M] */
+  const uint8_t* valid;            /* [M] or NULL(= all 1) */
+  float*  actor_grad_w[3];         /* shaped like the parameters; the first n_layers are used */
+  float*  actor_grad_b[3];
+  float*  critic_grad_w[3];
+  float*  critic_grad_b[3];
+  float*  grad_log_std;            /* [A] */
+  double* stats;                   /* [16], pf_ppo_loss's slots */
+} pf_ppo_grad_args;
+size_t pf_sizeof_ppo_grad(void);
+size_t pf_ppo_grad_workspace_bytes(const pf_mlp* actor, const pf_mlp* critic, int64_t rows);
+int pf_ppo_grad(pf_ctx* ctx, const pf_ppo_grad_args* a, int64_t rows, void* workspace, size_t workspace_bytes, void* stream);
+
 /* The optimiser's step of a PPO epoch: Adam / AdamW with global gradient-norm clipping over a set of 1..PF_ADAM_MAX_TENSORS float32
  * parameter tensors, in two launches. With it an epoch is pf_mlp_forward -> pf_ppo_loss -> pf_mlp_backward -> pf_adam_step and holds
  * nothing but this library's launches. The context serves its device and pf_last_error only: any context works, with an env task or

@@ -23,6 +23,11 @@
 // layer, X (two chunks), h0, h1 and G are 118 KB of the CU's 160 KB, declared statically (gfx950 admits it): one workgroup per CU.
 // The tile constants, the barrier, the accumulator's fill, row map and activation store and the forward's matrix chain are mlp_tile.hpp's,
 // shared with policy_act_kernel; the staging and the row loads are this file's own copies (profiles/mlp_tile/nothing_moved.txt: why).
+//
+// mlp_backward_kernel is a template over its argument block. With MlpK it is pf_mlp_backward's kernel, instruction for instruction what
+// it was as a plain function (profiles/ppo_grad/nothing_moved.txt). With a block derived from MlpK that has a head (ppo_grad.hpp:
+// PpoGradK), step 2 is replaced: the head loads its own row data a tile ahead, and once h_last stands in LDS it computes the output
+// layer and from it the tile's rows of G. Steps 1 and 3 - 6, the running sums and the block of partials are this one text either way.
 #pragma once
 
 namespace pf {
@@ -31,7 +36,11 @@ constexpr int kMlpMaxGrid = 256;       // one workgroup per CU of an MI355X (the
 constexpr int kMlpGS = kActMaxA + 1;   // the row stride of the grad_out tile
 constexpr int kMlpTile = kActRows * kActTS;
 
+struct MlpNone {};
 struct MlpK {
+  typedef MlpNone Rows;
+  typedef MlpNone Sums;
+  static constexpr int kHead = 0;  // the rows of G are the caller's grad_out (ppo_grad.hpp: the heads that compute them in the tile)
   pf_mlp Q;
   const float* x;
   const float* grad_out;
@@ -89,7 +98,10 @@ PF_DEV act_f16v mlp_outer(const float* a, const float* b, const int ca, const in
   return acc;
 }
 
-__global__ void __launch_bounds__(256) mlp_backward_kernel(const MlpK K) {
+// KT: MlpK, or a block derived from it whose head makes the tile's rows of G itself (step 2'; ppo_grad.hpp: PpoGradK)
+template <class KT>
+__global__ void __launch_bounds__(256) mlp_backward_kernel(const KT K) {
+  constexpr int HEAD = KT::kHead;
   __shared__ float W0s[2 * kPolH * kPolH];  // the first layer, two chunks of 64 inputs: [k][(unit + k) & 63]
   __shared__ float W1s[kPolH * kPolH];      // the second layer, likewise
   __shared__ float WOs[kPolH * kActMaxA];   // the output layer [i][c]
@@ -98,6 +110,11 @@ __global__ void __launch_bounds__(256) mlp_backward_kernel(const MlpK K) {
   __shared__ float TH0[kMlpTile];           // h0, then delta0
   __shared__ float TH1[kMlpTile];           // h1, then delta1
   __shared__ float G[kActRows * kMlpGS];    // the rows of grad_out
+  float* HS = nullptr;                      // a head's own LDS: its rows' data and the output bias
+  if constexpr (HEAD != 0) {
+    __shared__ float head_lds[KT::kLdsFloats];
+    HS = head_lds;
+  }
   const int t = (int)threadIdx.x, lane = t & 63, wv = t >> 6;
   const int l31 = lane & 31, h = lane >> 5, mt = wv & 1, nt = wv >> 1;
   const pf_mlp& Q = K.Q;
@@ -150,6 +167,7 @@ __global__ void __launch_bounds__(256) mlp_backward_kernel(const MlpK K) {
     Bs[t] = t < w0 ? Q.b[0][t] : 0.0f;
     Bs[kPolH + t] = (three && t < w1) ? Q.b[1][t] : 0.0f;
   }
+  if constexpr (HEAD != 0) K.stage_head(t, HS);
 
   const int arow = (mt * 32 + l31) * kActTS;     // A operand of a forward-shaped product: this lane's row of a tile
   const int bcol = nt * 32 + l31;                // B operand and C/D: this lane's unit
@@ -164,9 +182,11 @@ __global__ void __launch_bounds__(256) mlp_backward_kernel(const MlpK K) {
   for (int r = 0; r < 16; ++r) gw0[0][r] = gw0[1][r] = gw1[r] = 0.0f;
 
   float xc[2][16], gq[2];  // the next tile's rows, loaded a tile ahead of their use
+  typename KT::Rows hq;    // (a head's rows likewise; its sums for `stats`)
+  typename KT::Sums hsum;
   load_x((int)blockIdx.x, 0, xc[0]);
   load_x((int)blockIdx.x, 1, xc[1]);
-  load_g((int)blockIdx.x, gq);
+  if constexpr (HEAD == 0) load_g((int)blockIdx.x, gq); else K.load_rows((int)blockIdx.x, t, hq);
   __syncthreads();  // the staged weights
   for (int tile = (int)blockIdx.x; tile < ntiles; tile += (int)gridDim.x) {
     act_barrier();  // the previous tile's readers of TX, TH0 and G are done
@@ -176,15 +196,19 @@ __global__ void __launch_bounds__(256) mlp_backward_kernel(const MlpK K) {
 #pragma unroll
         for (int rr = 0; rr < 16; ++rr) TX[ch * kMlpTile + (wv * 16 + rr) * kActTS + lane] = xc[ch][rr];
       }
+    if constexpr (HEAD == 0) {
 #pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const int idx = t + 256 * u;
-      G[(idx / kActMaxA) * kMlpGS + idx % kActMaxA] = gq[u];
+      for (int u = 0; u < 2; ++u) {
+        const int idx = t + 256 * u;
+        G[(idx / kActMaxA) * kMlpGS + idx % kActMaxA] = gq[u];
+      }
+    } else {
+      K.stage_rows(t, hq, HS);
     }
     if (tile + (int)gridDim.x < ntiles) {
       load_x(tile + (int)gridDim.x, 0, xc[0]);
       load_x(tile + (int)gridDim.x, 1, xc[1]);
-      load_g(tile + (int)gridDim.x, gq);
+      if constexpr (HEAD == 0) load_g(tile + (int)gridDim.x, gq); else K.load_rows(tile + (int)gridDim.x, t, hq);
     }
     act_barrier();
 
@@ -203,6 +227,8 @@ __global__ void __launch_bounds__(256) mlp_backward_kernel(const MlpK K) {
       act_store_hidden(Q.activation, acc, TH1 + hpos, h);
       act_barrier();
     }
+    // ---- step 2': a head computes the output layer from h_last and from it the tile's rows of G
+    if constexpr (HEAD != 0) K.make_g(tile, t, TL, WOs, HS, G, hsum);
 
     // ---- the output layer: grad_w = G^T h_last over this wave's half of the rows, grad_b = the column sums of G
     if (32 * nt < hl) {
@@ -316,6 +342,7 @@ __global__ void __launch_bounds__(256) mlp_backward_kernel(const MlpK K) {
     for (int q = 1; q < 8; ++q) s = s + S[1024 + 8 * q + t];
     part[(three ? end[4] : end[2]) + t] = s;
   }
+  if constexpr (HEAD != 0) K.write_sums(t, hsum);
 }
 
 // One thread per parameter: the workgroups' partials in ascending workgroup order, in double

@@ -1,6 +1,7 @@
 // What policy_act_kernel (policy_act.hpp) and mlp_backward_kernel (mlp.hpp) share of the 64-row tile code: the constants, the barrier
-// between phases, the 32x32 accumulator's fill, register-to-row map and activation store, and the matrix chain of a layer -- so the
-// h0 / h1 the backward computes again come from the text the forward runs. Everything is force-inlined. The staging of the weights and
+// between phases, the 32x32 accumulator's fill, register-to-row map and activation store, the matrix chain of a layer and the fmaf
+// chain of a pair of outputs -- so the h0 / h1 the backward computes again, and the means and values the fused heads of ppo_grad.hpp
+// compute in the tile, come from the text the forward runs. Everything is force-inlined. The staging of the weights and
 // biases and the row loads are still written per kernel: each of them, as a shared function, made pf_mlp_backward measurably slower
 // (profiles/mlp_tile/nothing_moved.txt). Layouts: policy_act.hpp's top comment.
 #pragma once
@@ -42,6 +43,17 @@ PF_DEV act_f16v tile_chain(act_f16v acc, const float* arow, const float* W, cons
 PF_DEV void act_store_hidden(const int activation, const act_f16v& acc, float* trow0, const int h) {
 #pragma unroll
   for (int r = 0; r < 16; ++r) trow0[tile_row(r, h) * kActTS] = activation == PF_ACT_RELU ? __builtin_fmaxf(acc[r], 0.0f) : pol_tanh(acc[r]);
+}
+
+// the affine output layer of one row: outputs ca and ca + 1, each from its bias (m0, m1 on entry) over the 64 columns of the row's last
+// hidden layer xr (zero past the layer's width), i ascending, one fmaf each; WOs is the staged [i][c] block
+PF_DEV void tile_out_pair(const float* WOs, const float* xr, const int ca, float& m0, float& m1) {
+#pragma unroll 8
+  for (int i = 0; i < kPolH; ++i) {
+    const float x = xr[i];
+    m0 = fmaf(WOs[i * kActMaxA + ca], x, m0);
+    m1 = fmaf(WOs[i * kActMaxA + ca + 1], x, m1);
+  }
 }
 
 }  // namespace pf

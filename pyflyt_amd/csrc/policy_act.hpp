@@ -21,7 +21,8 @@
 //   * an odd D gets a zero last k-pair (T's column D and the weights' row D are zero): an exact term.
 //   * the output layer (4, 6 or 7 wide) is plain fmaf: lane = row, wave w the outputs 2w and 2w + 1, the weights broadcast from LDS.
 //   * nothing is kept between calls: no packed block in the context, the caller's tensors are read at every call.
-//   * the tile constants, the barrier, the accumulator's fill, row map and activation store and the matrix chain are mlp_tile.hpp's (mlp.hpp runs them too).
+//   * the tile constants, the barrier, the accumulator's fill, row map and activation store, the matrix chain and the output pair's
+//     fmaf chain are mlp_tile.hpp's (mlp.hpp and ppo_grad.hpp run them too).
 #pragma once
 
 namespace pf {
@@ -128,13 +129,7 @@ __global__ void __launch_bounds__(256) policy_act_kernel(const ActK K) {
     const int ca = 2 * wv;
     if (ca < A) {
       float m0 = Bs[2 * kPolH + ca], m1 = Bs[2 * kPolH + ca + 1];
-      const float* xr = T + lane * kActTS;
-#pragma unroll 8
-      for (int i = 0; i < kPolH; ++i) {
-        const float x = xr[i];
-        m0 = fmaf(WOs[i * kActMaxA + ca], x, m0);
-        m1 = fmaf(WOs[i * kActMaxA + ca + 1], x, m1);
-      }
+      tile_out_pair(WOs, T + lane * kActTS, ca, m0, m1);
       const int g = r0 + lane;
       float a0 = m0, a1 = m1;
       if (Q.log_std != nullptr) {

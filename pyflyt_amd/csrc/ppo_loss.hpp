@@ -9,7 +9,8 @@
 //                          1 / max(sigma, 1e-8) that the main kernel applies.
 //   ppo_main_kernel        grid-strided over the rows, U rows per trip: every load of the U rows (mean, action, old log-probability,
 //                          advantage, return, value, validity byte; rows past M re-read row M - 1 and select nothing) is issued,
-//                          unconditionally, before the first value is used. Per row one fixed float32 sequence; the two per-row
+//                          unconditionally, before the first value is used. Per row one fixed float32 sequence (ppo_actor_row and
+//                          ppo_critic_row below, which the fused kernels of ppo_grad.hpp run too); the two per-row
 //                          gradients leave by streaming stores (nobody in this call reads them again); the sums behind `stats` and
 //                          grad_log_std stay per thread in double, are added over the wave by the fixed butterfly of traj_stats.hpp
 //                          and over the block's four waves through LDS in ascending order: one row of partials per block.
@@ -140,6 +141,57 @@ __global__ __launch_bounds__(kPpoBlock) void ppo_adv_finish_kernel(const double*
   }
 }
 
+// The per-row float32 sequence, in two halves that share nothing but `live`: ppo_main_kernel runs both on a row, the fused kernels of
+// ppo_grad.hpp one each (the actor's launch the first, the critic's the second), so a row's gradients are the same bits either way.
+//
+// The actor's half, over the first `width` of W columns (ppo_main_kernel: width = W, known when it is compiled): the row's gradient
+// with respect to its means -> gm, the float32 terms of grad_log_std -> gt, and min(u, v), r and logp - logp_old for the statistics.
+// `cf`: lo_clip, hi_clip, w32, mu32, inv32. Every choice is a select: an invalid row's inputs are used and not chosen
+template <int W>
+PF_DEV void ppo_actor_row(const float (&m)[W], const float (&x)[W], const float (&ls)[W], const float (&inv)[W], const int width, const float lpo,
+                          const float ad, const bool live, const bool norm, const float (&cf)[5], float (&gm)[W], float (&gt)[W], float& surr,
+                          float& r, float& d) {
+  float z[W], logp = 0.0f;
+#pragma unroll
+  for (int c = 0; c < W; ++c) {
+    z[c] = (x[c] - m[c]) * inv[c];
+    logp = c < width ? logp + gae_logp_term(x[c], m[c], ls[c], inv[c]) : logp;
+  }
+  const float adv = norm ? (ad - cf[3]) * cf[4] : ad;
+  d = logp - lpo;
+  r = expf(d);
+  const float su = r * adv;
+  const float sv = fminf(fmaxf(r, cf[0]), cf[1]) * adv;
+  surr = fminf(su, sv);
+  const bool act = live && su <= sv;  // the branch of the minimum that depends on the new policy
+  const float gl = act ? ((-cf[2]) * adv) * r : 0.0f;  // d loss / d logp
+#pragma unroll
+  for (int c = 0; c < W; ++c) {
+    gm[c] = act && c < width ? (gl * z[c]) * inv[c] : 0.0f;
+    gt[c] = act && c < width ? gl * (z[c] * z[c] - 1.0f) : 0.0f;
+  }
+}
+// its terms of the statistics: sum min(u, v), sum (r - 1) - d, the rows with |r - 1| > clip, min r, max r
+PF_DEV void ppo_actor_terms(const bool live, const float surr, const float r, const float d, const float clip, double& s_surr, double& s_kl,
+                            uint32_t& n_clip, float& r_lo, float& r_hi) {
+  s_surr = s_surr + (live ? (double)surr : 0.0);
+  s_kl = s_kl + (live ? (double)((r - 1.0f) - d) : 0.0);
+  n_clip += live && fabsf(r - 1.0f) > clip ? 1u : 0u;
+  r_lo = live ? fminf(r_lo, r) : r_lo;
+  r_hi = live ? fmaxf(r_hi, r) : r_hi;
+}
+// The critic's half: returns the row's gradient with respect to its value, kv = vf_coef * w32; its terms: sum (V - R)^2, sum R,
+// sum R^2, sum (V - R)
+PF_DEV float ppo_critic_row(const float vl, const float rt, const float kv, const bool live, double& s_d2, double& s_r, double& s_r2, double& s_d) {
+  const float dv = vl - rt;
+  const double R = (double)rt, D = (double)dv;
+  s_d2 = s_d2 + (live ? D * D : 0.0);
+  s_r = s_r + (live ? R : 0.0);
+  s_r2 = s_r2 + (live ? R * R : 0.0);
+  s_d = s_d + (live ? D : 0.0);
+  return live ? kv * dv : 0.0f;
+}
+
 // (amdgpu_waves_per_eu(4, 4) and kPpoMaxGrid go together: 1024 blocks of four waves are 16 waves per CU on 256 CUs, four per SIMD, so the
 //  whole grid is resident at once whatever the instantiation; the float4 one needs the cap for its registers, the generic ones just obey it)
 template <int W, bool VEC>
@@ -156,7 +208,7 @@ __global__ __launch_bounds__(kPpoBlock) __attribute__((amdgpu_waves_per_eu(4, 4)
   const double cnt = fin[0];
   const float w32 = cnt > 0.0 ? (float)(1.0 / cnt) : 0.0f;
   const float mu32 = (float)fin[3], inv32 = (float)fin[4];
-  const float lo_clip = 1.0f - a.clip, hi_clip = 1.0f + a.clip, kv = a.vf_coef * w32;
+  const float cf[5] = {1.0f - a.clip, 1.0f + a.clip, w32, mu32, inv32}, kv = a.vf_coef * w32;
   const uint32_t all = a.vmask == 0u ? 1u : 0u;  // (no branch on it: a bit OR-ed into every row's byte)
   const bool norm = a.normalize != 0;
   const size_t stride = (size_t)gridDim.x * kPpoBlock;
@@ -197,28 +249,12 @@ __global__ __launch_bounds__(kPpoBlock) __attribute__((amdgpu_waves_per_eu(4, 4)
       const size_t rw = r0 + (size_t)u * stride;
       const bool in = rw < rows;
       const bool live = in && ((b[u] & a.vmask) | all) != 0u;
-      float z[W], logp = 0.0f;
+      float gm[W], gt[W], surr, r, d;
+      ppo_actor_row<W>(m[u], x[u], ls, inv, W, lpo[u], ad[u], live, norm, cf, gm, gt, surr, r, d);
 #pragma unroll
-      for (int c = 0; c < W; ++c) {
-        z[c] = (x[u][c] - m[u][c]) * inv[c];
-        logp = logp + gae_logp_term(x[u][c], m[u][c], ls[c], inv[c]);
-      }
-      const float adv = norm ? (ad[u] - mu32) * inv32 : ad[u];
-      const float d = logp - lpo[u];
-      const float r = expf(d);
-      const float su = r * adv;
-      const float sv = fminf(fmaxf(r, lo_clip), hi_clip) * adv;
-      const float surr = fminf(su, sv);
-      const bool act = live && su <= sv;  // the branch of the minimum that depends on the new policy
-      const float gl = act ? ((-w32) * adv) * r : 0.0f;  // d loss / d logp
-      const float dv = vl[u] - rt[u];
-      float gm[W];
-#pragma unroll
-      for (int c = 0; c < W; ++c) {
-        gm[c] = act ? (gl * z[c]) * inv[c] : 0.0f;
-        gls[c] = gls[c] + (double)(act ? gl * (z[c] * z[c] - 1.0f) : 0.0f);
-      }
-      const float gv = live ? kv * dv : 0.0f;
+      for (int c = 0; c < W; ++c) gls[c] = gls[c] + (double)gt[c];
+      ppo_actor_terms(live, surr, r, d, a.clip, sum[0], sum[2], n_clip, r_lo, r_hi);
+      const float gv = ppo_critic_row(vl[u], rt[u], kv, live, sum[1], sum[4], sum[5], sum[6]);
       if (in) {
         if constexpr (VEC) {
           ppo_f4 o;
@@ -230,16 +266,6 @@ __global__ __launch_bounds__(kPpoBlock) __attribute__((amdgpu_waves_per_eu(4, 4)
         }
         __builtin_nontemporal_store(gv, a.grad_value + rw);
       }
-      const double R = (double)rt[u], D = (double)dv;
-      sum[0] = sum[0] + (live ? (double)surr : 0.0);
-      sum[1] = sum[1] + (live ? D * D : 0.0);
-      sum[2] = sum[2] + (live ? (double)((r - 1.0f) - d) : 0.0);
-      n_clip += live && fabsf(r - 1.0f) > a.clip ? 1u : 0u;
-      sum[4] = sum[4] + (live ? R : 0.0);
-      sum[5] = sum[5] + (live ? R * R : 0.0);
-      sum[6] = sum[6] + (live ? D : 0.0);
-      r_lo = live ? fminf(r_lo, r) : r_lo;
-      r_hi = live ? fmaxf(r_hi, r) : r_hi;
     }
   }
   sum[3] = (double)n_clip;

@@ -728,6 +728,7 @@ __global__ void __launch_bounds__(256) sample_actions_kernel(const pf_params P, 
 #include "mlp_tile.hpp"
 #include "policy_act.hpp"
 #include "mlp.hpp"
+#include "ppo_grad.hpp"
 #include "adam.hpp"
 #include "world_sync.hpp"
 
@@ -970,6 +971,7 @@ size_t pf_sizeof_gae(void) { return sizeof(pf_gae_args); }
 size_t pf_sizeof_traj_stats(void) { return sizeof(pf_traj_stats_args); }
 size_t pf_sizeof_ppo_loss(void) { return sizeof(pf_ppo_loss_args); }
 size_t pf_sizeof_mlp(void) { return sizeof(pf_mlp); }
+size_t pf_sizeof_ppo_grad(void) { return sizeof(pf_ppo_grad_args); }
 size_t pf_sizeof_adam(void) { return sizeof(pf_adam_args); }
 size_t pf_sizeof_world_sync(void) { return sizeof(pf_world_sync_args); }
 const char* pf_last_error(const pf_ctx* ctx) { return ctx ? ctx->err : g_err; }
@@ -1269,10 +1271,10 @@ struct arg_span {
   const void* p;
   size_t bytes;
 };
-// the first pair of spans that share a byte, or null
-static const char* spans_overlap(const arg_span* s, int count, char* buf, size_t len) {
+// the first pair of spans that share a byte, or null; the spans before `first_written` are only read and may share bytes with one another
+static const char* spans_overlap(const arg_span* s, int count, char* buf, size_t len, int first_written = 0) {
   for (int i = 0; i < count; ++i)
-    for (int j = i + 1; j < count; ++j) {
+    for (int j = i + 1 > first_written ? i + 1 : first_written; j < count; ++j) {
       const uintptr_t a = (uintptr_t)s[i].p, b = (uintptr_t)s[j].p;
       if (a < b + s[j].bytes && b < a + s[i].bytes) {
         snprintf(buf, len, "%s and %s overlap", s[i].name, s[j].name);
@@ -1434,6 +1436,14 @@ int pf_traj_stats(pf_ctx* ctx, const pf_traj_stats_args* a, int k_steps, void* s
   PF_HIP(ctx, hipGetLastError());
   return PF_OK;
 }
+// what pf_ppo_loss and pf_ppo_grad check of the loss's coefficients
+static int ppo_coef_check(pf_ctx* ctx, const char* who, float clip, float vf_coef, float ent_coef, int32_t normalize_advantage) {
+  if (!(clip > 0.0f && clip < INFINITY)) return arg_fail(ctx, who, "clip must be finite and > 0");
+  if (!(vf_coef >= 0.0f && vf_coef < INFINITY)) return arg_fail(ctx, who, "vf_coef must be finite and >= 0");
+  if (!(ent_coef >= 0.0f && ent_coef < INFINITY)) return arg_fail(ctx, who, "ent_coef must be finite and >= 0");
+  if (normalize_advantage != 0 && normalize_advantage != 1) return arg_fail(ctx, who, "normalize_advantage must be 0 or 1");
+  return PF_OK;
+}
 int pf_ppo_loss(pf_ctx* ctx, const pf_ppo_loss_args* a, size_t rows, int width, void* stream) {
   if (!ctx || !a) return fail(ctx, PF_ERR_ARG, "pf_ppo_loss: ctx and the argument block are required");
   if (rows < 1) return fail(ctx, PF_ERR_ARG, "pf_ppo_loss: rows must be >= 1");
@@ -1442,10 +1452,7 @@ int pf_ppo_loss(pf_ctx* ctx, const pf_ppo_loss_args* a, size_t rows, int width, 
                               {"advantages", a->advantages}, {"returns", a->returns}, {"value", a->value}, {"grad_mean", a->grad_mean},
                               {"grad_value", a->grad_value}, {"grad_log_std", a->grad_log_std}, {"stats", a->stats}, {nullptr, nullptr}};
   if (int rc = require_args(ctx, "pf_ppo_loss", required)) return rc;
-  if (!(a->clip > 0.0f && a->clip < INFINITY)) return fail(ctx, PF_ERR_ARG, "pf_ppo_loss: clip must be finite and > 0");
-  if (!(a->vf_coef >= 0.0f && a->vf_coef < INFINITY)) return fail(ctx, PF_ERR_ARG, "pf_ppo_loss: vf_coef must be finite and >= 0");
-  if (!(a->ent_coef >= 0.0f && a->ent_coef < INFINITY)) return fail(ctx, PF_ERR_ARG, "pf_ppo_loss: ent_coef must be finite and >= 0");
-  if (a->normalize_advantage != 0 && a->normalize_advantage != 1) return fail(ctx, PF_ERR_ARG, "pf_ppo_loss: normalize_advantage must be 0 or 1");
+  if (int rc = ppo_coef_check(ctx, "pf_ppo_loss", a->clip, a->vf_coef, a->ent_coef, a->normalize_advantage)) return rc;
   int rc = ensure_device(ctx);
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
@@ -1566,7 +1573,7 @@ int pf_mlp_backward(pf_ctx* ctx, const pf_mlp* q, const float* x, const float* g
   hipStream_t s = (hipStream_t)stream;
   const int grid = pf::mlp_grid(rows);
   const pf::MlpK K{*q, x, grad_out, (float*)workspace, (int)rows};
-  hipLaunchKernelGGL(pf::mlp_backward_kernel, dim3(grid), dim3(256), 0, s, K);
+  hipLaunchKernelGGL(pf::mlp_backward_kernel<pf::MlpK>, dim3(grid), dim3(256), 0, s, K);
   pf::MlpOutK O;
   const int P = pf::mlp_param_count(*q, O.end);
   for (int l = 0; l < 3; ++l) {
@@ -1574,6 +1581,114 @@ int pf_mlp_backward(pf_ctx* ctx, const pf_mlp* q, const float* x, const float* g
     O.p[2 * l + 1] = l < q->n_layers ? grad_b[l] : nullptr;
   }
   hipLaunchKernelGGL(pf::mlp_reduce_kernel, dim3((P + 255) / 256), dim3(256), 0, s, (const float*)workspace, grid, P, O);
+  PF_HIP(ctx, hipGetLastError());
+  return PF_OK;
+}
+// pf_ppo_grad: the shape checks of the two networks; null, or the refusal with the network named (buf holds it)
+static const char* ppo_grad_shape_error(const pf_mlp* actor, const pf_mlp* critic, char* buf, size_t len) {
+  if (const char* e = mlp_shape_error(actor)) {
+    snprintf(buf, len, "actor: %s", e);
+    return buf;
+  }
+  if (const char* e = mlp_shape_error(critic)) {
+    snprintf(buf, len, "critic: %s", e);
+    return buf;
+  }
+  if (critic->out_dim != 1) return "critic: out_dim must be 1";
+  if (critic->in_dim != actor->in_dim) return "critic: in_dim must equal the actor's in_dim (both read x)";
+  return nullptr;
+}
+size_t pf_ppo_grad_workspace_bytes(const pf_mlp* actor, const pf_mlp* critic, int64_t rows) {
+  char buf[160];
+  if (!actor || !critic || ppo_grad_shape_error(actor, critic, buf, sizeof(buf)) || rows < 1) return 0;
+  const int grid = pf::mlp_grid(rows);
+  return pf::ppo_grad_stat_bytes(grid) + sizeof(float) * (size_t)grid * ((size_t)pf::mlp_param_count(*actor, nullptr) + (size_t)pf::mlp_param_count(*critic, nullptr));
+}
+int pf_ppo_grad(pf_ctx* ctx, const pf_ppo_grad_args* a, int64_t rows, void* workspace, size_t workspace_bytes, void* stream) {
+  static const char* who = "pf_ppo_grad";
+  if (!ctx) return arg_fail(ctx, who, "ctx is required");
+  if (!a) return arg_fail(ctx, who, "the argument block is required");
+  if (!a->actor) return arg_fail(ctx, who, "actor is required");
+  if (!a->critic) return arg_fail(ctx, who, "critic is required");
+  char buf[160];
+  if (const char* e = ppo_grad_shape_error(a->actor, a->critic, buf, sizeof(buf))) return arg_fail(ctx, who, e);
+  const pf_mlp* nets[2] = {a->actor, a->critic};
+  for (int k = 0; k < 2; ++k)
+    for (int l = 0; l < nets[k]->n_layers; ++l)
+      if (!nets[k]->w[l] || !nets[k]->b[l]) return arg_fail(ctx, who, k == 0 ? "actor: w / b: every layer needs w and b" : "critic: w / b: every layer needs w and b");
+  if (rows < 1) return arg_fail(ctx, who, "rows must be >= 1");
+  if (rows > (int64_t)INT32_MAX - pf::kActRows) return arg_fail(ctx, who, "rows must be below 2^31 - 64 (the kernels index rows with 32 bits)");
+  const arg_ptr required[] = {{"x", a->x}, {"log_std", a->log_std}, {"actions", a->actions}, {"logp_old", a->logp_old}, {"advantages", a->advantages},
+                              {"returns", a->returns}, {"grad_log_std", a->grad_log_std}, {"stats", a->stats}, {"workspace", workspace}, {nullptr, nullptr}};
+  if (int rc = require_args(ctx, who, required)) return rc;
+  static const char* const gn[2][2][3] = {{{"actor_grad_w[0]", "actor_grad_w[1]", "actor_grad_w[2]"}, {"actor_grad_b[0]", "actor_grad_b[1]", "actor_grad_b[2]"}},
+                                          {{"critic_grad_w[0]", "critic_grad_w[1]", "critic_grad_w[2]"}, {"critic_grad_b[0]", "critic_grad_b[1]", "critic_grad_b[2]"}}};
+  float* const* gw[2] = {a->actor_grad_w, a->critic_grad_w};
+  float* const* gb[2] = {a->actor_grad_b, a->critic_grad_b};
+  for (int k = 0; k < 2; ++k)
+    for (int l = 0; l < nets[k]->n_layers; ++l) {
+      const arg_ptr outs[] = {{gn[k][0][l], gw[k][l]}, {gn[k][1][l], gb[k][l]}, {nullptr, nullptr}};
+      if (int rc = require_args(ctx, who, outs)) return rc;
+    }
+  if (int rc = ppo_coef_check(ctx, who, a->clip, a->vf_coef, a->ent_coef, a->normalize_advantage)) return rc;
+  const size_t need = pf_ppo_grad_workspace_bytes(a->actor, a->critic, rows);
+  if (workspace_bytes < need) return arg_fail(ctx, who, "workspace_bytes is below pf_ppo_grad_workspace_bytes(actor, critic, rows)");
+  if (((uintptr_t)workspace & 7) != 0) return arg_fail(ctx, who, "workspace must be 8-byte aligned (it holds rows of double partial sums)");
+  const size_t M = (size_t)rows, A = (size_t)a->actor->out_dim;
+  arg_span spans[7 + 15];
+  int ns = 0;
+  spans[ns++] = {"x", a->x, sizeof(float) * M * a->actor->in_dim};
+  spans[ns++] = {"log_std", a->log_std, sizeof(float) * A};
+  spans[ns++] = {"actions", a->actions, sizeof(float) * M * A};
+  spans[ns++] = {"logp_old", a->logp_old, sizeof(float) * M};
+  spans[ns++] = {"advantages", a->advantages, sizeof(float) * M};
+  spans[ns++] = {"returns", a->returns, sizeof(float) * M};
+  if (a->valid) spans[ns++] = {"valid", a->valid, M};
+  const int n_read = ns;
+  spans[ns++] = {"workspace", workspace, need};
+  spans[ns++] = {"grad_log_std", a->grad_log_std, sizeof(float) * A};
+  spans[ns++] = {"stats", a->stats, sizeof(double) * 16};
+  for (int k = 0; k < 2; ++k)
+    for (int l = 0; l < nets[k]->n_layers; ++l) {
+      const pf_mlp* q = nets[k];
+      const size_t n_in = l == 0 ? q->in_dim : q->width[l - 1], n_out = l + 1 == q->n_layers ? q->out_dim : q->width[l];
+      spans[ns++] = {gn[k][0][l], gw[k][l], sizeof(float) * n_in * n_out};
+      spans[ns++] = {gn[k][1][l], gb[k][l], sizeof(float) * n_out};
+    }
+  if (const char* e = spans_overlap(spans, ns, buf, sizeof(buf), n_read)) return arg_fail(ctx, who, e);
+  int rc = ensure_device(ctx);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  double* adv_part = ctx->ppo_scratch + pf::kPpoAdvOffset;
+  double* fin = ctx->ppo_scratch + pf::kPpoFinOffset;
+  // (no valid: the byte loads read the advantages' first M bytes and the mask drops them)
+  const uint8_t* vbytes = a->valid ? a->valid : reinterpret_cast<const uint8_t*>(a->advantages);
+  const uint32_t vmask = a->valid ? 0xFFu : 0u;
+  const unsigned adv_grid = pf::ppo_grid(M);
+  hipLaunchKernelGGL(pf::ppo_adv_kernel, dim3(adv_grid), dim3(pf::kPpoBlock), 0, s, a->advantages, vbytes, vmask, M, adv_part);
+  hipLaunchKernelGGL(pf::ppo_adv_finish_kernel, dim3(1), dim3(pf::kPpoBlock), 0, s, adv_part, (int)adv_grid, fin);
+  const int grid = pf::mlp_grid(rows);
+  double* stat_part = (double*)workspace;
+  float* part[2];
+  part[0] = (float*)((char*)workspace + pf::ppo_grad_stat_bytes(grid));
+  part[1] = part[0] + (size_t)grid * (size_t)pf::mlp_param_count(*a->actor, nullptr);
+  const pf::PpoGradK<pf::kGradActor> KA{pf::MlpK{*a->actor, a->x, nullptr, part[0], (int)rows}, a->clip, a->vf_coef, a->normalize_advantage, a->log_std, a->actions,
+                                        a->logp_old, a->advantages, a->returns, vbytes, vmask, fin, stat_part};
+  const pf::PpoGradK<pf::kGradCritic> KC{pf::MlpK{*a->critic, a->x, nullptr, part[1], (int)rows}, a->clip, a->vf_coef, a->normalize_advantage, a->log_std, a->actions,
+                                         a->logp_old, a->advantages, a->returns, vbytes, vmask, fin, stat_part};
+  hipLaunchKernelGGL(pf::mlp_backward_kernel<pf::PpoGradK<pf::kGradActor>>, dim3(grid), dim3(256), 0, s, KA);
+  hipLaunchKernelGGL(pf::mlp_backward_kernel<pf::PpoGradK<pf::kGradCritic>>, dim3(grid), dim3(256), 0, s, KC);
+  for (int k = 0; k < 2; ++k) {
+    pf::MlpOutK O;
+    const int P = pf::mlp_param_count(*nets[k], O.end);
+    for (int l = 0; l < 3; ++l) {
+      O.p[2 * l] = l < nets[k]->n_layers ? gw[k][l] : nullptr;
+      O.p[2 * l + 1] = l < nets[k]->n_layers ? gb[k][l] : nullptr;
+    }
+    hipLaunchKernelGGL(pf::mlp_reduce_kernel, dim3((P + 255) / 256), dim3(256), 0, s, (const float*)part[k], grid, P, O);
+  }
+  hipLaunchKernelGGL(pf::ppo_finish_kernel, dim3(1), dim3(pf::kPpoBlock), 0, s, (const double*)stat_part, grid, (const double*)fin, a->log_std, (int)A, a->vf_coef,
+                     a->ent_coef, a->stats, a->grad_log_std);
   PF_HIP(ctx, hipGetLastError());
   return PF_OK;
 }

@@ -31,6 +31,41 @@ class _Mlp(torch.autograd.Function):
         return (None, None, None, *flat)
 
 
+def parse_net(net, activation=None, name="net"):
+    """(layers [(weight, bias), ...], "tanh" / "relu") of what mlp and ppo_grad accept as a network: a torch.nn.Sequential of Linear
+    layers with one kind of activation between them, or a list of (weight, bias) together with `activation`."""
+    nn = torch.nn
+    if isinstance(net, nn.Sequential):
+        mods = list(net)
+        if len(mods) % 2 == 0:
+            raise ValueError(f"{name}: the Sequential must end with a Linear (the output layer is affine)")
+        layers, acts = [], set()
+        for i, m in enumerate(mods):
+            if i % 2 == 0:
+                if not isinstance(m, nn.Linear) or m.bias is None:
+                    raise ValueError(f"{name}: module {i} must be a Linear with a bias, got {type(m).__name__}")
+                layers.append((m.weight, m.bias))
+            elif isinstance(m, (nn.Tanh, nn.ReLU)):
+                acts.add("tanh" if isinstance(m, nn.Tanh) else "relu")
+            else:
+                raise ValueError(f"{name}: module {i} must be a Tanh or a ReLU, got {type(m).__name__}")
+        if len(acts) > 1:
+            raise ValueError(f"{name}: one kind of activation per network (Tanh or ReLU), got both")
+        if activation is not None and acts and activation not in acts:
+            raise ValueError(f"activation={activation!r} contradicts the Sequential's modules")
+        activation = acts.pop() if acts else (activation or "tanh")
+    else:
+        try:
+            layers = [tuple(l) for l in net]
+        except TypeError:
+            raise ValueError(f"{name} must be a torch.nn.Sequential or a list of (weight, bias), got {type(net).__name__}") from None
+        if activation is None:
+            raise ValueError("a list of (weight, bias) comes with activation='tanh' or 'relu'")
+    if any(len(l) != 2 for l in layers):
+        raise ValueError(f"{name}: every layer is a (weight, bias) pair")
+    return layers, activation
+
+
 def mlp(env_or_engine, x, net, activation=None):
     """out = mlp(env, x, net): `net` on the rows of x [..., in_dim] -> [..., out_dim], on the device's matrix units without a GEMM
     library, differentiable with respect to the network's PARAMETERS. `net` is a torch.nn.Sequential of the shape
@@ -44,35 +79,7 @@ def mlp(env_or_engine, x, net, activation=None):
     engine = getattr(env_or_engine, "engine", env_or_engine)
     if not hasattr(engine, "mlp_forward"):
         raise ValueError(f"the first argument must be a vector env or a BatchEngine, got {type(env_or_engine).__name__}")
-    nn = torch.nn
-    if isinstance(net, nn.Sequential):
-        mods = list(net)
-        if len(mods) % 2 == 0:
-            raise ValueError("net: the Sequential must end with a Linear (the output layer is affine)")
-        layers, acts = [], set()
-        for i, m in enumerate(mods):
-            if i % 2 == 0:
-                if not isinstance(m, nn.Linear) or m.bias is None:
-                    raise ValueError(f"net: module {i} must be a Linear with a bias, got {type(m).__name__}")
-                layers.append((m.weight, m.bias))
-            elif isinstance(m, (nn.Tanh, nn.ReLU)):
-                acts.add("tanh" if isinstance(m, nn.Tanh) else "relu")
-            else:
-                raise ValueError(f"net: module {i} must be a Tanh or a ReLU, got {type(m).__name__}")
-        if len(acts) > 1:
-            raise ValueError("net: one kind of activation per network (Tanh or ReLU), got both")
-        if activation is not None and acts and activation not in acts:
-            raise ValueError(f"activation={activation!r} contradicts the Sequential's modules")
-        activation = acts.pop() if acts else (activation or "tanh")
-    else:
-        try:
-            layers = [tuple(l) for l in net]
-        except TypeError:
-            raise ValueError(f"net must be a torch.nn.Sequential or a list of (weight, bias), got {type(net).__name__}") from None
-        if activation is None:
-            raise ValueError("a list of (weight, bias) comes with activation='tanh' or 'relu'")
-    if any(len(l) != 2 for l in layers):
-        raise ValueError("net: every layer is a (weight, bias) pair")
+    layers, activation = parse_net(net, activation)
     if not torch.is_tensor(x):
         raise ValueError(f"x must be a float32 tensor of shape (..., in_dim), got {type(x).__name__}")
     if x.requires_grad:

@@ -34,6 +34,22 @@ class _PpoLoss(torch.autograd.Function):
                 gv.view(ctx.shapes[1]) * grad_loss if need[2] else None, None, None, None, None, None, None, None)
 
 
+def _batch_tensors(batch, valid):
+    """(actions, logp_old, advantages, returns, valid, from_dict) of ppo_loss's and ppo_grad's `*batch`: the dict env.collect
+    returned, or the four tensors."""
+    if len(batch) == 1 and isinstance(batch[0], dict):
+        b = batch[0]
+        missing = [k for k in ("actions", "logp", "advantages", "returns") if b.get(k) is None]
+        if missing:
+            raise ValueError(f"the batch lacks {missing} (env.collect returns logp only for a policy with a log_std)")
+        if valid is not None:
+            raise ValueError("valid comes from the batch dict; give it only with explicit tensors")
+        return b["actions"], b["logp"], b["advantages"], b["returns"], b.get("valid"), True
+    if len(batch) == 4:
+        return (*batch, valid, False)
+    raise ValueError("give the dict env.collect returned, or the four tensors actions, logp_old, advantages, returns")
+
+
 def ppo_loss(env_or_engine, mean, log_std, value, *batch, valid=None, clip: float = 0.2, vf_coef: float = 0.5, ent_coef: float = 0.0,
              normalize_advantage: bool = True):
     """loss, stats = ppo_loss(env, actor(obs), log_std, critic(obs), batch) with `batch` the dict env.collect returned (its actions,
@@ -48,21 +64,60 @@ def ppo_loss(env_or_engine, mean, log_std, value, *batch, valid=None, clip: floa
     engine = getattr(env_or_engine, "engine", env_or_engine)
     if not hasattr(engine, "ppo_loss"):
         raise ValueError(f"the first argument must be a vector env or a BatchEngine, got {type(env_or_engine).__name__}")
-    if len(batch) == 1 and isinstance(batch[0], dict):
-        b = batch[0]
-        missing = [k for k in ("actions", "logp", "advantages", "returns") if b.get(k) is None]
-        if missing:
-            raise ValueError(f"the batch lacks {missing} (env.collect returns logp only for a policy with a log_std)")
-        if valid is not None:
-            raise ValueError("valid comes from the batch dict; give it only with explicit tensors")
-        actions, logp_old, advantages, returns, valid = b["actions"], b["logp"], b["advantages"], b["returns"], b.get("valid")
+    actions, logp_old, advantages, returns, valid, from_dict = _batch_tensors(batch, valid)
+    if from_dict:
         mean, value = mean.reshape(actions.shape), value.reshape(advantages.shape)  # ([k n, A] and [k n, 1] from the networks)
-    elif len(batch) == 4:
-        actions, logp_old, advantages, returns = batch
-    else:
-        raise ValueError("give the dict env.collect returned, or the four tensors actions, logp_old, advantages, returns")
     coefficients = dict(clip=clip, vf_coef=vf_coef, ent_coef=ent_coef, normalize_advantage=normalize_advantage)
     return _PpoLoss.apply(mean, log_std, value, engine, actions, logp_old, advantages, returns, valid, coefficients)
+
+
+def ppo_grad(env_or_engine, x, actor, critic, log_std, *batch, valid=None, clip: float = 0.2, vf_coef: float = 0.5, ent_coef: float = 0.0,
+             normalize_advantage: bool = True, activation=None):
+    """stats = ppo_grad(env, x, actor, critic, log_std, batch): one epoch's gradients in one call (pf_ppo_grad). What
+    `ppo_loss(env, mlp(env, x, actor), log_std, mlp(env, x, critic), batch)[0].backward()` leaves in .grad, the network gradients bit
+    for bit, without the mean, value and their gradient tensors and without the two forward passes: the tile kernel of the backward
+    computes the output layer and the loss's per-row gradients where it used to load them. `actor` and `critic` are what
+    pyflyt_amd.mlp accepts (a torch.nn.Sequential, or a list of (weight, bias) with activation=); the critic is one wide; `batch` is
+    the dict env.collect returned (flattened and used whole; x then holds its k n rows) or the four tensors actions, logp_old,
+    advantages, returns with valid=.
+
+    The gradients are ADDED into .grad of every parameter of the two networks and of log_std (assigned, as copies of the engine's
+    tensors, where .grad is None), as loss.backward() does; parameters with requires_grad False are left alone. There is no autograd
+    graph and no loss tensor: `stats` is the [16] float64 device tensor of pf_ppo_loss (a copy; ppo_stats_dict names it, slot 1 is
+    the loss). x gets no gradient and an x with requires_grad raises ValueError. Nothing synchronises with the host."""
+    from .nets import parse_net
+
+    engine = getattr(env_or_engine, "engine", env_or_engine)
+    if not hasattr(engine, "ppo_grad"):
+        raise ValueError(f"the first argument must be a vector env or a BatchEngine, got {type(env_or_engine).__name__}")
+    a_layers, a_act = parse_net(actor, activation, "actor")
+    c_layers, c_act = parse_net(critic, activation, "critic")
+    if not torch.is_tensor(x):
+        raise ValueError(f"x must be a float32 tensor of shape (..., in_dim), got {type(x).__name__}")
+    if x.requires_grad:
+        raise ValueError("pyflyt_amd.ppo_grad produces no gradient for x (pf_ppo_grad differentiates the parameters only), and x requires one: "
+                         "pass x.detach(), or use torch modules where the input's gradient is needed")
+    if not torch.is_tensor(log_std):
+        raise ValueError(f"log_std must be a float32 tensor of shape (A,), got {type(log_std).__name__}")
+    actions, logp_old, advantages, returns, valid, from_dict = _batch_tensors(batch, valid)
+    if from_dict:  # ([k, n, ...] from collect: the rows of x in the same order)
+        A = actions.shape[-1]
+        actions, logp_old, advantages, returns = actions.reshape(-1, A), logp_old.reshape(-1), advantages.reshape(-1), returns.reshape(-1)
+        valid = None if valid is None else valid.reshape(-1)
+        x = x.reshape(-1, x.shape[-1])
+    detached = [[(w.detach(), b.detach()) for w, b in layers] for layers in (a_layers, c_layers)]
+    ga, gc, gls, stats = engine.ppo_grad(x, detached[0], detached[1], log_std.detach(), actions, logp_old, advantages, returns, valid=valid, clip=clip,
+                                         vf_coef=vf_coef, ent_coef=ent_coef, normalize_advantage=normalize_advantage, actor_activation=a_act,
+                                         critic_activation=c_act)
+    pairs = [(p, g) for layers, grads in ((a_layers, ga), (c_layers, gc)) for lp, lg in zip(layers, grads) for p, g in zip(lp, lg)] + [(log_std, gls)]
+    for p, g in pairs:  # (the engine owns its tensors and overwrites them at the next call: .grad gets copies, a few KB)
+        if not p.requires_grad:
+            continue
+        if p.grad is None:
+            p.grad = g.clone()
+        else:
+            p.grad.add_(g)
+    return stats.clone()
 
 
 def ppo_stats_dict(stats):

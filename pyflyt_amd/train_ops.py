@@ -33,6 +33,7 @@ class TrainOps:
     _ppo_out = None   # dict: ppo_loss()'s gradients for the last (M, A), stats, and the count of calls
     _mlp_fwd = None   # {(rows, out_dim): mlp_forward()'s output}
     _mlp_bwd = None   # {(rows, layer shapes): mlp_backward()'s gradients, pointer arrays and workspace}
+    _ppo_grad = None  # {(rows, both networks' layer shapes): ppo_grad()'s gradients, argument block and workspace}; "stats": its [16] block
     _adam = None      # {addresses: adam_step()'s filled argument block}, the 64 most recent
     _adam_ws = None   # {total elements: adam_step()'s workspace}
     _world_done = None  # [n] uint8: world_sync's latch as the world rollouts keep it (BatchEngine.world_done)
@@ -182,6 +183,16 @@ class TrainOps:
         return (ts["episode_return"] if store_steps else None), (ts["episode_length"] if store_steps else None), ts["summary"]
 
     # ------------------------------------------------------------------ the loss
+    @staticmethod
+    def _ppo_coefficients(clip, vf_coef, ent_coef, normalize_advantage):
+        """What ppo_loss and ppo_grad ask of the loss's coefficients."""
+        for name, x in (("clip", clip), ("vf_coef", vf_coef), ("ent_coef", ent_coef)):
+            K.number(x, name)
+        K.boolean(normalize_advantage, "normalize_advantage")
+        K.positive(clip, "clip")
+        K.non_negative(vf_coef, "vf_coef")
+        K.non_negative(ent_coef, "ent_coef")
+
     def ppo_loss(self, mean, log_std, value, actions, logp_old, advantages, returns, valid=None, clip: float = 0.2, vf_coef: float = 0.5,
                  ent_coef: float = 0.0, normalize_advantage: bool = True):
         """pf_ppo_loss: the clipped PPO objective of a diagonal-Gaussian policy, its statistics and its gradients with respect to
@@ -203,12 +214,7 @@ class TrainOps:
                                         ("returns", returns, rows, f32), ("valid", valid, rows, K.FLAGS)):
             if name != "valid" or x is not None:
                 K.tensor(self.device, x, name, shapes, dtypes, required="{name} is required: a tensor of shape {shape}")
-        for name, x in (("clip", clip), ("vf_coef", vf_coef), ("ent_coef", ent_coef)):
-            K.number(x, name)
-        K.boolean(normalize_advantage, "normalize_advantage")
-        K.positive(clip, "clip")
-        K.non_negative(vf_coef, "vf_coef")
-        K.non_negative(ent_coef, "ent_coef")
+        self._ppo_coefficients(clip, vf_coef, ent_coef, normalize_advantage)
         o = self._lazy("_ppo_out", lambda: dict(M=0, A=0, stats=torch.zeros(16, dtype=torch.float64, device=self.device), calls=0))
         if o["M"] != M or o["A"] != A:
             kw = dict(dtype=torch.float32, device=self.device)
@@ -301,6 +307,51 @@ class TrainOps:
             o = cache[key] = dict(grads=grads, gw=gw, gb=gb, bytes=nbytes, workspace=torch.empty((nbytes + 3) // 4, **kw))
         self._launch(self.lib.pf_mlp_backward, C.byref(q), _ptr(x), _ptr(grad_out), rows, o["gw"], o["gb"], _ptr(o["workspace"]), o["bytes"])
         return o["grads"]
+
+    def ppo_grad(self, x, actor, critic, log_std, actions, logp_old, advantages, returns, valid=None, clip: float = 0.2, vf_coef: float = 0.5,
+                 ent_coef: float = 0.0, normalize_advantage: bool = True, actor_activation="tanh", critic_activation="tanh"):
+        """pf_ppo_grad: what mlp_forward(actor), mlp_forward(critic), ppo_loss, mlp_backward(actor), mlp_backward(critic) give on the
+        rows of x [..., in_dim], without the mean, value, grad_mean and grad_value tensors between them (include/pyflyt_amd.h has the
+        semantics). actor, critic: [(weight, bias), ...] as for mlp_forward, the critic one wide and on the same in_dim; actions
+        [..., A]; logp_old, advantages, returns [...] (a trailing axis of 1 is accepted); valid [...] bool / uint8 or None. Returns
+        (actor_grads, critic_grads, grad_log_std [A], stats [16] float64), the first two [(grad_weight, grad_bias), ...]: tensors the
+        engine owns, overwritten by the next call with the same rows and layer shapes (stats by every call); so is the workspace."""
+        qa, rows, dims_a = self._mlp_block(x, actor, actor_activation)
+        qc, _, dims_c = self._mlp_block(x, critic, critic_activation)
+        A = dims_a[-1][0]
+        if dims_c[-1][0] != 1:
+            raise ValueError(f"the critic's last layer must be 1 wide, got {dims_c[-1][0]}")
+        lead = tuple(x.shape[:-1])
+        f32, per_row = (torch.float32,), (lead, lead + (1,), (rows,), (rows, 1))
+        for name, t, shapes, dtypes in (("log_std", log_std, ((A,),), f32), ("actions", actions, (lead + (A,), (rows, A)), f32),
+                                        ("logp_old", logp_old, per_row, f32), ("advantages", advantages, per_row, f32),
+                                        ("returns", returns, per_row, f32), ("valid", valid, per_row, K.FLAGS)):
+            if name != "valid" or t is not None:
+                K.tensor(self.device, t, name, shapes, dtypes, required="{name} is required: a tensor of shape {shape}")
+        self._ppo_coefficients(clip, vf_coef, ent_coef, normalize_advantage)
+        cache = self._lazy("_ppo_grad", lambda: dict(stats=torch.zeros(16, dtype=torch.float64, device=self.device)))
+        key = (rows, tuple(dims_a), tuple(dims_c))
+        o = cache.get(key)
+        if o is None:
+            kw = dict(dtype=torch.float32, device=self.device)
+            nbytes = int(self.lib.pf_ppo_grad_workspace_bytes(C.byref(qa), C.byref(qc), rows))
+            if nbytes < 1:
+                raise L.PyFlytAmdError("pf_ppo_grad_workspace_bytes refused the networks' shapes")
+            a = L.PfPpoGradArgs()
+            grads = [[(torch.empty(n_out, n_in, **kw), torch.empty(n_out, **kw)) for n_out, n_in in dims] for dims in (dims_a, dims_c)]
+            for gw, gb, net in ((a.actor_grad_w, a.actor_grad_b, grads[0]), (a.critic_grad_w, a.critic_grad_b, grads[1])):
+                for l, (w, b) in enumerate(net):
+                    gw[l], gb[l] = w.data_ptr(), b.data_ptr()
+            gls = torch.empty(A, **kw)
+            a.grad_log_std, a.stats = gls.data_ptr(), cache["stats"].data_ptr()
+            o = cache[key] = dict(args=a, grads=grads, grad_log_std=gls, bytes=nbytes, workspace=torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=self.device))
+        a = o["args"]
+        a.clip, a.vf_coef, a.ent_coef, a.normalize_advantage = float(clip), float(vf_coef), float(ent_coef), int(normalize_advantage)
+        a.actor, a.critic = C.addressof(qa), C.addressof(qc)
+        a.x, a.log_std, a.actions, a.logp_old = _ptr(x), _ptr(log_std), _ptr(actions), _ptr(logp_old)
+        a.advantages, a.returns, a.valid = _ptr(advantages), _ptr(returns), _ptr(valid)
+        self._launch(self.lib.pf_ppo_grad, C.byref(a), rows, _ptr(o["workspace"]), o["bytes"])
+        return o["grads"][0], o["grads"][1], o["grad_log_std"], cache["stats"]
 
     # ------------------------------------------------------------------ the optimiser
     def adam_step(self, params, grads, exp_avg, exp_avg_sq, state, *, lr=3e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
