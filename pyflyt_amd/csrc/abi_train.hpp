@@ -1,0 +1,456 @@
+// abi_train.hpp -- the C ABI's training side: pf_policy_act, pf_gae, pf_traj_stats, pf_ppo_loss, pf_mlp_forward / pf_mlp_backward, pf_ppo_grad,
+// pf_adam_step and pf_world_sync, each behind the checks and launches it shares with another. Host code.
+#pragma once
+#include <cmath>
+
+#include "abi_ctx.hpp"  // (with the HIP runtime)
+#include "rocket_landing.hpp"  // kRlActionDim
+#include "gae.hpp"
+#include "traj_stats.hpp"
+#include "ppo_loss.hpp"
+#include "policy_act.hpp"
+#include "mlp.hpp"
+#include "ppo_grad.hpp"
+#include "adam.hpp"
+#include "world_sync.hpp"
+
+// the env's action width: what pf_policy_act writes per row and pf_gae's log-probabilities sum over
+static int env_action_dim(const pf_params& P) { return P.task == PF_TASK_ROCKET_LANDING ? pf::kRlActionDim : (P.task == PF_TASK_DOGFIGHT && P.df_action_dim == 6) ? 6 : 4; }
+static_assert(pf::kRlActionDim <= pf::kActMaxA, "the output layer's block holds the widest action");
+// policy_act_kernel's one launch site: workgroups stride over the 64-row tiles, two per CU at the most (all resident), so the weight staging is paid once per workgroup
+static int launch_policy_act(pf_ctx* ctx, const pf::ActK& AK, int64_t rows, void* stream) {
+  const int64_t tiles = (rows + pf::kActRows - 1) / pf::kActRows;
+  const int grid = tiles < (int64_t)ctx->act_grid_cap ? (int)tiles : ctx->act_grid_cap;
+  hipLaunchKernelGGL(pf::policy_act_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, AK);
+  return launched(ctx);
+}
+
+extern "C" {
+int pf_policy_act(pf_ctx* ctx, const pf_policy* q, float* actions_out, uint32_t step_index, void* stream) {
+  static const char* who = "pf_policy_act";
+  if (!ctx) return arg_fail(ctx, who, "ctx is required");
+  if (!q) return arg_fail(ctx, who, "policy is required");
+  const pf_params& P = ctx->P;
+  if (P.task == PF_TASK_NONE) return who_fail(ctx, PF_ERR_UNSUPPORTED, who, "needs a context with an env task (this one drives the Aviary level only)");
+  if (!actions_out) return arg_fail(ctx, who, "actions_out is required");
+  if (!q->obs0) return arg_fail(ctx, who, "obs0 (the [n][pf_obs_dim()] input rows) is required");
+  if (int rc = policy_net_check(ctx, who, q)) return rc;
+  const int D = pf_obs_dim(ctx);
+  if (D > pf::kActMaxIn) return who_fail(ctx, PF_ERR_UNSUPPORTED, who, "observation wider than 128");
+  if (int rc = ensure_device(ctx)) return rc;
+  const pf::ActK AK{*q, actions_out, ctx->n, D, env_action_dim(P), (uint32_t)P.seed, (uint32_t)(P.seed >> 32), step_index, ctx->lane0};
+  return launch_policy_act(ctx, AK, ctx->n, stream);
+}
+// what pf_gae and pf_traj_stats refuse first, in this order (`a`: the call's argument block)
+static int traj_call_check(pf_ctx* ctx, const char* who, const void* a, int k_steps) {
+  if (!ctx || !a) return arg_fail(ctx, who, "ctx and the argument block are required");
+  if (ctx->P.task == PF_TASK_NONE) return who_fail(ctx, PF_ERR_UNSUPPORTED, who, "needs a context with an env task (this one drives the Aviary level only)");
+  if (k_steps < 1) return arg_fail(ctx, who, "k_steps must be >= 1");
+  return PF_OK;
+}
+int pf_gae(pf_ctx* ctx, const pf_gae_args* a, int k_steps, void* stream) {
+  static const char* who = "pf_gae";
+  if (int rc = traj_call_check(ctx, who, a, k_steps)) return rc;
+  const pf_params& P = ctx->P;
+  const arg_ptr required[] = {{"reward", a->reward}, {"terminated", a->terminated}, {"truncated", a->truncated}, {"values", a->values},
+                              {"advantages", a->advantages}, {"returns", a->returns}, {nullptr, nullptr}};
+  if (int rc = require_args(ctx, who, required)) return rc;
+  if (!(a->gamma >= 0.0f && a->gamma <= 1.0f)) return arg_fail(ctx, who, "gamma must be finite and in [0, 1]");
+  if (!(a->lambda >= 0.0f && a->lambda <= 1.0f)) return arg_fail(ctx, who, "lambda must be finite and in [0, 1]");
+  if (P.autoreset == PF_AUTORESET_SAME_STEP && !a->final_values)
+    return arg_fail(ctx, who, "final_values is required under SAME_STEP (the value of the terminal observation in final_obs)");
+  if (P.autoreset != PF_AUTORESET_SAME_STEP && a->final_values)
+    return arg_fail(ctx, who, "final_values must be NULL outside SAME_STEP (there is no final_obs)");
+  if (P.autoreset != PF_AUTORESET_NEXT_STEP && a->episode_start)
+    return arg_fail(ctx, who, "episode_start must be NULL outside NEXT_STEP (no other mode has reset steps)");
+  const int n_logp = (a->actions != nullptr) + (a->mean != nullptr) + (a->log_std != nullptr) + (a->logp_out != nullptr);
+  if (n_logp != 0 && n_logp != 4) return arg_fail(ctx, who, "actions, mean, log_std and logp_out come together or are all NULL");
+  if (int rc = ensure_device(ctx)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const pf::GaeK K{a->gamma, a->lambda, a->reward, a->terminated, a->truncated, a->values, a->final_values, a->episode_start,
+                   a->advantages, a->returns, a->valid_out};
+  const auto scan = P.autoreset == PF_AUTORESET_NEXT_STEP   ? pf::gae_scan_kernel<PF_AUTORESET_NEXT_STEP>
+                    : P.autoreset == PF_AUTORESET_SAME_STEP ? pf::gae_scan_kernel<PF_AUTORESET_SAME_STEP>
+                                                            : pf::gae_scan_kernel<PF_AUTORESET_OFF>;
+  hipLaunchKernelGGL(scan, dim3((ctx->n + 63) / 64), dim3(64), 0, s, K, ctx->n, k_steps);
+  if (n_logp) {
+    const int width = env_action_dim(P);
+    const size_t rows = (size_t)k_steps * (size_t)ctx->n;
+    const size_t blocks = (rows + pf::kGaeLogpBlock - 1) / pf::kGaeLogpBlock;
+    const dim3 grid((unsigned)(blocks < (size_t)pf::kGaeLogpMaxGrid ? blocks : (size_t)pf::kGaeLogpMaxGrid));
+    // (one float4 per row where the rows are four wide and the caller's pointers allow it; the same arithmetic either way)
+    const bool vec = width == 4 && (((uintptr_t)a->actions | (uintptr_t)a->mean) & 15) == 0;
+    hipLaunchKernelGGL(vec ? pf::gae_logp_kernel<true> : pf::gae_logp_kernel<false>, grid, dim3(pf::kGaeLogpBlock), 0, s, a->actions, a->mean,
+                       a->log_std, a->logp_out, rows, width);
+  }
+  return launched(ctx);
+}
+int pf_traj_stats(pf_ctx* ctx, const pf_traj_stats_args* a, int k_steps, void* stream) {
+  static const char* who = "pf_traj_stats";
+  if (int rc = traj_call_check(ctx, who, a, k_steps)) return rc;
+  const pf_params& P = ctx->P;
+  const arg_ptr required[] = {{"reward", a->reward}, {"terminated", a->terminated}, {"truncated", a->truncated}, {"summary", a->summary},
+                              {"carry_return", a->carry_return}, {"carry_length", a->carry_length}, {"carry_disc", a->carry_disc}, {nullptr, nullptr}};
+  if (int rc = require_args(ctx, who, required)) return rc;
+  if (!(a->gamma >= 0.0f && a->gamma <= 1.0f)) return arg_fail(ctx, who, "gamma must be finite and in [0, 1]");
+  if (P.autoreset != PF_AUTORESET_NEXT_STEP && a->episode_start)
+    return arg_fail(ctx, who, "episode_start must be NULL outside NEXT_STEP (no other mode has reset steps)");
+  if (a->obs && !a->obs_moments) return arg_fail(ctx, who, "obs comes with obs_moments (the block its moments are merged into)");
+  if (!a->obs && a->obs_moments) return arg_fail(ctx, who, "obs_moments comes with obs");
+  const int D = pf_obs_dim(ctx);
+  if (a->obs && D > pf::kTsMaxD) return who_fail(ctx, PF_ERR_UNSUPPORTED, who, "observation rows wider than 128 have no moments kernel");
+  if (int rc = ensure_device(ctx)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const bool next = P.autoreset == PF_AUTORESET_NEXT_STEP;
+  const int waves = (ctx->n + 63) / 64;
+  double* scan_part = ctx->ts_scratch;
+  double* obs_part = ctx->ts_scratch + pf::ts_scan_words(ctx->n);
+  const pf::TsK K{a->gamma, a->reward, a->terminated, a->truncated, a->episode_start, a->carry_return, a->carry_length, a->carry_disc,
+                  a->ep_return_out, a->ep_length_out, a->ret_moments};
+  hipLaunchKernelGGL(next ? pf::ts_scan_kernel<true> : pf::ts_scan_kernel<false>, dim3(waves), dim3(64), 0, s, K, ctx->n, k_steps, scan_part);
+  unsigned grid = 0;
+  if (a->obs) {
+    const size_t rows = (size_t)k_steps * (size_t)ctx->n;
+    grid = pf::ts_obs_grid(rows * (size_t)D);
+    hipLaunchKernelGGL(next ? pf::ts_obs_kernel<true> : pf::ts_obs_kernel<false>, dim3(grid), dim3(pf::kTsObsBlock), 0, s, a->obs, a->terminated,
+                       a->truncated, a->episode_start, a->obs_moments, obs_part, rows, ctx->n, D);
+  }
+  hipLaunchKernelGGL(pf::ts_finish_kernel, dim3(1), dim3(pf::kTsFinishBlock), 0, s, scan_part, waves, a->obs ? obs_part : nullptr, (int)grid, D,
+                     a->summary, a->ret_moments, a->obs_moments);
+  return launched(ctx);
+}
+// what pf_ppo_loss and pf_ppo_grad check of the loss's coefficients
+static int ppo_coef_check(pf_ctx* ctx, const char* who, float clip, float vf_coef, float ent_coef, int32_t normalize_advantage) {
+  if (!(clip > 0.0f && clip < INFINITY)) return arg_fail(ctx, who, "clip must be finite and > 0");
+  if (!(vf_coef >= 0.0f && vf_coef < INFINITY)) return arg_fail(ctx, who, "vf_coef must be finite and >= 0");
+  if (!(ent_coef >= 0.0f && ent_coef < INFINITY)) return arg_fail(ctx, who, "ent_coef must be finite and >= 0");
+  if (normalize_advantage != 0 && normalize_advantage != 1) return arg_fail(ctx, who, "normalize_advantage must be 0 or 1");
+  return PF_OK;
+}
+// What pf_ppo_loss and pf_ppo_grad launch first: the advantages' moments, into `fin`; vbytes / vmask: how the kernels behind it read `valid`.
+struct ppo_adv {
+  const uint8_t* vbytes;
+  uint32_t vmask;
+  double* fin;
+};
+static ppo_adv launch_ppo_adv(pf_ctx* ctx, const float* advantages, const uint8_t* valid, size_t rows, hipStream_t s) {
+  double* adv_part = ctx->ppo_scratch + pf::kPpoAdvOffset;
+  // (no valid: the byte loads read the advantages' first M bytes and the mask drops them)
+  const ppo_adv r{valid ? valid : reinterpret_cast<const uint8_t*>(advantages), valid ? 0xFFu : 0u, ctx->ppo_scratch + pf::kPpoFinOffset};
+  const unsigned grid = pf::ppo_grid(rows);
+  hipLaunchKernelGGL(pf::ppo_adv_kernel, dim3(grid), dim3(pf::kPpoBlock), 0, s, advantages, r.vbytes, r.vmask, rows, adv_part);
+  hipLaunchKernelGGL(pf::ppo_adv_finish_kernel, dim3(1), dim3(pf::kPpoBlock), 0, s, adv_part, (int)grid, r.fin);
+  return r;
+}
+int pf_ppo_loss(pf_ctx* ctx, const pf_ppo_loss_args* a, size_t rows, int width, void* stream) {
+  static const char* who = "pf_ppo_loss";
+  if (!ctx || !a) return fail(ctx, PF_ERR_ARG, "pf_ppo_loss: ctx and the argument block are required");
+  if (rows < 1) return arg_fail(ctx, who, "rows must be >= 1");
+  if (width < 1 || width > pf::kPpoMaxA) return arg_fail(ctx, who, "width must be in 1..8");
+  const arg_ptr required[] = {{"mean", a->mean}, {"log_std", a->log_std}, {"actions", a->actions}, {"logp_old", a->logp_old},
+                              {"advantages", a->advantages}, {"returns", a->returns}, {"value", a->value}, {"grad_mean", a->grad_mean},
+                              {"grad_value", a->grad_value}, {"grad_log_std", a->grad_log_std}, {"stats", a->stats}, {nullptr, nullptr}};
+  if (int rc = require_args(ctx, who, required)) return rc;
+  if (int rc = ppo_coef_check(ctx, who, a->clip, a->vf_coef, a->ent_coef, a->normalize_advantage)) return rc;
+  if (int rc = ensure_device(ctx)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const ppo_adv adv = launch_ppo_adv(ctx, a->advantages, a->valid, rows, s);
+  double* main_part = ctx->ppo_scratch + pf::kPpoMainOffset;
+  const unsigned grid = pf::ppo_grid(rows);
+  const pf::PpoK K{a->clip, a->vf_coef, a->normalize_advantage, a->mean, a->log_std, a->actions, a->logp_old, a->advantages, a->returns, a->value,
+                   adv.vbytes, adv.vmask, a->grad_mean, a->grad_value};
+  // (one float4 per row where the rows are four wide and the caller's pointers allow it; the same arithmetic either way)
+  const bool vec = width == 4 && (((uintptr_t)a->actions | (uintptr_t)a->mean | (uintptr_t)a->grad_mean) & 15) == 0;
+  using pf::ppo_main_kernel;
+  void (*const by_width[pf::kPpoMaxA])(pf::PpoK, size_t, const double*, double*) = {ppo_main_kernel<1, false>, ppo_main_kernel<2, false>, ppo_main_kernel<3, false>, ppo_main_kernel<4, false>,
+                                                                                    ppo_main_kernel<5, false>, ppo_main_kernel<6, false>, ppo_main_kernel<7, false>, ppo_main_kernel<8, false>};
+  const auto main_kernel = vec ? ppo_main_kernel<4, true> : by_width[width - 1];
+  hipLaunchKernelGGL(main_kernel, dim3(grid), dim3(pf::kPpoBlock), 0, s, K, rows, (const double*)adv.fin, main_part);
+  hipLaunchKernelGGL(pf::ppo_finish_kernel, dim3(1), dim3(pf::kPpoBlock), 0, s, (const double*)main_part, (int)grid, (const double*)adv.fin, a->log_std, width,
+                     a->vf_coef, a->ent_coef, a->stats, a->grad_log_std);
+  return launched(ctx);
+}
+// ---- pf_mlp_forward, pf_mlp_backward and pf_ppo_grad: what they check of a network and of `rows`, and the pieces of their launches
+static const char* mlp_shape_error(const pf_mlp* q) {
+  if (q->n_layers != 2 && q->n_layers != 3) return "n_layers must be 2 or 3";
+  for (int l = 0; l + 1 < q->n_layers; ++l)
+    if (q->width[l] < 1 || q->width[l] > PF_POLICY_MAX_HIDDEN) return "width: hidden widths must be in 1..PF_POLICY_MAX_HIDDEN (64)";
+  if (q->activation != PF_ACT_TANH && q->activation != PF_ACT_RELU) return "activation must be PF_ACT_TANH or PF_ACT_RELU";
+  if (q->in_dim < 1 || q->in_dim > pf::kActMaxIn) return "in_dim must be in 1..128";
+  if (q->out_dim < 1 || q->out_dim > pf::kActMaxA) return "out_dim must be in 1..8";
+  return nullptr;
+}
+static bool mlp_has_params(const pf_mlp* q) {
+  for (int l = 0; l < q->n_layers; ++l)
+    if (!q->w[l] || !q->b[l]) return false;
+  return true;
+}
+static int rows_check(pf_ctx* ctx, const char* who, int64_t rows) {
+  if (rows < 1) return arg_fail(ctx, who, "rows must be >= 1");
+  if (rows > (int64_t)INT32_MAX - pf::kActRows) return arg_fail(ctx, who, "rows must be below 2^31 - 64 (the kernels index rows with 32 bits)");
+  return PF_OK;
+}
+// pf_mlp_forward / pf_mlp_backward: what both check first, the context included; `who` is the call's name
+static int mlp_check(pf_ctx* ctx, const char* who, const pf_mlp* q, int64_t rows) {
+  if (!ctx) return arg_fail(ctx, who, "ctx is required");
+  if (!q) return arg_fail(ctx, who, "mlp is required");
+  if (const char* e = mlp_shape_error(q)) return arg_fail(ctx, who, e);
+  if (!mlp_has_params(q)) return arg_fail(ctx, who, "w / b: every layer needs w and b");
+  return rows_check(ctx, who, rows);
+}
+// a network's gradient outputs as spans, layer l's under the names wn[l] and bn[l]; returns the new count
+static int append_grad_spans(arg_span* spans, int ns, const pf_mlp* q, const char* const* wn, const char* const* bn, float* const* gw, float* const* gb) {
+  for (int l = 0; l < q->n_layers; ++l) {
+    const size_t n_in = l == 0 ? q->in_dim : q->width[l - 1], n_out = l + 1 == q->n_layers ? q->out_dim : q->width[l];
+    spans[ns++] = {wn[l], gw[l], sizeof(float) * n_in * n_out};
+    spans[ns++] = {bn[l], gb[l], sizeof(float) * n_out};
+  }
+  return ns;
+}
+// the workgroups' partial gradients (`part`, one row of the network's parameters per workgroup of the backward launch) summed into gw / gb
+static void launch_mlp_reduce(const pf_mlp* q, float* const* gw, float* const* gb, const float* part, int grid, hipStream_t s) {
+  pf::MlpOutK O;
+  const int P = pf::mlp_param_count(*q, O.end);
+  for (int l = 0; l < 3; ++l) {
+    O.p[2 * l] = l < q->n_layers ? gw[l] : nullptr;
+    O.p[2 * l + 1] = l < q->n_layers ? gb[l] : nullptr;
+  }
+  hipLaunchKernelGGL(pf::mlp_reduce_kernel, dim3((P + 255) / 256), dim3(256), 0, s, part, grid, P, O);
+}
+int pf_mlp_forward(pf_ctx* ctx, const pf_mlp* q, const float* x, int64_t rows, float* out, void* stream) {
+  static const char* who = "pf_mlp_forward";
+  if (int rc = mlp_check(ctx, who, q, rows)) return rc;
+  if (!x) return arg_fail(ctx, who, "x is required");
+  if (!out) return arg_fail(ctx, who, "out is required");
+  char buf[128];
+  const arg_span spans[2] = {{"x", x, sizeof(float) * (size_t)rows * q->in_dim}, {"out", out, sizeof(float) * (size_t)rows * q->out_dim}};
+  if (const char* e = spans_overlap(spans, 2, buf, sizeof(buf))) return arg_fail(ctx, who, e);
+  if (int rc = ensure_device(ctx)) return rc;
+  // policy_act_kernel itself, the draw off (no log_std), the caller's rows as its observations and out_dim as its action width
+  pf_policy P{};  // (log_std, mean_out and the layers the network does not have: null)
+  P.n_layers = q->n_layers;
+  P.width[0] = q->width[0];
+  P.width[1] = q->width[1];
+  P.activation = q->activation;
+  for (int l = 0; l < q->n_layers; ++l) P.w[l] = q->w[l], P.b[l] = q->b[l];
+  P.obs0 = x;
+  const pf::ActK AK{P, out, (int)rows, q->in_dim, q->out_dim, 0u, 0u, 0u, 0ull};
+  return launch_policy_act(ctx, AK, rows, stream);
+}
+size_t pf_mlp_backward_workspace_bytes(const pf_mlp* q, int64_t rows) {
+  if (!q || mlp_shape_error(q) || rows < 1) return 0;
+  return sizeof(float) * (size_t)pf::mlp_grid(rows) * (size_t)pf::mlp_param_count(*q, nullptr);
+}
+int pf_mlp_backward(pf_ctx* ctx, const pf_mlp* q, const float* x, const float* grad_out, int64_t rows, float* const grad_w[3], float* const grad_b[3],
+                    void* workspace, size_t workspace_bytes, void* stream) {
+  static const char* who = "pf_mlp_backward";
+  if (int rc = mlp_check(ctx, who, q, rows)) return rc;
+  const arg_ptr required[] = {{"x", x}, {"grad_out", grad_out}, {"grad_w", grad_w}, {"grad_b", grad_b}, {nullptr, nullptr}};
+  if (int rc = require_args(ctx, who, required)) return rc;
+  for (int l = 0; l < q->n_layers; ++l) {
+    if (!grad_w[l]) return arg_fail(ctx, who, "grad_w: every layer needs its output");
+    if (!grad_b[l]) return arg_fail(ctx, who, "grad_b: every layer needs its output");
+  }
+  if (!workspace) return arg_fail(ctx, who, "workspace is required");
+  const size_t need = pf_mlp_backward_workspace_bytes(q, rows);
+  if (workspace_bytes < need) return arg_fail(ctx, who, "workspace_bytes is below pf_mlp_backward_workspace_bytes(mlp, rows)");
+  static const char* const wn[3] = {"grad_w[0]", "grad_w[1]", "grad_w[2]"};
+  static const char* const bn[3] = {"grad_b[0]", "grad_b[1]", "grad_b[2]"};
+  arg_span spans[9];
+  int ns = 0;
+  spans[ns++] = {"x", x, sizeof(float) * (size_t)rows * q->in_dim};
+  spans[ns++] = {"grad_out", grad_out, sizeof(float) * (size_t)rows * q->out_dim};
+  spans[ns++] = {"workspace", workspace, need};
+  ns = append_grad_spans(spans, ns, q, wn, bn, grad_w, grad_b);
+  char buf[128];
+  if (const char* e = spans_overlap(spans, ns, buf, sizeof(buf))) return arg_fail(ctx, who, e);
+  if (int rc = ensure_device(ctx)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const int grid = pf::mlp_grid(rows);
+  const pf::MlpK K{*q, x, grad_out, (float*)workspace, (int)rows};
+  hipLaunchKernelGGL(pf::mlp_backward_kernel<pf::MlpK>, dim3(grid), dim3(256), 0, s, K);
+  launch_mlp_reduce(q, grad_w, grad_b, (const float*)workspace, grid, s);
+  return launched(ctx);
+}
+// pf_ppo_grad: the shape checks of the two networks; null, or the refusal with the network named (buf holds it)
+static const char* ppo_grad_shape_error(const pf_mlp* actor, const pf_mlp* critic, char* buf, size_t len) {
+  if (const char* e = mlp_shape_error(actor)) {
+    snprintf(buf, len, "actor: %s", e);
+    return buf;
+  }
+  if (const char* e = mlp_shape_error(critic)) {
+    snprintf(buf, len, "critic: %s", e);
+    return buf;
+  }
+  if (critic->out_dim != 1) return "critic: out_dim must be 1";
+  if (critic->in_dim != actor->in_dim) return "critic: in_dim must equal the actor's in_dim (both read x)";
+  return nullptr;
+}
+size_t pf_ppo_grad_workspace_bytes(const pf_mlp* actor, const pf_mlp* critic, int64_t rows) {
+  char buf[160];
+  if (!actor || !critic || ppo_grad_shape_error(actor, critic, buf, sizeof(buf)) || rows < 1) return 0;
+  const int grid = pf::mlp_grid(rows);
+  return pf::ppo_grad_stat_bytes(grid) + sizeof(float) * (size_t)grid * ((size_t)pf::mlp_param_count(*actor, nullptr) + (size_t)pf::mlp_param_count(*critic, nullptr));
+}
+int pf_ppo_grad(pf_ctx* ctx, const pf_ppo_grad_args* a, int64_t rows, void* workspace, size_t workspace_bytes, void* stream) {
+  static const char* who = "pf_ppo_grad";
+  if (!ctx) return arg_fail(ctx, who, "ctx is required");
+  if (!a) return arg_fail(ctx, who, "the argument block is required");
+  if (!a->actor) return arg_fail(ctx, who, "actor is required");
+  if (!a->critic) return arg_fail(ctx, who, "critic is required");
+  char buf[160];
+  if (const char* e = ppo_grad_shape_error(a->actor, a->critic, buf, sizeof(buf))) return arg_fail(ctx, who, e);
+  const pf_mlp* nets[2] = {a->actor, a->critic};
+  if (!mlp_has_params(a->actor)) return arg_fail(ctx, who, "actor: w / b: every layer needs w and b");
+  if (!mlp_has_params(a->critic)) return arg_fail(ctx, who, "critic: w / b: every layer needs w and b");
+  if (int rc = rows_check(ctx, who, rows)) return rc;
+  const arg_ptr required[] = {{"x", a->x}, {"log_std", a->log_std}, {"actions", a->actions}, {"logp_old", a->logp_old}, {"advantages", a->advantages},
+                              {"returns", a->returns}, {"grad_log_std", a->grad_log_std}, {"stats", a->stats}, {"workspace", workspace}, {nullptr, nullptr}};
+  if (int rc = require_args(ctx, who, required)) return rc;
+  static const char* const gn[2][2][3] = {{{"actor_grad_w[0]", "actor_grad_w[1]", "actor_grad_w[2]"}, {"actor_grad_b[0]", "actor_grad_b[1]", "actor_grad_b[2]"}},
+                                          {{"critic_grad_w[0]", "critic_grad_w[1]", "critic_grad_w[2]"}, {"critic_grad_b[0]", "critic_grad_b[1]", "critic_grad_b[2]"}}};
+  float* const* gw[2] = {a->actor_grad_w, a->critic_grad_w};
+  float* const* gb[2] = {a->actor_grad_b, a->critic_grad_b};
+  for (int k = 0; k < 2; ++k)
+    for (int l = 0; l < nets[k]->n_layers; ++l) {
+      const arg_ptr outs[] = {{gn[k][0][l], gw[k][l]}, {gn[k][1][l], gb[k][l]}, {nullptr, nullptr}};
+      if (int rc = require_args(ctx, who, outs)) return rc;
+    }
+  if (int rc = ppo_coef_check(ctx, who, a->clip, a->vf_coef, a->ent_coef, a->normalize_advantage)) return rc;
+  const size_t need = pf_ppo_grad_workspace_bytes(a->actor, a->critic, rows);
+  if (workspace_bytes < need) return arg_fail(ctx, who, "workspace_bytes is below pf_ppo_grad_workspace_bytes(actor, critic, rows)");
+  if (((uintptr_t)workspace & 7) != 0) return arg_fail(ctx, who, "workspace must be 8-byte aligned (it holds rows of double partial sums)");
+  const size_t M = (size_t)rows, A = (size_t)a->actor->out_dim;
+  arg_span spans[7 + 15];
+  int ns = 0;
+  spans[ns++] = {"x", a->x, sizeof(float) * M * a->actor->in_dim};
+  spans[ns++] = {"log_std", a->log_std, sizeof(float) * A};
+  spans[ns++] = {"actions", a->actions, sizeof(float) * M * A};
+  spans[ns++] = {"logp_old", a->logp_old, sizeof(float) * M};
+  spans[ns++] = {"advantages", a->advantages, sizeof(float) * M};
+  spans[ns++] = {"returns", a->returns, sizeof(float) * M};
+  if (a->valid) spans[ns++] = {"valid", a->valid, M};
+  const int n_read = ns;
+  spans[ns++] = {"workspace", workspace, need};
+  spans[ns++] = {"grad_log_std", a->grad_log_std, sizeof(float) * A};
+  spans[ns++] = {"stats", a->stats, sizeof(double) * 16};
+  for (int k = 0; k < 2; ++k) ns = append_grad_spans(spans, ns, nets[k], gn[k][0], gn[k][1], gw[k], gb[k]);
+  if (const char* e = spans_overlap(spans, ns, buf, sizeof(buf), n_read)) return arg_fail(ctx, who, e);
+  if (int rc = ensure_device(ctx)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const ppo_adv adv = launch_ppo_adv(ctx, a->advantages, a->valid, M, s);
+  const int grid = pf::mlp_grid(rows);
+  double* stat_part = (double*)workspace;
+  float* const part0 = (float*)((char*)workspace + pf::ppo_grad_stat_bytes(grid));
+  float* const part[2] = {part0, part0 + (size_t)grid * (size_t)pf::mlp_param_count(*a->actor, nullptr)};
+  const pf::PpoGradK<pf::kGradActor> KA{pf::MlpK{*a->actor, a->x, nullptr, part[0], (int)rows}, a->clip, a->vf_coef, a->normalize_advantage, a->log_std, a->actions,
+                                        a->logp_old, a->advantages, a->returns, adv.vbytes, adv.vmask, adv.fin, stat_part};
+  const pf::PpoGradK<pf::kGradCritic> KC{pf::MlpK{*a->critic, a->x, nullptr, part[1], (int)rows}, a->clip, a->vf_coef, a->normalize_advantage, a->log_std, a->actions,
+                                         a->logp_old, a->advantages, a->returns, adv.vbytes, adv.vmask, adv.fin, stat_part};
+  hipLaunchKernelGGL(pf::mlp_backward_kernel<pf::PpoGradK<pf::kGradActor>>, dim3(grid), dim3(256), 0, s, KA);
+  hipLaunchKernelGGL(pf::mlp_backward_kernel<pf::PpoGradK<pf::kGradCritic>>, dim3(grid), dim3(256), 0, s, KC);
+  for (int k = 0; k < 2; ++k) launch_mlp_reduce(nets[k], gw[k], gb[k], part[k], grid, s);
+  hipLaunchKernelGGL(pf::ppo_finish_kernel, dim3(1), dim3(pf::kPpoBlock), 0, s, (const double*)stat_part, grid, (const double*)adv.fin, a->log_std, (int)A, a->vf_coef,
+                     a->ent_coef, a->stats, a->grad_log_std);
+  return launched(ctx);
+}
+size_t pf_adam_workspace_bytes(int64_t total_numel) {
+  if (total_numel < 1 || total_numel > (int64_t)INT32_MAX) return 0;
+  return sizeof(double) * (pf::adam_grid_bound(total_numel) + pf::kAdamHeader);
+}
+// what pf_adam_step refuses, or null; `buf` holds a composed message
+static const char* adam_error(const pf_adam_args* a, const void* workspace, size_t workspace_bytes, char* buf, size_t len) {
+  if (!a) return "the argument block is required";
+  if (a->n_tensors < 1 || a->n_tensors > PF_ADAM_MAX_TENSORS) return "n_tensors must be in 1..PF_ADAM_MAX_TENSORS (32)";
+  if (a->skip_nonfinite != 0 && a->skip_nonfinite != 1) return "skip_nonfinite must be 0 or 1";
+  if (!a->lr_dev && !(a->lr >= 0.0f && a->lr < INFINITY)) return "lr must be finite and >= 0";
+  if (!(a->beta1 >= 0.0f && a->beta1 < 1.0f)) return "beta1 must be in [0, 1)";
+  if (!(a->beta2 >= 0.0f && a->beta2 < 1.0f)) return "beta2 must be in [0, 1)";
+  if (!(a->eps > 0.0f && a->eps < INFINITY)) return "eps must be finite and > 0";
+  if (!(a->weight_decay >= 0.0f && a->weight_decay < INFINITY)) return "weight_decay must be finite and >= 0";
+  if (!(a->max_grad_norm > 0.0f)) return "max_grad_norm must be > 0 (+infinity: no clipping)";
+  if (!a->state) return "state is required";
+  if (!workspace) return "workspace is required";
+  static const char* const kinds[4] = {"param", "grad", "exp_avg", "exp_avg_sq"};
+  arg_span spans[4 * PF_ADAM_MAX_TENSORS + 3];
+  char names[4 * PF_ADAM_MAX_TENSORS][16];
+  int ns = 0;
+  int64_t total = 0;
+  for (int i = 0; i < a->n_tensors; ++i) {
+    if (a->numel[i] < 1) {
+      snprintf(buf, len, "numel[%d] must be >= 1", i);
+      return buf;
+    }
+    total += a->numel[i];
+    if (total > (int64_t)INT32_MAX) return "numel: the total must be below 2^31";
+    const void* const ptrs[4] = {a->param[i], a->grad[i], a->exp_avg[i], a->exp_avg_sq[i]};
+    for (int k = 0; k < 4; ++k) {
+      snprintf(names[ns], sizeof(names[ns]), "%s[%d]", kinds[k], i);
+      if (!ptrs[k]) {
+        snprintf(buf, len, "%s is required", names[ns]);
+        return buf;
+      }
+      spans[ns] = {names[ns], ptrs[k], sizeof(float) * (size_t)a->numel[i]};
+      ++ns;
+    }
+  }
+  const size_t need = pf_adam_workspace_bytes(total);
+  if (workspace_bytes < need) return "workspace_bytes is below pf_adam_workspace_bytes(the total of numel)";
+  spans[ns++] = {"state", a->state, sizeof(double) * 8};
+  spans[ns++] = {"workspace", workspace, need};
+  if (a->lr_dev) spans[ns++] = {"lr_dev", a->lr_dev, sizeof(float)};
+  return spans_overlap(spans, ns, buf, len);
+}
+int pf_adam_step(pf_ctx* ctx, const pf_adam_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+  static const char* who = "pf_adam_step";
+  if (!ctx) return arg_fail(ctx, who, "ctx is required");
+  char buf[128];
+  if (const char* e = adam_error(a, workspace, workspace_bytes, buf, sizeof(buf))) return arg_fail(ctx, who, e);
+  if (int rc = ensure_device(ctx)) return rc;
+  pf::AdamK K;
+  K.n_tensors = a->n_tensors;
+  K.skip_nonfinite = a->skip_nonfinite;
+  K.lr = a->lr;
+  K.beta1 = a->beta1, K.beta2 = a->beta2, K.eps = a->eps, K.weight_decay = a->weight_decay, K.max_grad_norm = a->max_grad_norm;
+  K.lr_dev = a->lr_dev;
+  K.state = a->state;
+  K.work = (double*)workspace;
+  int chunks = 0;
+  for (int i = 0; i < PF_ADAM_MAX_TENSORS; ++i) {
+    const bool on = i < a->n_tensors;
+    K.first_chunk[i] = chunks;
+    K.numel[i] = on ? (int32_t)a->numel[i] : 0;
+    K.param[i] = on ? a->param[i] : nullptr;
+    K.grad[i] = on ? a->grad[i] : nullptr;
+    K.exp_avg[i] = on ? a->exp_avg[i] : nullptr;
+    K.exp_avg_sq[i] = on ? a->exp_avg_sq[i] : nullptr;
+    if (on) chunks += (int)((a->numel[i] + pf::kAdamChunk - 1) / pf::kAdamChunk);
+  }
+  K.first_chunk[PF_ADAM_MAX_TENSORS] = chunks;
+  K.chunks = chunks;
+  const int grid = chunks < pf::kAdamMaxGrid ? chunks : pf::kAdamMaxGrid;  // (<= adam_grid_bound(total): a chunk holds an element or more)
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(pf::adam_norm_kernel, dim3(grid), dim3(pf::kAdamBlock), 0, s, K);
+  hipLaunchKernelGGL(pf::adam_update_kernel, dim3(grid), dim3(pf::kAdamBlock), 0, s, K);
+  return launched(ctx);
+}
+int pf_world_sync(pf_ctx* ctx, const pf_world_sync_args* a, int agents_per_world, void* stream) {
+  static const char* who = "pf_world_sync";
+  if (!ctx) return arg_fail(ctx, who, "ctx is required");
+  if (!a) return arg_fail(ctx, who, "the argument block is required");
+  const arg_ptr required[] = {{"terminated", a->terminated}, {"truncated", a->truncated}, {"reward", a->reward}, {"done", a->done},
+                              {"valid_out", a->valid_out}, {"reset_out", a->reset_out}, {nullptr, nullptr}};
+  if (int rc = require_args(ctx, who, required)) return rc;
+  if (agents_per_world < 1 || agents_per_world > pf::kWorldSyncMaxA) return arg_fail(ctx, who, "agents_per_world must be in 1..64");
+  if (ctx->n % agents_per_world != 0) return arg_fail(ctx, who, "agents_per_world must divide the context's lane count n");
+  if (int rc = ensure_device(ctx)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  // (the new latch goes to the context's staging buffer and is copied over the caller's behind the kernel: world_sync.hpp)
+  const pf::WorldSyncK K{a->terminated, a->truncated, a->reward, a->done, a->exclude, a->valid_out, a->reset_out, ctx->sync_latch};
+  hipLaunchKernelGGL(pf::world_sync_kernel, dim3((ctx->n + pf::kWorldSyncBlock - 1) / pf::kWorldSyncBlock), dim3(pf::kWorldSyncBlock), 0, s, K, ctx->n,
+                     agents_per_world);
+  PF_HIP(ctx, hipGetLastError());
+  PF_HIP(ctx, hipMemcpyAsync(a->done, ctx->sync_latch, (size_t)ctx->n, hipMemcpyDeviceToDevice, s));
+  return PF_OK;
+}
+}  // extern "C"

@@ -19,6 +19,14 @@
 // exist, and element by element otherwise: a thread owns the same four elements either way, so the bits agree. The grid is
 // min(chunks, kAdamMaxGrid): a function of numel[] alone. No atomics.
 #pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "../../include/pyflyt_amd.h"
+#include "uav_device.hpp"
+#include "traj_stats.hpp"  // ts_wave_sum
 
 namespace pf {
 

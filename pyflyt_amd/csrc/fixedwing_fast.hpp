@@ -28,12 +28,13 @@
 //   * one gyroscopic inertia (I_pa + I_own) instead of two products, rotation scale 2 for the unit
 //     quaternion, Euler angles only in the epilogue;
 //   * resets copy the context's settled spawn state (the settle throttle command is 0, so the motor
-//     noise scales nothing: pyflyt_amd.hip, settle_template_kernel).
+//     noise scales nothing: aviary_kernels.hpp, settle_template_kernel).
 #pragma once
 #include "../../include/pyflyt_amd.h"
 #include "uav_device.hpp"
 #include "uav_vehicles.hpp"  // contact_solve_dev
 #include "shared_world.hpp"  // pair_stage_dev (the dogfight's shared worlds)
+#include "quadx_fast.hpp"    // PF_STAMP
 #include <cstddef>
 #include <type_traits>
 

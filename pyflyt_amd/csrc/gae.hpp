@@ -18,6 +18,13 @@
 // Selections are selects: the stale rows of final_values and the reward of a reset step are loaded and then NOT chosen -- they are
 // never multiplied by a zero, so a NaN in them reaches nothing.
 #pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "../../include/pyflyt_amd.h"
+#include "uav_device.hpp"
 
 namespace pf {
 

@@ -29,6 +29,16 @@
 // PpoGradK), step 2 is replaced: the head loads its own row data a tile ahead, and once h_last stands in LDS it computes the output
 // layer and from it the tile's rows of G. Steps 1 and 3 - 6, the running sums and the block of partials are this one text either way.
 #pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "../../include/pyflyt_amd.h"
+#include "uav_device.hpp"
+#include "policy_mlp.hpp"
+#include "mlp_tile.hpp"
+#include "policy_act.hpp"
 
 namespace pf {
 

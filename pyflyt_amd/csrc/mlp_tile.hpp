@@ -5,6 +5,14 @@
 // biases and the row loads are still written per kernel: each of them, as a shared function, made pf_mlp_backward measurably slower
 // (profiles/mlp_tile/nothing_moved.txt). Layouts: policy_act.hpp's top comment.
 #pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "../../include/pyflyt_amd.h"
+#include "uav_device.hpp"
+#include "policy_mlp.hpp"  // kPolH
 
 namespace pf {
 

@@ -24,6 +24,15 @@
 //   * the tile constants, the barrier, the accumulator's fill, row map and activation store, the matrix chain and the output pair's
 //     fmaf chain are mlp_tile.hpp's (mlp.hpp and ppo_grad.hpp run them too).
 #pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "../../include/pyflyt_amd.h"
+#include "uav_device.hpp"
+#include "policy_mlp.hpp"
+#include "mlp_tile.hpp"
 
 namespace pf {
 

@@ -18,6 +18,14 @@
 //   * summation order, fixed: acc = bias, then the inputs in ascending index, one fmaf each, float32. It does not depend on the
 //     launch shape or on where in a launch the step falls: splitting a rollout leaves every bit as it was.
 #pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "../../include/pyflyt_amd.h"
+#include "uav_device.hpp"
+#include "uav_vehicles.hpp"  // lds_fptr
 
 namespace pf {
 

@@ -20,6 +20,16 @@
 // workgroup's tiles gridDim apart; at most 256 rows of partials instead of 1024) and nothing else does. LDS: the backward's 120 576 bytes
 // plus 3 200 for the head, under gfx950's 160 KB with one network staged: a launch per network. No atomics; the grid is mlp_grid(rows).
 #pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "../../include/pyflyt_amd.h"
+#include "uav_device.hpp"
+#include "mlp_tile.hpp"
+#include "ppo_loss.hpp"  // the per-row terms of the loss
+#include "mlp.hpp"  // mlp_backward_kernel, which these heads instantiate
 
 namespace pf {
 

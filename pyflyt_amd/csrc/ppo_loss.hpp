@@ -24,6 +24,15 @@
 // atomics. Selections are selects: every input of an invalid row is loaded and then NOT chosen, so a NaN there reaches nothing.
 // A missing `valid` is served without a second instantiation: the byte is read from memory that is readable anyway and masked off.
 #pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "../../include/pyflyt_amd.h"
+#include "uav_device.hpp"
+#include "gae.hpp"         // gae_logp_term
+#include "traj_stats.hpp"  // ts_wave_sum
 
 namespace pf {
 

@@ -164,7 +164,7 @@ inline bool quadk_from_params(const pf_params& P, QuadK& K) {
     K.calm_t2 = fmaxf(tstar * tstar, 1.0f);
     K.calm_c = fmaxf(fmaxf(__builtin_fabsf(K.dragM[0]), __builtin_fabsf(K.dragM[1])), __builtin_fabsf(K.dragM[2]));
     // (injected noise is unbounded; mode -1 hands the action to the motors unclipped; a shared world has the pair stage in its tick;
-    //  PF_NO_CALM_PATH: the kernel selection clears it -- pyflyt_amd.hip, select_env_kernel)
+    //  PF_NO_CALM_PATH: the kernel selection clears it -- abi_env.hpp, select_env_kernel)
     K.calm_on = (P.contact_response && P.noise_mode != PF_NOISE_INJECT && P.flight_mode != -1 && K.apw == 1 && P.motor_dt_over_tau[0] <= 1.0f &&
                  K.calm_t2 < 1e6f) ? 1 : 0;
   }
@@ -1292,7 +1292,7 @@ constexpr int kQuadFixedRatio = TASK == PF_TASK_WAYPOINTS ? 4 : 3;
 //  was 2, final occupancy is 1" in rounds 4 / 5 --: their budget says so)
 // FIXED (ROLL == 0, flight mode 0, independent lanes, noise drawn on device or off): the call shape of every training loop's hot call,
 // pinned at compile time -- pf_env_step without a mask, NEXT_STEP auto-reset, the task's own number of Aviary steps per env step
-// (kQuadFixedRatio), quaternion observations, dense reward. The launcher (pyflyt_amd.hip: launch_env) picks it for exactly that call of exactly such a context; the body is the
+// (kQuadFixedRatio), quaternion observations, dense reward. The launcher (abi_env.hpp: launch_env) picks it for exactly that call of exactly such a context; the body is the
 // general one with those six wave-uniform values constant, so the reset op, the SAME_STEP block, the Euler branch and the loop bound's
 // reads fold away -- the arithmetic and its order are untouched, and the state layout is the same: the two interleave freely.
 template <int TASK, int NOISE, int LPW, int ROLL, bool CR, bool MODES = false, bool SHARED = false, int WPS = 2, bool FIXED = false>

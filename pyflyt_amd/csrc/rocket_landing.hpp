@@ -15,6 +15,7 @@
 //     tested against the slab as before. The rim and the side wall are not modelled.
 #pragma once
 #include "rocket.hpp"
+#include "env_generic.hpp"  // env_kernel, which this header specialises; SideBlock, kWave, kMaxObs
 
 namespace pf {
 

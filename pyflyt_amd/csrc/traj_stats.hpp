@@ -23,6 +23,13 @@
 // observation kernel is a function of k n D, never of the device. No atomics. Selections are selects: the reward and the observation
 // row of an invalid step are loaded and then NOT chosen, so a NaN in them reaches nothing.
 #pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "../../include/pyflyt_amd.h"
+#include "uav_device.hpp"
 
 namespace pf {
 

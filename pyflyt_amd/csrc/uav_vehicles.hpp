@@ -1226,7 +1226,7 @@ struct Fixedwing {
 };
 
 // ------------------------------------------------------------------------------------------
-// What every Aviary-level kernel (pyflyt_amd.hip) does around its own loop: bind, load, ..., store, outputs.
+// What every Aviary-level kernel (aviary_kernels.hpp) does around its own loop: bind, load, ..., store, outputs.
 // (The caller's variables go in by reference: see flush_obs_tile.)
 
 // Floats per drone in the setpoint buffer: fixedwing.py:221-224, rocket.py:228 (host and device)

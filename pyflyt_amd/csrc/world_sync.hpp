@@ -12,6 +12,9 @@
 //
 // Selections are selects: the reward of a latched lane is loaded and not chosen, so a NaN in it reaches nothing.
 #pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
 
 namespace pf {
 
