@@ -570,6 +570,39 @@ typedef struct pf_traj_stats_args {
 size_t pf_sizeof_traj_stats(void);
 int pf_traj_stats(pf_ctx* ctx, const pf_traj_stats_args* a, int k_steps, void* stream);
 
+/* pf_traj_stats with the validity of every step given by the caller: what the multi-agent envs need, whose valid steps are
+ * pf_world_sync's valid_out -- zero where an agent sits a step out after its episode ended, on the step that resets its world and
+ * on an opponent's lanes -- and follow from no auto-reset mode. The contract is pf_traj_stats's, word for word, except:
+ *   - VALID. Step s of lane i is valid if and only if valid[s][i] != 0: in every auto-reset mode, on any context with an env task.
+ *     There is no episode_start and no done[-1].
+ *   - INVALID STEPS. terminated, truncated, reward and the observation row of an invalid step are loaded and NOT selected: a flag
+ *     set there ends no episode (it is in no count of summary), and a NaN there reaches no output, no carry and no moment.
+ *   - ERRORS. pf_traj_stats's list without the episode_start case, and PF_ERR_ARG naming `valid` when valid is NULL.
+ *   - Three launches, no host synchronisation, no allocation, no copy -- capturable in a HIP graph. The partial sums live in the
+ *     same context-owned block: calls on one context, of this function and of pf_traj_stats, must not overlap on different streams.
+ *   - EQUIVALENCE. With valid = the mask pf_gae writes to valid_out for a NEXT_STEP trajectory (the same episode_start), or all
+ *     ones under SAME_STEP / OFF, every per-step output, carry, summary word and moment has the SAME BITS as pf_traj_stats's on
+ *     those inputs: a lane's sums run in step order, and the order of the double sums is decided by (n, k_steps, D) alone here too.
+ *   (Added without a new PF_ABI_VERSION: a new function and a new block; pf_traj_stats_args as it was.) */
+typedef struct pf_traj_stats_masked_args {
+  float gamma;                     /* in [0, 1] */
+  const float*   reward;           /* [k][n]    */
+  const uint8_t* terminated;       /* [k][n]    */
+  const uint8_t* truncated;        /* [k][n]    */
+  const uint8_t* valid;            /* [k][n], required: non-zero = this step is a transition of this lane */
+  const float*   obs;              /* [k][n][D] policy inputs, or NULL (with obs_moments) = no observation moments */
+  float*   carry_return;           /* [n] in / out */
+  int32_t* carry_length;           /* [n] in / out */
+  float*   carry_disc;             /* [n] in / out */
+  float*   ep_return_out;          /* [k][n] or NULL */
+  int32_t* ep_length_out;          /* [k][n] or NULL */
+  double*  summary;                /* [8] out */
+  double*  ret_moments;            /* [3] in / out, or NULL */
+  double*  obs_moments;            /* [1 + 2 D] in / out, or NULL */
+} pf_traj_stats_masked_args;
+size_t pf_sizeof_traj_stats_masked(void);
+int pf_traj_stats_masked(pf_ctx* ctx, const pf_traj_stats_masked_args* a, int k_steps, void* stream);
+
 /* The clipped PPO objective of a diagonal-Gaussian policy over M rows of a batch, its statistics, and its gradients with respect to
  * the actor's means, the critic's values and log_std: everything between the outputs of the caller's two networks and their
  * output-gradients, in one call. Any context, with an env task or without: it serves the error string and owns the partial sums.

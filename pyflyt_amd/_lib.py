@@ -80,6 +80,7 @@ PfParams, PfBuffers, PfPolicy, PfGae = _STRUCTS["pf_params"], _STRUCTS["pf_buffe
 PfTrajStats, PfPpoLoss, PfMlp = _STRUCTS["pf_traj_stats_args"], _STRUCTS["pf_ppo_loss_args"], _STRUCTS["pf_mlp"]
 PfAdam, PF_ADAM_MAX_TENSORS = _STRUCTS["pf_adam_args"], _DEFINES["PF_ADAM_MAX_TENSORS"]
 PfWorldSync = _STRUCTS["pf_world_sync_args"]
+PfTrajStatsMasked = _STRUCTS["pf_traj_stats_masked_args"]
 PfPpoGradArgs = _STRUCTS["pf_ppo_grad_args"]
 for _k, _v in _ENUMS.items():  # PF_F_TERMINATED -> F_TERMINATED etc. stay spelled out above; expose the rest as PF_*
     globals().setdefault(_k, _v)
@@ -142,6 +143,8 @@ def lib():
     L.pf_sizeof_gae.restype = C.c_size_t
     L.pf_traj_stats.argtypes = [C.c_void_p, C.POINTER(PfTrajStats), C.c_int, C.c_void_p]
     L.pf_sizeof_traj_stats.restype = C.c_size_t
+    L.pf_traj_stats_masked.argtypes = [C.c_void_p, C.POINTER(PfTrajStatsMasked), C.c_int, C.c_void_p]
+    L.pf_sizeof_traj_stats_masked.restype = C.c_size_t
     L.pf_ppo_loss.argtypes = [C.c_void_p, C.POINTER(PfPpoLoss), C.c_size_t, C.c_int, C.c_void_p]
     L.pf_sizeof_ppo_loss.restype = C.c_size_t
     L.pf_sizeof_mlp.restype = C.c_size_t
@@ -165,7 +168,8 @@ def lib():
     if L.pf_sizeof_params() != C.sizeof(PfParams) or L.pf_sizeof_buffers() != C.sizeof(PfBuffers) or L.pf_sizeof_policy() != C.sizeof(PfPolicy) \
             or L.pf_sizeof_gae() != C.sizeof(PfGae) or L.pf_sizeof_traj_stats() != C.sizeof(PfTrajStats) \
             or L.pf_sizeof_ppo_loss() != C.sizeof(PfPpoLoss) or L.pf_sizeof_mlp() != C.sizeof(PfMlp) or L.pf_sizeof_adam() != C.sizeof(PfAdam) \
-            or L.pf_sizeof_world_sync() != C.sizeof(PfWorldSync) or L.pf_sizeof_ppo_grad() != C.sizeof(PfPpoGradArgs):
+            or L.pf_sizeof_world_sync() != C.sizeof(PfWorldSync) or L.pf_sizeof_ppo_grad() != C.sizeof(PfPpoGradArgs) \
+            or L.pf_sizeof_traj_stats_masked() != C.sizeof(PfTrajStatsMasked):
         raise PyFlytAmdError("struct layout mismatch between pyflyt_amd/_lib.py and include/pyflyt_amd.h")
     if L.pf_abi_version() != PF_ABI_VERSION:
         raise PyFlytAmdError("ABI version mismatch between pyflyt_amd/_lib.py and libpyflyt_amd.so")

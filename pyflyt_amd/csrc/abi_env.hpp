@@ -176,6 +176,7 @@ size_t pf_sizeof_buffers(void) { return sizeof(pf_buffers); }
 size_t pf_sizeof_policy(void) { return sizeof(pf_policy); }
 size_t pf_sizeof_gae(void) { return sizeof(pf_gae_args); }
 size_t pf_sizeof_traj_stats(void) { return sizeof(pf_traj_stats_args); }
+size_t pf_sizeof_traj_stats_masked(void) { return sizeof(pf_traj_stats_masked_args); }
 size_t pf_sizeof_ppo_loss(void) { return sizeof(pf_ppo_loss_args); }
 size_t pf_sizeof_mlp(void) { return sizeof(pf_mlp); }
 size_t pf_sizeof_ppo_grad(void) { return sizeof(pf_ppo_grad_args); }

@@ -1,4 +1,4 @@
-// abi_train.hpp -- the C ABI's training side: pf_policy_act, pf_gae, pf_traj_stats, pf_ppo_loss, pf_mlp_forward / pf_mlp_backward, pf_ppo_grad,
+// abi_train.hpp -- the C ABI's training side: pf_policy_act, pf_gae, pf_traj_stats / pf_traj_stats_masked, pf_ppo_loss, pf_mlp_forward / pf_mlp_backward, pf_ppo_grad,
 // pf_adam_step and pf_world_sync, each behind the checks and launches it shares with another. Host code.
 #pragma once
 #include <cmath>
@@ -85,13 +85,13 @@ int pf_gae(pf_ctx* ctx, const pf_gae_args* a, int k_steps, void* stream) {
   }
   return launched(ctx);
 }
-int pf_traj_stats(pf_ctx* ctx, const pf_traj_stats_args* a, int k_steps, void* stream) {
-  static const char* who = "pf_traj_stats";
-  if (int rc = traj_call_check(ctx, who, a, k_steps)) return rc;
+// pf_traj_stats and pf_traj_stats_masked behind traj_call_check: `masked` = validity is the [k][n] bytes of `valid` (and a->episode_start is NULL)
+static int traj_stats_launch(pf_ctx* ctx, const char* who, const pf_traj_stats_args* a, bool masked, const uint8_t* valid, int k_steps, void* stream) {
   const pf_params& P = ctx->P;
   const arg_ptr required[] = {{"reward", a->reward}, {"terminated", a->terminated}, {"truncated", a->truncated}, {"summary", a->summary},
                               {"carry_return", a->carry_return}, {"carry_length", a->carry_length}, {"carry_disc", a->carry_disc}, {nullptr, nullptr}};
   if (int rc = require_args(ctx, who, required)) return rc;
+  if (masked && !valid) return arg_fail(ctx, who, "valid (the [k][n] mask of the steps that are transitions) is required");
   if (!(a->gamma >= 0.0f && a->gamma <= 1.0f)) return arg_fail(ctx, who, "gamma must be finite and in [0, 1]");
   if (P.autoreset != PF_AUTORESET_NEXT_STEP && a->episode_start)
     return arg_fail(ctx, who, "episode_start must be NULL outside NEXT_STEP (no other mode has reset steps)");
@@ -105,19 +105,35 @@ int pf_traj_stats(pf_ctx* ctx, const pf_traj_stats_args* a, int k_steps, void* s
   const int waves = (ctx->n + 63) / 64;
   double* scan_part = ctx->ts_scratch;
   double* obs_part = ctx->ts_scratch + pf::ts_scan_words(ctx->n);
-  const pf::TsK K{a->gamma, a->reward, a->terminated, a->truncated, a->episode_start, a->carry_return, a->carry_length, a->carry_disc,
+  const uint8_t* bytes = masked ? valid : a->episode_start;  // (the kernels' one slot for either: traj_stats.hpp)
+  const pf::TsK K{a->gamma, a->reward, a->terminated, a->truncated, bytes, a->carry_return, a->carry_length, a->carry_disc,
                   a->ep_return_out, a->ep_length_out, a->ret_moments};
-  hipLaunchKernelGGL(next ? pf::ts_scan_kernel<true> : pf::ts_scan_kernel<false>, dim3(waves), dim3(64), 0, s, K, ctx->n, k_steps, scan_part);
+  using pf::kTsAll, pf::kTsMask, pf::kTsNext;
+  hipLaunchKernelGGL(masked ? pf::ts_scan_kernel<kTsMask> : next ? pf::ts_scan_kernel<kTsNext> : pf::ts_scan_kernel<kTsAll>, dim3(waves), dim3(64), 0, s, K,
+                     ctx->n, k_steps, scan_part);
   unsigned grid = 0;
   if (a->obs) {
     const size_t rows = (size_t)k_steps * (size_t)ctx->n;
     grid = pf::ts_obs_grid(rows * (size_t)D);
-    hipLaunchKernelGGL(next ? pf::ts_obs_kernel<true> : pf::ts_obs_kernel<false>, dim3(grid), dim3(pf::kTsObsBlock), 0, s, a->obs, a->terminated,
-                       a->truncated, a->episode_start, a->obs_moments, obs_part, rows, ctx->n, D);
+    hipLaunchKernelGGL(masked ? pf::ts_obs_kernel<kTsMask> : next ? pf::ts_obs_kernel<kTsNext> : pf::ts_obs_kernel<kTsAll>, dim3(grid), dim3(pf::kTsObsBlock),
+                       0, s, a->obs, a->terminated, a->truncated, bytes, a->obs_moments, obs_part, rows, ctx->n, D);
   }
   hipLaunchKernelGGL(pf::ts_finish_kernel, dim3(1), dim3(pf::kTsFinishBlock), 0, s, scan_part, waves, a->obs ? obs_part : nullptr, (int)grid, D,
                      a->summary, a->ret_moments, a->obs_moments);
   return launched(ctx);
+}
+int pf_traj_stats(pf_ctx* ctx, const pf_traj_stats_args* a, int k_steps, void* stream) {
+  static const char* who = "pf_traj_stats";
+  if (int rc = traj_call_check(ctx, who, a, k_steps)) return rc;
+  return traj_stats_launch(ctx, who, a, false, nullptr, k_steps, stream);
+}
+int pf_traj_stats_masked(pf_ctx* ctx, const pf_traj_stats_masked_args* a, int k_steps, void* stream) {
+  static const char* who = "pf_traj_stats_masked";
+  if (int rc = traj_call_check(ctx, who, a, k_steps)) return rc;
+  // (the block is pf_traj_stats_args with `valid` where episode_start stood; there is no episode_start here)
+  const pf_traj_stats_args u{a->gamma, a->reward, a->terminated, a->truncated, nullptr, a->obs, a->carry_return, a->carry_length, a->carry_disc,
+                             a->ep_return_out, a->ep_length_out, a->summary, a->ret_moments, a->obs_moments};
+  return traj_stats_launch(ctx, who, &u, true, a->valid, k_steps, stream);
 }
 // what pf_ppo_loss and pf_ppo_grad check of the loss's coefficients
 static int ppo_coef_check(pf_ctx* ctx, const char* who, float clip, float vf_coef, float ent_coef, int32_t normalize_advantage) {

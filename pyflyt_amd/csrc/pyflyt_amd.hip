@@ -9,7 +9,7 @@
 //   gae.hpp, traj_stats.hpp, ppo_loss.hpp, ppo_grad.hpp, adam.hpp, world_sync.hpp   the training operations
 //   abi_ctx.hpp     pf_ctx, the refusals, the argument tables, the current device, the per-lane launch
 //   abi_env.hpp     the choice of the env kernel and its launch, pf_ctx_create / destroy and the queries, pf_env_*, pf_aviary_*, pf_rollout*
-//   abi_train.hpp   pf_policy_act, pf_gae, pf_traj_stats, pf_ppo_loss, pf_mlp_*, pf_ppo_grad, pf_adam_step, pf_world_sync
+//   abi_train.hpp   pf_policy_act, pf_gae, pf_traj_stats, pf_traj_stats_masked, pf_ppo_loss, pf_mlp_*, pf_ppo_grad, pf_adam_step, pf_world_sync
 // Every header includes what it uses, so the order below is only the order of reading.
 #include "abi_ctx.hpp"
 #include "abi_env.hpp"

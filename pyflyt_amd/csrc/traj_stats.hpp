@@ -22,6 +22,12 @@
 // same whichever window a step falls in. The double reductions run in an order that (n, k, D) alone decide: the grid of the
 // observation kernel is a function of k n D, never of the device. No atomics. Selections are selects: the reward and the observation
 // row of an invalid step are loaded and then NOT chosen, so a NaN in them reaches nothing.
+//
+// pf_traj_stats_masked is the same three launches with a third source of validity (TsValid below): a [k][n] byte mask, pf_world_sync's
+// on the multi-agent envs. Its instantiations differ from the other two in where the validity bit comes from and in nothing else --
+// the scan loads one more byte per step and so takes windows of kTsWinMask steps, which no float32 sequence and no double sum
+// depends on; the observation kernel loads valid[row] where NEXT_STEP loads two flag bytes. With pf_gae's valid_out (NEXT_STEP) or all
+// ones (the other modes) as the mask, every output has the bits of pf_traj_stats.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -34,6 +40,7 @@
 namespace pf {
 
 constexpr int kTsWin = 16;            // steps per window of the scan
+constexpr int kTsWinMask = 12;        // the same where a step has a fourth load, its byte of `valid`: 48 loads in flight either way (the counter of outstanding vector-memory loads stops at 63)
 constexpr int kTsScanQ = 11;          // doubles a wave leaves: summary[8], then count / sum / sum of squares of G - shift over its valid steps
 constexpr int kTsScanStride = 12;     // (16-byte aligned rows)
 constexpr int kTsObsBlock = 256;
@@ -48,7 +55,7 @@ struct TsK {
   const float* reward;
   const uint8_t* terminated;
   const uint8_t* truncated;
-  const uint8_t* episode_start;
+  const uint8_t* episode_start;  // (kTsMask: `valid` [k][n] stands here, as in pf_traj_stats_masked_args)
   float* carry_return;
   int32_t* carry_length;
   float* carry_disc;
@@ -82,9 +89,14 @@ __device__ __forceinline__ double ts_wave_max(double x) {
   return x;
 }
 
-// NEXT: the context's auto-reset mode is NEXT_STEP (the only mode with invalid steps)
-template <bool NEXT>
+// Where a step's validity comes from. kTsAll: every step is valid (SAME_STEP, OFF); kTsNext: the context's auto-reset mode is NEXT_STEP,
+// a step is invalid where the one before it was done; kTsMask: pf_traj_stats_masked, one byte per step and lane says so.
+enum TsValid { kTsAll = 0, kTsNext = 1, kTsMask = 2 };
+
+template <TsValid V>
 __global__ __launch_bounds__(64) void ts_scan_kernel(TsK a, int n_lanes, int k, double* __restrict__ partials) {
+  constexpr bool NEXT = V == kTsNext, MASK = V == kTsMask;
+  constexpr int kWin = MASK ? kTsWinMask : kTsWin;
   const size_t n = (size_t)n_lanes;
   const size_t lane = (size_t)blockIdx.x * 64 + threadIdx.x;
   const bool live = lane < n;
@@ -96,24 +108,25 @@ __global__ __launch_bounds__(64) void ts_scan_kernel(TsK a, int n_lanes, int k, 
   uint32_t n_ep = 0, n_term = 0, n_trunc = 0, n_valid = 0, sum_len = 0;
   double sum_ret = 0.0, sum_sq = 0.0, g1 = 0.0, g2 = 0.0;
   float lo = INFINITY, hi = -INFINITY;
-  for (int s0 = 0; s0 < k; s0 += kTsWin) {  // (nothing of a window is carried round the loop)
-    float r[kTsWin];
-    uint32_t te[kTsWin], tr[kTsWin];  // (a register each, as in gae.hpp)
+  for (int s0 = 0; s0 < k; s0 += kWin) {  // (nothing of a window is carried round the loop)
+    float r[kWin];
+    uint32_t te[kWin], tr[kWin], vb[kWin];  // (a register each, as in gae.hpp; vb: the step's byte of `valid`, kTsMask only)
 #pragma unroll
-    for (int j = 0; j < kTsWin; ++j) {  // every load of the window; the slots past step k - 1 read row k - 1 again and are skipped below
+    for (int j = 0; j < kWin; ++j) {  // every load of the window; the slots past step k - 1 read row k - 1 again and are skipped below
       const int s = s0 + j < k ? s0 + j : k - 1;
       const size_t o = (size_t)s * n + i;
       r[j] = a.reward[o];
       te[j] = a.terminated[o];
       tr[j] = a.truncated[o];
+      vb[j] = MASK ? a.episode_start[o] : 0u;
     }
 #pragma unroll
-    for (int j = 0; j < kTsWin; ++j) {
+    for (int j = 0; j < kWin; ++j) {
       if (s0 + j < k) {  // (wave-uniform)
         const size_t o = (size_t)(s0 + j) * n + i;
         const bool term = te[j] != 0;
         const bool done = term || tr[j] != 0;
-        const bool valid = live && !(NEXT && prev_done);
+        const bool valid = MASK ? live && vb[j] != 0 : live && !(NEXT && prev_done);
         const float ret1 = ret + r[j];
         const float G1 = fmaf(a.gamma, G, r[j]);
         ret = valid ? ret1 : ret;
@@ -171,11 +184,13 @@ __global__ __launch_bounds__(64) void ts_scan_kernel(TsK a, int n_lanes, int k, 
 }
 
 // rows = k n rows of D floats; stride = the threads that work, a multiple of D (the last gridDim.x * kTsObsBlock - stride threads idle)
-template <bool NEXT>
+// kTsMask: episode_start is `valid` [k n], a flat row's index is its index there; terminated and truncated are not read
+template <TsValid V>
 __global__ __launch_bounds__(kTsObsBlock) void ts_obs_kernel(const float* __restrict__ obs, const uint8_t* __restrict__ terminated,
                                                               const uint8_t* __restrict__ truncated, const uint8_t* __restrict__ episode_start,
                                                               const double* __restrict__ obs_moments, double* __restrict__ partials, size_t rows,
                                                               int n_lanes, int D) {
+  constexpr bool NEXT = V == kTsNext, MASK = V == kTsMask;
   __shared__ double sh1[kTsObsBlock], sh2[kTsObsBlock];
   const size_t n = (size_t)n_lanes;
   const size_t g = (size_t)blockIdx.x * kTsObsBlock + threadIdx.x;
@@ -193,9 +208,10 @@ __global__ __launch_bounds__(kTsObsBlock) void ts_obs_kernel(const float* __rest
     // bytes of the row n above, or, for the first n rows, episode_start twice (es: episode_start, or any readable [n] bytes with
     // es_mask 0 where the caller gave none). The bytes are kept as loaded and combined where they are used: combining them next
     // to the loads would wait for them there (gae.hpp).
+    // kTsMask: one byte load, valid[row], in the first's place; the second is not issued.
     auto flag_ptr = [&](const uint8_t* flags, size_t rw) { return rw >= n ? flags + (rw - n) : es + rw; };
     auto take = [&](float x, uint32_t b1, uint32_t b2, size_t rw) {
-      const bool ok = !NEXT || ((b1 | b2) & (rw >= n ? 0xFFu : es_mask)) == 0;
+      const bool ok = MASK ? b1 != 0 : !NEXT || ((b1 | b2) & (rw >= n ? 0xFFu : es_mask)) == 0;
       const double d = (double)x - shift;
       s1 = s1 + (ok ? d : 0.0);
       s2 = s2 + (ok ? d * d : 0.0);
@@ -207,13 +223,13 @@ __global__ __launch_bounds__(kTsObsBlock) void ts_obs_kernel(const float* __rest
       for (int u = 0; u < kTsObsUnroll; ++u) {  // every load of the eight rows (nothing here waits)
         const size_t rw = row + (size_t)u * row_step;
         x[u] = obs[rw * (size_t)D + c];
-        b1[u] = NEXT ? *flag_ptr(terminated, rw) : 0u;
+        b1[u] = MASK ? episode_start[rw] : NEXT ? *flag_ptr(terminated, rw) : 0u;
         b2[u] = NEXT ? *flag_ptr(truncated, rw) : 0u;
       }
 #pragma unroll
       for (int u = 0; u < kTsObsUnroll; ++u) take(x[u], b1[u], b2[u], row + (size_t)u * row_step);
     }
-    for (; row < rows; row += row_step) take(obs[row * (size_t)D + c], NEXT ? *flag_ptr(terminated, row) : 0u, NEXT ? *flag_ptr(truncated, row) : 0u, row);
+    for (; row < rows; row += row_step) take(obs[row * (size_t)D + c], MASK ? episode_start[row] : NEXT ? *flag_ptr(terminated, row) : 0u, NEXT ? *flag_ptr(truncated, row) : 0u, row);
   }
   sh1[threadIdx.x] = s1;
   sh2[threadIdx.x] = s2;

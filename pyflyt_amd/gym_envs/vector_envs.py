@@ -28,6 +28,7 @@ import torch
 from .. import _checks as K
 from .. import _lib as L
 from ..engine import BatchEngine
+from ..moments import EpisodeStats
 from ..params import build_params
 from ..spaces import Box, Dict, batch_box
 
@@ -91,7 +92,7 @@ class LazyInfos(dict):
         return {k: (v.clone() if torch.is_tensor(v) else (v.materialize() if isinstance(v, LazyInfos) else v)) for k, v in self.items()}
 
 
-class _VecEnvBase:
+class _VecEnvBase(EpisodeStats):
     metadata = {"render_modes": [], "autoreset_mode": "next_step"}
     _vehicle = "quadx"
     _task = "hover"
@@ -147,9 +148,7 @@ class _VecEnvBase:
             moments = self.engine.made_moments()  # (traj_stats' running moments outlive the engine; its carries do not)
             self.engine.close()
             self._build(self._seed)
-            if moments is not None:
-                self.engine.obs_moments.copy_(moments[0])
-                self.engine.ret_moments.copy_(moments[1])
+            self._adopt_moments(moments)
         elif seed is not None and mask is None:
             # same seed: restart the event counters so that the rollout repeats exactly
             self.engine.state.zero_()
@@ -293,29 +292,6 @@ class _VecEnvBase:
         return dict(obs=t["obs_all"][:-1], actions=t["actions"], mean=t["mean"], logp=logp, values=values[:-1], advantages=adv, returns=ret,
                     valid=valid, reward=t["reward"], terminated=t["terminated"], truncated=t["truncated"],
                     last_value=values[-1], infos=self._infos_obj, **extra)
-
-    @property
-    def obs_rms(self):
-        """RunningMoments of the observation columns the policy saw on valid steps, updated by collect(stats=True)."""
-        from ..moments import RunningMoments
-
-        return RunningMoments(self.engine.obs_moments)
-
-    @property
-    def ret_rms(self):
-        """RunningMoments (dim 1) of the discounted return over the valid steps, updated by collect(stats=True)."""
-        from ..moments import RunningMoments
-
-        return RunningMoments(self.engine.ret_moments)
-
-    def episode_summary_dict(self):
-        """The last collect(stats=True)'s episode_summary as Python numbers (THE place that synchronises with the device): episodes,
-        return_mean / return_std / return_min / return_max, length_mean, terminated, truncated; the means are nan when no episode
-        finished in that call."""
-        c, s1, s2, lo, hi, ln, te, tr = self.engine._traj_state()["summary"].tolist()
-        mean = s1 / c if c else float("nan")
-        return dict(episodes=int(c), return_mean=mean, return_std=max(s2 / c - mean * mean, 0.0) ** 0.5 if c else float("nan"), return_min=lo,
-                    return_max=hi, length_mean=ln / c if c else float("nan"), terminated=int(te), truncated=int(tr))
 
     def close(self):
         self.engine.close()

@@ -5,6 +5,9 @@ device) and the PPO batch pf_gae makes of it. One copy of the code for both envs
 The batch is flat: a tensor is [k, n, ...] with n = num_envs * agents and lane = copy * agents + agent, so t.view(k, num_envs, agents,
 ...) reads it per copy and agent. `valid` is pf_world_sync's: False on the steps an agent sat out after its episode had ended, on
 the step that reset its copy, and on an opponent's lanes. pf_gae's own `valid` is all ones under auto-reset OFF and is not returned.
+
+collect(stats=True) hands that `valid` to pf_traj_stats_masked (BatchEngine.traj_stats(valid=...)): the episode accounting and the running
+moments behind obs_rms / ret_rms (moments.EpisodeStats, the vector envs' copy) see the valid steps and nothing else.
 """
 from __future__ import annotations
 
@@ -13,9 +16,10 @@ import torch
 from .. import _checks as K
 from ..engine import BatchEngine
 from ..gym_envs.vector_envs import LazyInfos
+from ..moments import EpisodeStats
 
 
-class WorldRollout:
+class WorldRollout(EpisodeStats):
     """Mixin of MAFixedwingDogfightEnv and MAQuadXHoverEnv: needs engine, num_possible_agents, possible_agents, agents, and
     _flat_infos() (the infos of the last step over the flat lanes)."""
 
@@ -43,9 +47,12 @@ class WorldRollout:
         self._after_worlds(k)
         return out
 
-    def _world_collect(self, policy, value_fn, k_steps, gamma, lam, opponent):
+    def _world_collect(self, policy, value_fn, k_steps, gamma, lam, opponent, stats=False, normalize_reward=False):
         if self._needs_reset:
             raise RuntimeError("call reset() before collect()")
+        K.boolean(stats, "stats")
+        K.boolean(normalize_reward, "normalize_reward")
+        stats = stats or normalize_reward
         BatchEngine._check_policy(policy)
         if not callable(value_fn):
             raise ValueError(f"value_fn must be callable (a float32 [M, D] tensor -> [M] or [M, 1]), got {type(value_fn).__name__}")
@@ -64,9 +71,15 @@ class WorldRollout:
                              f"got {(v.dtype, tuple(v.shape)) if torch.is_tensor(v) else type(v).__name__}")
         values = v.reshape(rows.shape[0], rows.shape[1]).contiguous()
         has_std = policy.log_std is not None
-        adv, ret, logp, _ = eng.gae(t["reward"], t["terminated"], t["truncated"], values, gamma=gamma, lam=lam,
+        extra, reward = {}, t["reward"]
+        if stats:
+            ep_ret, ep_len, summary = eng.traj_stats(t["reward"], t["terminated"], t["truncated"], gamma=gamma, obs=t["obs_all"][:-1], valid=t["valid"])
+            extra = dict(episode_return=ep_ret, episode_length=ep_len, episode_summary=summary)
+            if normalize_reward:
+                reward = extra["reward_scaled"] = t["reward"] / (self.ret_rms.var + 1e-8).sqrt()
+        adv, ret, logp, _ = eng.gae(reward, t["terminated"], t["truncated"], values, gamma=gamma, lam=lam,
                                     actions=t["actions"] if has_std else None, mean=t["mean"] if has_std else None,
                                     log_std=policy.log_std if has_std else None)
         return dict(obs=t["obs_all"][:-1], actions=t["actions"], mean=t["mean"], logp=logp, values=values[:-1], advantages=adv, returns=ret,
                     valid=t["valid"], reward=t["reward"], terminated=t["terminated"], truncated=t["truncated"], last_value=values[-1],
-                    infos=LazyInfos(self._flat_infos()))
+                    infos=LazyInfos(self._flat_infos()), **extra)

@@ -134,8 +134,10 @@ class MAFixedwingDogfightEnv(WorldRollout):
                 # current / past actions are created in __init__ and survive resets: groups 7-8, and 15 (entries 4, 5 of the
                 # six-wide action space, assisted_flight=False)
                 keep, keep45 = self.engine.state[7:9].clone(), self.engine.state[15].clone()
+                moments = self.engine.made_moments()
                 self.engine.close()
                 self._build(self._seed)
+                self._adopt_moments(moments)
                 self.engine.state[7:9] = keep
                 self.engine.state[15] = keep45
             # a seeded reset replays the seed's stream from its start (np.random.RandomState(seed) in the reference, :187):
@@ -203,7 +205,8 @@ class MAFixedwingDogfightEnv(WorldRollout):
         the latch as the last step left it, `agents` the full list (as after reset_envs), and step() / reset_envs() go on from there."""
         return self._world_rollout(policy, k_steps, opponent, store_mean)
 
-    def collect(self, policy, value_fn, k_steps: int, gamma: float = 0.99, lam: float = 0.95, opponent=None):
+    def collect(self, policy, value_fn, k_steps: int, gamma: float = 0.99, lam: float = 0.95, opponent=None, stats: bool = False,
+                normalize_reward: bool = False):
         """One PPO batch from rollout()'s loop, as the vector envs' collect(): `value_fn` (a float32 [M, D] tensor -> [M] or [M, 1])
         runs under torch.no_grad() on all k + 1 observation rows, pf_gae (BatchEngine.gae) supplies advantages, returns and logp.
         Returns a dict with the vector envs' keys: obs [k, n, D] the policy's inputs, actions, mean, logp (None without a log_std),
@@ -212,9 +215,20 @@ class MAFixedwingDogfightEnv(WorldRollout):
         own is all ones without an auto-reset mode): mask the losses with it -- pyflyt_amd.ppo_loss(env, ..., batch) does. A valid step's
         advantage depends on valid steps only: an episode's last step cuts the recursion, and a truncated aircraft bootstraps from
         its terminal observation, which the reset never overwrites (it lands in the row of the reset step).
-        `stats=` and `normalize_reward=` do not exist here: pf_traj_stats under auto-reset OFF counts every step, so the steps a
-        finished aircraft sits out would be counted into its next episode's return and length."""
-        return self._world_collect(policy, value_fn, k_steps, gamma, lam, opponent)
+        stats=True runs pf_traj_stats_masked (BatchEngine.traj_stats(valid=...)) on the same trajectory before pf_gae, with `valid` as
+        the mask, and adds episode_return, episode_length [k, n] (the finished episode's return and length where an episode ended in
+        a valid step, 0 elsewhere) and episode_summary ([8] float64 on the device; episode_summary_dict() reads it back); it updates
+        the running moments behind obs_rms (the columns of the policy's inputs) and ret_rms (the discounted return, with this call's
+        gamma) over the valid steps. normalize_reward=True implies stats, hands pf_gae reward / sqrt(ret_rms.var + 1e-8) with the
+        moments AFTER this batch's update, and adds it as reward_scaled; reward stays raw. The steps a finished aircraft sits out and
+        the step that resets its copy are in no return, length or moment, whatever their flags and rewards read. The per-lane
+        carries need nothing extra: a copy is reset only after every one of its aircraft finished in a valid step, which zeroed
+        that lane's carries; an opponent's lanes are never valid, so their carries stay zero and they are in no statistic. The
+        episode accounting is carried from one collect(stats=True) to the next and sees only their steps: a step(), rollout() or
+        collect() without stats in between advances the env behind its back, and the first episode_return / episode_length after
+        it would lack those steps -- reset() the env before switching. reset() and reset_envs() zero the carries of the lanes they
+        reset; reset(seed=other) keeps the running moments."""
+        return self._world_collect(policy, value_fn, k_steps, gamma, lam, opponent, stats, normalize_reward)
 
     # ------------------------------------------------------------------ ma_fixedwing_base_env.py:272-334
     def step(self, actions: dict):

@@ -135,8 +135,10 @@ class MAQuadXHoverEnv(WorldRollout):
         if seed is not None and int(seed) != self._seed:
             self._seed = int(seed)
             keep = self.engine.state[12:16].clone()  # spawn poses and the action memories survive
+            moments = self.engine.made_moments()
             self.engine.close()
             self._build(self._seed)
+            self._adopt_moments(moments)
             self.engine.state[12:16] = keep
         if seed is not None:
             self._policy_step = 0
@@ -164,14 +166,19 @@ class MAQuadXHoverEnv(WorldRollout):
         advances by k_steps per call and restarts with reset(seed=...). Afterwards `agents` is the full list."""
         return self._world_rollout(policy, k_steps, None, store_mean)
 
-    def collect(self, policy, value_fn, k_steps: int, gamma: float = 0.99, lam: float = 0.95):
+    def collect(self, policy, value_fn, k_steps: int, gamma: float = 0.99, lam: float = 0.95, stats: bool = False, normalize_reward: bool = False):
         """One PPO batch from rollout()'s loop, as the vector envs' collect(): `value_fn` (a float32 [M, D] tensor -> [M] or [M, 1])
         runs under torch.no_grad() on all k + 1 observation rows, pf_gae (BatchEngine.gae) supplies advantages, returns and logp.
         Returns a dict with the vector envs' keys (obs, actions, mean, logp, values, advantages, returns, valid, reward, terminated,
         truncated, last_value, infos), flat as in rollout(): t.view(k, num_envs, agents, ...). `valid` is rollout()'s
-        (pf_world_sync's): mask the losses with it. `stats=` and `normalize_reward=` do not exist here: pf_traj_stats under
-        auto-reset OFF counts every step, so the steps a finished drone sits out would be counted into its next episode."""
-        return self._world_collect(policy, value_fn, k_steps, gamma, lam, None)
+        (pf_world_sync's): mask the losses with it.
+        stats=True adds episode_return, episode_length [k, n] and episode_summary and updates obs_rms / ret_rms over the valid steps;
+        normalize_reward=True implies it, hands pf_gae reward / sqrt(ret_rms.var + 1e-8) and adds reward_scaled -- both exactly as
+        MAFixedwingDogfightEnv.collect describes them (pf_traj_stats_masked with `valid` as the mask: the steps a finished drone sits
+        out and the step that resets its copy are in no return, length or moment; a copy is reset only after every drone finished in
+        a valid step, which zeroed that lane's carries). The accounting sees the steps of collect(stats=True) only: reset() before
+        mixing it with step(), rollout() or a collect() without stats."""
+        return self._world_collect(policy, value_fn, k_steps, gamma, lam, None, stats, normalize_reward)
 
     # ------------------------------------------------------------------ ma_quadx_base_env.py:309-371
     def step(self, actions: dict):

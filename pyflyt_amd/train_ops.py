@@ -1,4 +1,4 @@
-"""The training operations of a BatchEngine -- pf_gae, pf_traj_stats, pf_ppo_loss, pf_mlp_forward / pf_mlp_backward, pf_adam_step --
+"""The training operations of a BatchEngine -- pf_gae, pf_traj_stats / pf_traj_stats_masked, pf_ppo_loss, pf_mlp_forward / pf_mlp_backward, pf_adam_step --
 and the plumbing they share with the env level in engine.py: the tensor check bound to the engine's device, the launch wrapper and
 the state an engine makes at first use. A base class without __init__: everything here works on an engine that has only `n`,
 `device`, `params` and `_ctx` (and `obs_dim` for traj_stats), which is how the CPU tests reach the refusals.
@@ -151,11 +151,14 @@ class TrainOps:
         ts["obs_moments"].zero_()
         ts["ret_moments"].zero_()
 
-    def traj_stats(self, reward, terminated, truncated, gamma: float = 0.99, episode_start=None, obs=None, store_steps: bool = True):
+    def traj_stats(self, reward, terminated, truncated, gamma: float = 0.99, episode_start=None, obs=None, store_steps: bool = True, valid=None):
         """pf_traj_stats: the return and length of every episode that finished inside a trajectory, and the running moments of a
         reward and an observation normaliser (include/pyflyt_amd.h has the semantics). reward / terminated / truncated [k, n] as a
         rollout wrote them; episode_start [n]: NEXT_STEP only, as for gae(); obs [k, n, D]: the observations the policy saw (collect's
-        obs), or None for no observation moments; store_steps=False skips the two per-step outputs. The engine owns the per-lane
+        obs), or None for no observation moments; store_steps=False skips the two per-step outputs. valid [k, n] bool / uint8: the
+        steps that are transitions, given instead of derived from the auto-reset mode -- the call is then pf_traj_stats_masked (the
+        multi-agent rollouts' valid, pf_world_sync's; flags, reward and observation of the other steps are ignored), in any mode,
+        and episode_start must be None. The engine owns the per-lane
         carries (a trajectory may be split over calls; env_reset zeroes the lanes it resets), summary and the running moments
         (self.obs_moments, self.ret_moments; reset_moments() empties them). The carries describe the lanes' open episodes only if
         EVERY env step since the last reset goes through traj_stats, in order: steps taken by env_step, rollout or a collect without
@@ -164,22 +167,29 @@ class TrainOps:
         int32 -- both None without store_steps --, summary [8] float64): overwritten by the next call with the same k."""
         k = self._traj_args(reward, terminated, truncated)
         K.unit_interval(gamma, "gamma")
+        if valid is not None and episode_start is not None:
+            raise ValueError("valid and episode_start do not come together (valid says which steps are transitions; there is no reset step to derive)")
         self._episode_start(episode_start)
+        K.tensor(self.device, valid, "valid", (k, self.n), K.FLAGS)
         if obs is not None:
             K.tensor(self.device, obs, "obs", (k, self.n, self.obs_dim), required=f"{{name}} must be a float32 tensor of shape (k, {self.n}, D)")
         ts = self._traj_state()
         if store_steps and ts["k"] != k:
             ts.update(k=k, episode_return=torch.empty(k, self.n, dtype=torch.float32, device=self.device),
                       episode_length=torch.empty(k, self.n, dtype=torch.int32, device=self.device))
-        a = L.PfTrajStats()
+        a = L.PfTrajStats() if valid is None else L.PfTrajStatsMasked()
         a.gamma = float(gamma)
-        a.reward, a.terminated, a.truncated, a.episode_start = _ptr(reward), _ptr(terminated), _ptr(truncated), _ptr(episode_start)
+        a.reward, a.terminated, a.truncated = _ptr(reward), _ptr(terminated), _ptr(truncated)
+        if valid is None:
+            a.episode_start = _ptr(episode_start)
+        else:
+            a.valid = _ptr(valid)
         a.obs, a.obs_moments = _ptr(obs), (_ptr(ts["obs_moments"]) if obs is not None else None)
         a.carry_return, a.carry_length, a.carry_disc = _ptr(ts["carry_return"]), _ptr(ts["carry_length"]), _ptr(ts["carry_disc"])
         a.ep_return_out = _ptr(ts["episode_return"]) if store_steps else None
         a.ep_length_out = _ptr(ts["episode_length"]) if store_steps else None
         a.summary, a.ret_moments = _ptr(ts["summary"]), _ptr(ts["ret_moments"])
-        self._launch(self.lib.pf_traj_stats, C.byref(a), k)
+        self._launch(self.lib.pf_traj_stats if valid is None else self.lib.pf_traj_stats_masked, C.byref(a), k)
         return (ts["episode_return"] if store_steps else None), (ts["episode_length"] if store_steps else None), ts["summary"]
 
     # ------------------------------------------------------------------ the loss

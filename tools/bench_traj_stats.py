@@ -10,6 +10,16 @@ SAME_STEP. One process, device events around batches of calls (at least 0.3 s pe
 and repeated three times; median and spread. (a) and (b) are checked against each other before they are timed. Prints one JSON line
 and writes profiles/traj_stats/bench.json with the algorithmic bytes of pf_traj_stats and the fraction of the 8 TB/s HBM peak they
 make at the time of (a).
+
+--masked: pf_traj_stats_masked against pf_traj_stats of the same library, on the NEXT_STEP trajectory above with pf_gae's valid_out as
+the mask (so both compute the same bits, which is checked before they are timed), at the same shapes:
+
+  a       engine.traj_stats(..., episode_start=..., obs=...)   pf_traj_stats
+  m       engine.traj_stats(..., valid=..., obs=...)           pf_traj_stats_masked
+  a_scan  (a) without obs: the scan and the finish kernel only
+  m_scan  (m) without obs
+
+Legs alternated and timed as above. Writes profiles/ma_stats/bench.json; no threshold, the numbers are recorded.
 """
 import argparse
 import json
@@ -105,21 +115,71 @@ def make_legs(n, mode):
         assert ((ours_block[1:1 + w] - mean).abs() <= 1e-5 * (mean.abs() + (m2 / cnt).sqrt()) + 1e-9).all()
         assert ((ours_block[1 + w:] - m2).abs() <= 1e-5 * (m2 + cnt * mean * mean) + 1e-9).all()
     legs = {"a": leg_a, "b": leg_b, "c": lambda: env.collect(pol, critic, K, stats=True), "d": lambda: env.collect(pol, critic, K)}
-    return legs, env
+    return legs, env, dict(x, episode_start=es)
+
+
+def make_masked_legs(n):
+    _, env, x = make_legs(n, "next_step")  # (the trajectory of legs a and b)
+    eng = env.engine
+    valid = eng.gae(x["reward"], x["terminated"], x["truncated"], torch.zeros(K + 1, n, device=env.device), episode_start=x["episode_start"])[3].clone()
+    flags = (x["reward"], x["terminated"], x["truncated"])
+
+    def run(obs, **how):
+        return eng.traj_stats(*flags, gamma=0.99, obs=obs, **how)
+
+    masked = {"a": lambda: run(x["obs"], episode_start=x["episode_start"]), "m": lambda: run(x["obs"], valid=valid),
+              "a_scan": lambda: run(None, episode_start=x["episode_start"]), "m_scan": lambda: run(None, valid=valid)}
+    state = ("carry_return", "carry_length", "carry_disc", "obs_moments", "ret_moments")
+    got = []
+    for name in ("a", "m"):  # the same bits from both, from the empty state
+        ts = eng._traj_state()
+        for key in state:
+            ts[key].zero_()
+        out = masked[name]()
+        got.append([t.clone() for t in out] + [ts[key].clone() for key in state])
+    torch.cuda.synchronize()
+    assert all(torch.equal(p.view(torch.uint8), q.view(torch.uint8)) for p, q in zip(*got))
+    return masked, env, float(valid.float().mean())
+
+
+def main_masked(args):
+    res = {"workload": "pf_traj_stats_masked (m) against pf_traj_stats (a), QuadX-Hover (D = 21) NEXT_STEP trajectory, k = 100, valid = pf_gae's valid_out; "
+                       "_scan: without obs (scan + finish only)", "unit": "us per call", "cases": {}}
+    for n in (int(v) for v in args.sizes.split(",")):
+        legs, env, share = make_masked_legs(n)
+        samples = {name: [] for name in legs}
+        for _ in range(args.repeats):
+            for name, fn in legs.items():
+                samples[name].append(time_leg(fn))
+        case = {name: {"us": sorted(v)[len(v) // 2], "min": min(v), "max": max(v), "samples": v} for name, v in samples.items()}
+        case["valid_share"] = share
+        case["masked_over_unmasked"] = case["m"]["us"] / case["a"]["us"]
+        case["masked_over_unmasked_scan"] = case["m_scan"]["us"] / case["a_scan"]["us"]
+        res["cases"][f"{n}/next_step"] = case
+        del legs
+        env.close()
+        torch.cuda.empty_cache()
+    line = json.dumps(res)
+    print(line)
+    os.makedirs(os.path.join(ROOT, "profiles", "ma_stats"), exist_ok=True)
+    open(os.path.join(ROOT, "profiles", "ma_stats", "bench.json"), "w").write(line + "\n")
 
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--masked", action="store_true", help="pf_traj_stats_masked against pf_traj_stats (see the module docstring)")
     ap.add_argument("--legs", default="abcd")
     ap.add_argument("--sizes", default="65536,524288")
     ap.add_argument("--modes", default="next_step,same_step")
     ap.add_argument("--repeats", type=int, default=3)
     args = ap.parse_args()
+    if args.masked:
+        return main_masked(args)
     res = {"workload": "QuadX-Hover (D = 21), 64-64 tanh policy, Gaussian head, 64-unit critic, k = 100", "unit": "us per call", "hbm_peak_bytes_per_s": HBM_PEAK,
            "cases": {}}
     for n in (int(x) for x in args.sizes.split(",")):
         for mode in args.modes.split(","):
-            legs, env = make_legs(n, mode)
+            legs, env, _ = make_legs(n, mode)
             legs = {name: fn for name, fn in legs.items() if name in args.legs}
             samples = {name: [] for name in legs}
             for _ in range(args.repeats):
