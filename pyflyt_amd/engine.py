@@ -115,6 +115,21 @@ class BatchEngine(TrainOps):
         b.out_contact_peers = _ptr(self.out_contact_peers)
         return b
 
+    @staticmethod
+    def _block(src):
+        """A private copy of the pf_buffers block `src` (self._buffers(...) fills the ONE shared block, which the next call fills
+        again): what outlives the call that made it -- a prepared step, the closed loop's row cursor."""
+        b = L.PfBuffers()
+        C.memmove(C.byref(b), C.byref(src), C.sizeof(L.PfBuffers))
+        return b
+
+    @staticmethod
+    def _point_at(b, t):
+        """Point the block `b` at the trajectory tensors `t`: a launch that runs all k steps writes their rows itself."""
+        b.obs, b.reward, b.terminated, b.truncated = _ptr(t["obs"]), _ptr(t["reward"]), _ptr(t["terminated"]), _ptr(t["truncated"])
+        b.final_obs, b.final_info = _ptr(t["final_obs"]), _ptr(t["final_info"])
+        return b
+
     def _sp_dim(self, mode=None):
         """Floats per drone in the setpoint buffer (fixedwing.py:221-224, rocket.py:228): csrc's setpoint_width."""
         mode = self.params.flight_mode if mode is None else mode
@@ -193,8 +208,7 @@ class BatchEngine(TrainOps):
         if not torch.is_tensor(actions):
             raise ValueError(f"actions must be a float32 tensor of shape {(self.n, self.action_dim)} on {self.device}, got {type(actions).__name__}")
         K.tensor(self.device, actions, "actions", (self.n, self.action_dim))
-        b = L.PfBuffers()
-        C.memmove(C.byref(b), C.byref(self._buffers(actions=actions)), C.sizeof(L.PfBuffers))
+        b = self._block(self._buffers(actions=actions))
         if len(self._prepared) >= max(8, min(_PREPARED_MAX, _PREPARED_BYTES // (16 * self.n))):
             self._prepared.clear()
         hit = self._prepared[id(actions)] = (actions, C.byref(b), b, actions.data_ptr())
@@ -210,8 +224,7 @@ class BatchEngine(TrainOps):
         if self.params.noise_mode == L.NOISE_INJECT:
             raise ValueError("prepare_step: PF_NOISE_INJECT passes per-step noise tensors; use env_step")
         K.tensor(self.device, actions, "actions", (self.n, self.action_dim))
-        b = L.PfBuffers()
-        C.memmove(C.byref(b), C.byref(self._buffers(actions=actions)), C.sizeof(L.PfBuffers))
+        b = self._block(self._buffers(actions=actions))
         fn, ctx, ref, check = self.lib.pf_env_step, self._ctx, C.byref(b), L.check
 
         def launch(stream_ptr):
@@ -244,9 +257,7 @@ class BatchEngine(TrainOps):
         t = self._traj_tensors(k)
         K.tensor(self.device, actions, "actions", (k, self.n, self.action_dim))
         keep = store_actions and actions is None  # (the kernels sample in registers; the draws are written out only on request)
-        b = self._buffers(actions=actions, actions_out=t["actions"] if keep else None)
-        b.obs, b.reward, b.terminated, b.truncated = _ptr(t["obs"]), _ptr(t["reward"]), _ptr(t["terminated"]), _ptr(t["truncated"])
-        b.final_obs, b.final_info = _ptr(t["final_obs"]), _ptr(t["final_info"])
+        b = self._point_at(self._buffers(actions=actions, actions_out=t["actions"] if keep else None), t)
         self._launch(self.lib.pf_rollout, C.byref(b), k, int(step_index0) & 0xFFFFFFFF)
         self._cur_obs = t["obs"][k - 1]
         return t["obs"], t["reward"], t["terminated"], t["truncated"], (t["actions"] if actions is None and store_actions else actions)
@@ -327,7 +338,7 @@ class BatchEngine(TrainOps):
         multi-agent tasks (dogfight, multi-agent hover), which exist with auto-reset OFF only, are refused here: their loop is
         rollout_policy_worlds (whole worlds reset on the device), or policy_act and env_step with the culling by hand."""
         q, k, _ = self._closed_loop(policy, k_steps, False)
-        return self._rollout_with(self._launch_policy_steps, q, k, step_index0, store_mean)
+        return self._rollout_with(self._launch_steps, q, k, step_index0, store_mean)
 
     def _rollout_with(self, launch, q, k, step_index0, store_mean):
         """Either closed loop into the trajectory tensors the rollouts share, and what both return. (The means are as wide as the
@@ -367,27 +378,48 @@ class BatchEngine(TrainOps):
             raise ValueError(f"fused must be None, True or False, got {fused!r}")
         return fused
 
-    def _launch_policy_steps(self, q, t, k, step_index0, mean):
-        """k x (pf_policy_act, pf_env_step) into the trajectory tensors `t`, acting first on the engine's current observation: the
-        act of step s reads the row the env wrote at step s - 1, the env's buffer block points at the rows of step s."""
-        b = self._buffers()
-        act, step, ctx, qref, bref = self.lib.pf_policy_act, self.lib.pf_env_step, self._ctx, C.byref(q), C.byref(b)
-        n, D, A = self.n, self.obs_dim, self.action_dim
+    def _launch_steps(self, q, t, k, step_index0, mean, A=None, qo=None, opp_lanes=None):
+        """THE stepwise closed loop: k x (pf_policy_act, pf_env_step) into the trajectory tensors `t`, acting first on the engine's
+        current observation -- the act of step s reads the row the env wrote at step s - 1, the env's buffer block (a private copy:
+        nothing else sees the row cursor) points at the rows of step s, final_obs / final_info rows included where `t` has them.
+        With `A` the lanes are worlds of A (auto-reset OFF): every step adds pf_world_sync on its row and pf_env_reset of the worlds
+        that were waiting, whose block points at the observation row of the step; with `qo` and `opp_lanes` the opponent's
+        pf_policy_act (the same step index) and one merge come between the act and the step. One device selection and one stream
+        handle for all the calls; no allocation inside the loop, nothing synchronises."""
+        b = self._block(self._buffers())
+        lib, ctx, check, qref, bref = self.lib, self._ctx, L.check, C.byref(q), C.byref(b)
+        act, step = lib.pf_policy_act, lib.pf_env_step
+        n, D, W = self.n, self.obs_dim, self.action_dim
         p_obs, p_act, p_rew = t["obs"].data_ptr(), t["actions"].data_ptr(), t["reward"].data_ptr()
         p_term, p_trunc = t["terminated"].data_ptr(), t["truncated"].data_ptr()
         p_fobs = t["final_obs"].data_ptr() if t["final_obs"] is not None else None
         p_finfo = t["final_info"].data_ptr() if t["final_info"] is not None else None
         p_mean = mean.data_ptr() if mean is not None else None
+        if A is not None:
+            br, w = self._block(b), L.PfWorldSync()
+            sync, reset, brref, wref, p_valid = lib.pf_world_sync, lib.pf_env_reset, C.byref(br), C.byref(w), t["valid"].data_ptr()
+            w.done, w.reset_out, w.exclude = self.world_done.data_ptr(), t["reset"].data_ptr(), _ptr(opp_lanes)
+            p_mask = C.c_void_p(t["reset"].data_ptr())
+        opp = None
+        if qo is not None:
+            opp = self._lazy("_opp_act", lambda: torch.empty(n, W, dtype=torch.float32, device=self.device), keep=lambda o: o.shape[1] == W)
+            qo.mean_out, p_opp, oref, pick = None, C.c_void_p(opp.data_ptr()), C.byref(qo), opp_lanes.bool().view(n, 1)
         cur = self._cur_obs.data_ptr()
         with torch.cuda.device(self.device):
             stream = self._stream()
             for s in range(k):
+                step_index = (int(step_index0) + s) & 0xFFFFFFFF
                 q.obs0 = cur
-                q.mean_out = p_mean + 4 * n * A * s if p_mean is not None else None
-                a = p_act + 4 * n * A * s
-                rc = act(ctx, qref, a, (int(step_index0) + s) & 0xFFFFFFFF, stream)
+                q.mean_out = p_mean + 4 * n * W * s if p_mean is not None else None
+                a = p_act + 4 * n * W * s
+                rc = act(ctx, qref, a, step_index, stream)
                 if rc:
-                    L.check(rc, ctx)
+                    check(rc, ctx)
+                if opp is not None:
+                    qo.obs0 = cur
+                    check(act(ctx, oref, p_opp, step_index, stream), ctx)
+                    row = t["actions"][s]
+                    torch.where(pick, opp, row, out=row)  # (the merge: one launch on the same stream)
                 cur = p_obs + 4 * n * D * s
                 b.actions, b.obs, b.reward = a, cur, p_rew + 4 * n * s
                 b.terminated, b.truncated = p_term + n * s, p_trunc + n * s
@@ -395,18 +427,41 @@ class BatchEngine(TrainOps):
                     b.final_obs, b.final_info = p_fobs + 4 * n * D * s, p_finfo + 8 * n * s
                 rc = step(ctx, bref, stream)
                 if rc:
-                    L.check(rc, ctx)
-        self._cur_obs = t["obs"][k - 1]
+                    check(rc, ctx)
+                if A is not None:
+                    w.terminated, w.truncated, w.reward, w.valid_out = b.terminated, b.truncated, b.reward, p_valid + n * s
+                    check(sync(ctx, wref, A, stream), ctx)
+                    br.obs = cur
+                    check(reset(ctx, brref, p_mask, stream), ctx)
+        if A is None:
+            self._cur_obs = t["obs"][k - 1]
+        else:
+            # the last row becomes self.obs: a masked env_reset (reset_envs) writes the lanes it resets THERE and leaves the others, so
+            # the tensor it writes must hold every lane's current observation -- as after an env_step, not k steps old
+            self.obs.copy_(t["obs"][k - 1])
+            self._cur_obs = self.obs
 
     def _launch_policy(self, q, t, k, step_index0, mean):
         """pf_rollout_policy into the trajectory tensors `t`, acting first on the engine's current observation."""
         q.obs0 = self._cur_obs.data_ptr()
         q.mean_out = mean.data_ptr() if mean is not None else None
-        b = self._buffers(actions_out=t["actions"])
-        b.obs, b.reward, b.terminated, b.truncated = _ptr(t["obs"]), _ptr(t["reward"]), _ptr(t["terminated"]), _ptr(t["truncated"])
-        b.final_obs, b.final_info = _ptr(t["final_obs"]), _ptr(t["final_info"])
+        b = self._point_at(self._buffers(actions_out=t["actions"]), t)
         self._launch(self.lib.pf_rollout_policy, C.byref(b), C.byref(q), k, int(step_index0) & 0xFFFFFFFF)
         self._cur_obs = t["obs"][k - 1]
+
+    def _collect_into(self, t, launch):
+        """What the collect_* calls share: row 0 of `t`'s obs_all becomes a copy of the engine's current observation (the previous
+        call's last row, in this buffer or another, or self.obs) and IS the current observation while launch(t) runs, which leaves
+        _cur_obs on the last row it wrote. Refused: the engine's current observation is where it was."""
+        cur = self._cur_obs
+        t["obs_all"][0].copy_(cur)
+        self._cur_obs = t["obs_all"][0]
+        try:
+            launch(t)
+        except L.PyFlytAmdError:
+            self._cur_obs = cur
+            raise
+        return t
 
     def collect_rollout(self, policy, k_steps: int, step_index0: int = 0, fused=None):
         """rollout_policy for a learner: the same launch (`fused`: None = where the library has it, QuadX-Hover / QuadX-Waypoints, and
@@ -418,15 +473,8 @@ class BatchEngine(TrainOps):
         mean, final_obs / final_info under SAME_STEP), overwritten by the next call with the same k_steps."""
         q, k, fused = self._closed_loop(policy, k_steps, fused)
         t = self._lazy("_ctraj", lambda: self._new_traj(k, k + 1, mean=True), keep=lambda t: t["k"] == k)
-        cur = self._cur_obs
-        t["obs_all"][0].copy_(cur)  # (the previous call's last row, in this buffer or another, or self.obs)
-        self._cur_obs = t["obs_all"][0]
-        try:
-            (self._launch_policy if fused else self._launch_policy_steps)(q, t, k, step_index0, t["mean"])
-        except L.PyFlytAmdError:  # (refused: the engine's current observation is where it was)
-            self._cur_obs = cur
-            raise
-        return t
+        launch = self._launch_policy if fused else self._launch_steps
+        return self._collect_into(t, lambda t: launch(q, t, k, step_index0, t["mean"]))
 
     # ------------------------------------------------------------------ multi-agent worlds
     @property
@@ -506,7 +554,7 @@ class BatchEngine(TrainOps):
         q, qo, k, A = self._closed_loop_worlds(policy, k_steps, agents_per_world, opponent, opponent_lanes)
         t = self._lazy("_wtraj", lambda: self._new_world_traj(k, k), keep=lambda t: t["k"] == k)
         mean = self._traj_mean(t) if store_mean else None
-        self._launch_policy_worlds(q, qo, opponent_lanes, t, k, A, step_index0, mean)
+        self._launch_steps(q, t, k, step_index0, mean, A, qo, opponent_lanes)
         out = (t["obs"], t["reward"], t["terminated"], t["truncated"], t["actions"], t["valid"])
         return out + (mean,) if store_mean else out
 
@@ -517,67 +565,13 @@ class BatchEngine(TrainOps):
         obs_all[1:], reward, terminated, truncated, actions, mean) plus valid [k, n] bool."""
         q, qo, k, A = self._closed_loop_worlds(policy, k_steps, agents_per_world, opponent, opponent_lanes)
         t = self._lazy("_wctraj", lambda: self._new_world_traj(k, k + 1), keep=lambda t: t["k"] == k)
-        cur = self._cur_obs
-        t["obs_all"][0].copy_(cur)
-        self._cur_obs = t["obs_all"][0]
-        try:
-            self._launch_policy_worlds(q, qo, opponent_lanes, t, k, A, step_index0, self._traj_mean(t))
-        except L.PyFlytAmdError:  # (refused: the engine's current observation is where it was)
-            self._cur_obs = cur
-            raise
-        return t
+        return self._collect_into(t, lambda t: self._launch_steps(q, t, k, step_index0, self._traj_mean(t), A, qo, opponent_lanes))
 
     def _new_world_traj(self, k, obs_rows):
         t = self._new_traj(k, obs_rows, mean=False)
         t["valid"] = torch.empty(k, self.n, dtype=torch.bool, device=self.device)
         t["reset"] = torch.empty(self.n, dtype=torch.uint8, device=self.device)  # (this step's reset mask: world_sync writes it, the reset reads it)
         return t
-
-    def _launch_policy_worlds(self, q, qo, opp_lanes, t, k, A, step_index0, mean):
-        """k x (pf_policy_act [, the opponent's and the merge], pf_env_step, pf_world_sync, pf_env_reset) into the trajectory tensors
-        `t`, acting first on the engine's current observation. The reset's buffer block points at the observation row of the step."""
-        b = L.PfBuffers()
-        C.memmove(C.byref(b), C.byref(self._buffers()), C.sizeof(L.PfBuffers))
-        br = L.PfBuffers()
-        C.memmove(C.byref(br), C.byref(b), C.sizeof(L.PfBuffers))
-        w = L.PfWorldSync()
-        lib, ctx, qref, bref, brref, wref = self.lib, self._ctx, C.byref(q), C.byref(b), C.byref(br), C.byref(w)
-        n, D, W = self.n, self.obs_dim, self.action_dim
-        p_obs, p_act, p_rew = t["obs"].data_ptr(), t["actions"].data_ptr(), t["reward"].data_ptr()
-        p_term, p_trunc, p_valid = t["terminated"].data_ptr(), t["truncated"].data_ptr(), t["valid"].data_ptr()
-        p_mean = mean.data_ptr() if mean is not None else None
-        w.done, w.reset_out, w.exclude = self.world_done.data_ptr(), t["reset"].data_ptr(), _ptr(opp_lanes)
-        p_mask = C.c_void_p(t["reset"].data_ptr())
-        opp = None
-        if qo is not None:
-            opp = self._lazy("_opp_act", lambda: torch.empty(n, W, dtype=torch.float32, device=self.device), keep=lambda o: o.shape[1] == W)
-            qo.mean_out, p_opp, oref, pick = None, C.c_void_p(opp.data_ptr()), C.byref(qo), opp_lanes.bool().view(n, 1)
-        cur = self._cur_obs.data_ptr()
-        with torch.cuda.device(self.device):
-            stream = self._stream()
-            for s in range(k):
-                step_index = (int(step_index0) + s) & 0xFFFFFFFF
-                q.obs0 = cur
-                q.mean_out = p_mean + 4 * n * W * s if p_mean is not None else None
-                a = p_act + 4 * n * W * s
-                L.check(lib.pf_policy_act(ctx, qref, a, step_index, stream), ctx)
-                if opp is not None:
-                    qo.obs0 = cur
-                    L.check(lib.pf_policy_act(ctx, oref, p_opp, step_index, stream), ctx)
-                    row = t["actions"][s]
-                    torch.where(pick, opp, row, out=row)  # (the merge: one launch on the same stream)
-                cur = p_obs + 4 * n * D * s
-                b.actions, b.obs, b.reward = a, cur, p_rew + 4 * n * s
-                b.terminated, b.truncated = p_term + n * s, p_trunc + n * s
-                L.check(lib.pf_env_step(ctx, bref, stream), ctx)
-                w.terminated, w.truncated, w.reward, w.valid_out = b.terminated, b.truncated, b.reward, p_valid + n * s
-                L.check(lib.pf_world_sync(ctx, wref, A, stream), ctx)
-                br.obs = cur
-                L.check(lib.pf_env_reset(ctx, brref, p_mask, stream), ctx)
-        # the last row becomes self.obs: a masked env_reset (reset_envs) writes the lanes it resets THERE and leaves the others, so the
-        # tensor it writes must hold every lane's current observation -- as after an env_step, not k steps old
-        self.obs.copy_(t["obs"][k - 1])
-        self._cur_obs = self.obs
 
     def body_tick(self, wrench, n_ticks: int = 1):
         """pf_body_tick: the free-body tick alone under a held body-frame wrench [n, 6] (force, torque)."""

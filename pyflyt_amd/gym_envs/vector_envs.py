@@ -25,10 +25,9 @@ from typing import Any
 import numpy as np
 import torch
 
-from .. import _checks as K
 from .. import _lib as L
+from .._collect import ClosedLoopEnv
 from ..engine import BatchEngine
-from ..moments import EpisodeStats
 from ..params import build_params
 from ..spaces import Box, Dict, batch_box
 
@@ -92,7 +91,7 @@ class LazyInfos(dict):
         return {k: (v.clone() if torch.is_tensor(v) else (v.materialize() if isinstance(v, LazyInfos) else v)) for k, v in self.items()}
 
 
-class _VecEnvBase(EpisodeStats):
+class _VecEnvBase(ClosedLoopEnv):
     metadata = {"render_modes": [], "autoreset_mode": "next_step"}
     _vehicle = "quadx"
     _task = "hover"
@@ -118,7 +117,6 @@ class _VecEnvBase(EpisodeStats):
                                        high=np.array(list(P.action_high), dtype=np.float32), dtype=np.float32)
         self.action_space = batch_box(self.single_action_space, self.num_envs)
         self._make_obs_space()
-        self._needs_reset = True
         self._coerced = None  # (what the last foreign action array was converted into: kept alive until the next one)
 
     # ------------------------------------------------------------------ construction
@@ -129,7 +127,6 @@ class _VecEnvBase(EpisodeStats):
         self._ret = None
         self._infos_obj = None
         self._final_infos = None
-        self._policy_step = 0  # (rollout(): the step index that keys the policy's exploration noise)
 
     def _make_obs_space(self):
         self.single_observation_space = Box(low=-np.inf, high=np.inf, shape=(self.attitude_dim,), dtype=np.float32)
@@ -144,11 +141,7 @@ class _VecEnvBase(EpisodeStats):
         if seed is not None and int(seed) != self._seed:
             if mask is not None:
                 raise ValueError("cannot re-seed and partially reset in one call")
-            self._seed = int(seed)
-            moments = self.engine.made_moments()  # (traj_stats' running moments outlive the engine; its carries do not)
-            self.engine.close()
-            self._build(self._seed)
-            self._adopt_moments(moments)
+            self._reseed(seed)
         elif seed is not None and mask is None:
             # same seed: restart the event counters so that the rollout repeats exactly
             self.engine.state.zero_()
@@ -217,11 +210,16 @@ class _VecEnvBase(EpisodeStats):
             out = self.engine.rollout_policy(policy, k, step_index0=self._policy_step, store_mean=store_mean)
         else:
             out = self.engine.rollout_policy_steps(policy, k, step_index0=self._policy_step, store_mean=store_mean)
+        self._after_policy_steps(k)
+        return out + (self._infos_obj,)
+
+    def _after_policy_steps(self, k):
+        """What rollout() and collect() do once their k steps are enqueued: the noise's step index moves on, the infos are stale.
+        (step() invalidates the infos itself: it is one foreign call and nothing else, and it leaves the step index alone.)"""
         self._policy_step = (self._policy_step + k) & 0xFFFFFFFF
         self._infos_obj.invalidate()
         if self._final_infos is not None:
             self._final_infos.invalidate()
-        return out + (self._infos_obj,)
 
     def collect(self, policy, value_fn, k_steps: int, gamma: float = 0.99, lam: float = 0.95, stats: bool = False, normalize_reward: bool = False,
                 fused=None):
@@ -244,16 +242,7 @@ class _VecEnvBase(EpisodeStats):
         update, and adds it as reward_scaled; reward stays raw. The episode accounting is carried from one collect(stats=True) to the
         next and sees only their steps: a step(), rollout() or collect() without stats in between advances the env behind its back,
         and the first episode_return / episode_length after it would lack those steps -- reset() the env before switching."""
-        if self._needs_reset:
-            raise RuntimeError("call reset() before collect()")
-        K.boolean(stats, "stats")
-        K.boolean(normalize_reward, "normalize_reward")
-        stats = stats or normalize_reward
-        BatchEngine._check_policy(policy)
-        if not callable(value_fn):
-            raise ValueError(f"value_fn must be callable (a float32 [M, D] tensor -> [M] or [M, 1]), got {type(value_fn).__name__}")
-        K.unit_interval(gamma, "gamma")
-        K.unit_interval(lam, "lam")
+        stats = self._collect_args(policy, value_fn, gamma, lam, stats, normalize_reward)
         eng, k = self.engine, int(k_steps)
         if not eng._fused_policy(fused):  # (refused before the flags are read or anything is launched)
             eng._check_stepwise()
@@ -262,39 +251,8 @@ class _VecEnvBase(EpisodeStats):
             # lanes whose last step ended an episode: the launch's first step only resets them (read before the launch rewrites the flags)
             episode_start = (eng.flags() & (L.F_TERMINATED | L.F_TRUNCATED)) != 0
         t = eng.collect_rollout(policy, k, step_index0=self._policy_step, fused=fused)
-        self._policy_step = (self._policy_step + k) & 0xFFFFFFFF
-        self._infos_obj.invalidate()
-        if self._final_infos is not None:
-            self._final_infos.invalidate()
-
-        def value(rows, what):
-            m = rows.shape[0] * rows.shape[1]
-            v = value_fn(rows.view(m, eng.obs_dim))
-            if not torch.is_tensor(v) or v.dtype != torch.float32 or tuple(v.shape) not in ((m,), (m, 1)):
-                raise ValueError(f"value_fn must map the float32 {(m, eng.obs_dim)} {what} to a float32 tensor of shape {(m,)} or {(m, 1)}, "
-                                 f"got {(v.dtype, tuple(v.shape)) if torch.is_tensor(v) else type(v).__name__}")
-            return v.reshape(rows.shape[0], rows.shape[1]).contiguous()
-
-        with torch.no_grad():
-            values = value(t["obs_all"], "observations")
-            final_values = value(t["final_obs"], "final observations") if t["final_obs"] is not None else None
-        has_std = policy.log_std is not None
-        extra, reward = {}, t["reward"]
-        if stats:
-            ep_ret, ep_len, summary = eng.traj_stats(t["reward"], t["terminated"], t["truncated"], gamma=gamma, episode_start=episode_start,
-                                                     obs=t["obs_all"][:-1])
-            extra = dict(episode_return=ep_ret, episode_length=ep_len, episode_summary=summary)
-            if normalize_reward:
-                reward = extra["reward_scaled"] = t["reward"] / (self.ret_rms.var + 1e-8).sqrt()
-        adv, ret, logp, valid = eng.gae(reward, t["terminated"], t["truncated"], values, gamma=gamma, lam=lam, final_values=final_values,
-                                        episode_start=episode_start, actions=t["actions"] if has_std else None,
-                                        mean=t["mean"] if has_std else None, log_std=policy.log_std if has_std else None)
-        return dict(obs=t["obs_all"][:-1], actions=t["actions"], mean=t["mean"], logp=logp, values=values[:-1], advantages=adv, returns=ret,
-                    valid=valid, reward=t["reward"], terminated=t["terminated"], truncated=t["truncated"],
-                    last_value=values[-1], infos=self._infos_obj, **extra)
-
-    def close(self):
-        self.engine.close()
+        self._after_policy_steps(k)
+        return self._collect_batch(t, policy, value_fn, gamma, lam, stats, normalize_reward, self._infos_obj, episode_start=episode_start)
 
     def sample_actions(self, step_index: int = 0):
         """Device-side uniform sample of the action box (the role of action_space.sample())."""
@@ -451,6 +409,7 @@ class RocketLandingVecEnv(_VecEnvBase):
             self._seed = self._seed if seed is None else int(seed)
             self.engine.close()
             self._build(self._seed)
+            self._policy_step = 0
         return super().reset(seed=seed, options=options)
 
     def sample_actions(self, step_index: int = 0):

@@ -26,8 +26,6 @@ Differences from the reference, by construction of the batched path:
 """
 from __future__ import annotations
 
-from typing import Any
-
 import numpy as np
 import torch
 
@@ -50,25 +48,17 @@ class MAFixedwingDogfightEnv(WorldRollout):
                  flatten_observation: bool = True, flight_dome_size: float = 800.0, max_duration_seconds: float = 60.0,
                  agent_hz: int = 30, render_mode=None, num_envs: int = 1, device="cuda:0", seed: int = 0, motor_noise: bool = True,
                  freeze_wrecks: bool = False):
-        if render_mode is not None:
-            raise ValueError("rendering is out of scope for the batched GPU path")
+        self._no_render(render_mode)
         self.assisted_flight = bool(assisted_flight)
         self.flatten_observation = bool(flatten_observation)
-        if 120 % agent_hz != 0:  # ma_fixedwing_base_env.py:52-57
-            lowest, highest = int(120 / (int(120 / agent_hz) + 1)), int(120 / int(120 / agent_hz))
-            raise AssertionError(f"`agent_hz` must be round denominator of 120, try {lowest} or {highest}.")
+        self._check_agent_hz(agent_hz)
         if not 1 <= team_size <= 4:
             raise ValueError("team_size must be in 1..4 (the aircraft of a world share a wavefront: 2 * team_size <= 8)")
         # (spawn_min_height / spawn_max_height are accepted and unused, as in the reference: :197-201 draws the height
         #  between the RADIUS bounds)
         self.team_size = int(team_size)
-        self.num_possible_agents = 2 * self.team_size
-        self.possible_agents = ["uav_" + str(r) for r in range(self.num_possible_agents)]
-        self.agent_name_mapping = dict(zip(self.possible_agents, range(self.num_possible_agents)))
+        self._init_agents(2 * self.team_size, num_envs, device)
         self.team_flag = np.concatenate((np.zeros(self.team_size, dtype=bool), np.ones(self.team_size, dtype=bool)))
-        self.agents: list[str] = []
-        self.num_envs = int(num_envs)
-        self.device = torch.device(device)
         self._df = dict(team_size=self.team_size, spawn_min_radius=spawn_min_radius, spawn_max_radius=spawn_max_radius,
                         damage_per_hit=damage_per_hit, lethal_distance=lethal_distance, lethal_angle=lethal_angle_radians,
                         aggressiveness=aggressiveness, cooperativeness=cooperativeness, sample_spawn=True, assisted_flight=self.assisted_flight,
@@ -89,21 +79,6 @@ class MAFixedwingDogfightEnv(WorldRollout):
         P = build_params("fixedwing", "dogfight", noise=self._noise, autoreset="off", seed=seed, angle_representation="euler",
                          vehicle_options=dict(drone_model="acrowing"), world_options=dict(world_scale=5.0), dogfight=self._df, **self._kw)
         self.engine = BatchEngine(P, self.num_possible_agents * self.num_envs, device=self.device)
-
-    def observation_space(self, agent: Any = None):
-        return self._observation_space
-
-    def action_space(self, agent: Any = None):
-        return self._action_space
-
-    def close(self):
-        self.engine.close()
-
-    def _split(self, t):
-        """[E*A, ...] -> per-agent views [E, ...] (squeezed when E == 1)."""
-        A, E = self.num_possible_agents, self.num_envs
-        t = t.view(E, A, *t.shape[1:])
-        return [t[:, i].squeeze(0) if E == 1 else t[:, i] for i in range(A)]
 
     def _obs_out(self, o):
         """The observation of one agent in the form `flatten_observation` asks for (pop_obs_by_id, :724-752)."""
@@ -130,16 +105,9 @@ class MAFixedwingDogfightEnv(WorldRollout):
     def reset(self, seed=None, options=None):
         if seed is not None:
             if int(seed) != self._seed:
-                self._seed = int(seed)
                 # current / past actions are created in __init__ and survive resets: groups 7-8, and 15 (entries 4, 5 of the
                 # six-wide action space, assisted_flight=False)
-                keep, keep45 = self.engine.state[7:9].clone(), self.engine.state[15].clone()
-                moments = self.engine.made_moments()
-                self.engine.close()
-                self._build(self._seed)
-                self._adopt_moments(moments)
-                self.engine.state[7:9] = keep
-                self.engine.state[15] = keep45
+                self._reseed(seed, keep=(slice(7, 9), 15))
             # a seeded reset replays the seed's stream from its start (np.random.RandomState(seed) in the reference, :187):
             # the counter RNG's event counters go back to zero; reset(seed=None) continues the stream
             self.engine.state[5, :, 2] = 0.0

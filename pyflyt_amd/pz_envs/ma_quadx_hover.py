@@ -26,8 +26,6 @@ one foreign call and nothing else, and a whole policy -> step loop can be captur
 """
 from __future__ import annotations
 
-from typing import Any
-
 import numpy as np
 import torch
 
@@ -47,21 +45,13 @@ class MAQuadXHoverEnv(WorldRollout):
                  max_duration_seconds: float = 30.0, angle_representation: str = "quaternion", agent_hz: int = 40,
                  render_mode=None, num_envs: int = 1, device="cuda:0", seed: int = 0, motor_noise: bool = True,
                  shared_world: bool = False, cull_agents: bool = True):
-        if render_mode is not None:
-            raise ValueError("rendering is out of scope for the batched GPU path")
+        self._no_render(render_mode)
         start_pos, start_orn = np.asarray(start_pos, dtype=np.float64), np.asarray(start_orn, dtype=np.float64)
         assert len(start_pos.shape) == 2 and start_pos.shape[-1] == 3, f"Expected `start_pos` to be of shape [num_agents, 3], got {start_pos.shape}."
         assert start_pos.shape == start_orn.shape, f"Expected `start_pos` to be of shape [num_agents, 3], got {start_pos.shape}."
-        if 120 % agent_hz != 0:  # ma_quadx_base_env.py:60-65
-            lowest, highest = int(120 / (int(120 / agent_hz) + 1)), int(120 / int(120 / agent_hz))
-            raise AssertionError(f"`agent_hz` must be round denominator of 120, try {lowest} or {highest}.")
+        self._check_agent_hz(agent_hz)
         self.start_pos, self.start_orn = start_pos, start_orn
-        self.num_possible_agents = len(start_pos)
-        self.possible_agents = ["uav_" + str(r) for r in range(self.num_possible_agents)]
-        self.agent_name_mapping = dict(zip(self.possible_agents, range(self.num_possible_agents)))
-        self.agents: list[str] = []
-        self.num_envs = int(num_envs)
-        self.device = torch.device(device)
+        self._init_agents(len(start_pos), num_envs, device)
         self._kw = dict(flight_mode=flight_mode, flight_dome_size=flight_dome_size, max_duration_seconds=max_duration_seconds,
                         angle_representation=angle_representation, agent_hz=agent_hz, sparse_reward=sparse_reward)
         self._noise = "philox" if motor_noise else "off"
@@ -110,36 +100,15 @@ class MAQuadXHoverEnv(WorldRollout):
             self._out.append((o[i], r[i], t[i], u[i], infos))
         self._done_all = self.engine.terminated.view(E, A), self.engine.truncated.view(E, A)
 
-    def observation_space(self, agent: Any = None):
-        return self._observation_space
-
-    def action_space(self, agent: Any = None):
-        return self._action_space
-
-    def close(self):
-        self.engine.close()
-
     def action_buffers(self) -> dict:
         """{agent: view [num_envs, 4] (or [4]) of the env's own action tensor}: write the actions here and pass the views to step()
         -- no copy on the way in."""
         return {ag: self._act_views[i] for i, ag in enumerate(self.possible_agents)}
 
-    def _split(self, t):
-        """[E*A, ...] -> per-agent views [E, ...] (squeezed when E == 1)."""
-        A, E = self.num_possible_agents, self.num_envs
-        t = t.view(E, A, *t.shape[1:])
-        return [t[:, i].squeeze(0) if E == 1 else t[:, i] for i in range(A)]
-
     # ------------------------------------------------------------------ ma_quadx_hover_env.py:99-121
     def reset(self, seed=None, options=None):
         if seed is not None and int(seed) != self._seed:
-            self._seed = int(seed)
-            keep = self.engine.state[12:16].clone()  # spawn poses and the action memories survive
-            moments = self.engine.made_moments()
-            self.engine.close()
-            self._build(self._seed)
-            self._adopt_moments(moments)
-            self.engine.state[12:16] = keep
+            self._reseed(seed, keep=(slice(12, 16),))  # spawn poses and the action memories survive
         if seed is not None:
             self._policy_step = 0
         self._needs_reset = False
