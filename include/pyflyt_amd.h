@@ -854,6 +854,74 @@ typedef struct pf_world_sync_args {
 size_t pf_sizeof_world_sync(void);
 int pf_world_sync(pf_ctx* ctx, const pf_world_sync_args* a, int agents_per_world, void* stream);
 
+/* Why episodes end, and who wins a world: the reference reports `collision`, `out_of_bounds`, `env_complete` and
+ * `num_targets_reached` (the dogfight: `team_win`, `dead`, `received_hits`) on every step(); inside a closed loop the words behind
+ * them are overwritten by the next reset. This call reads them where an episode ends and counts them on the device, per group of
+ * lanes. Any context with an env task. (Added without a new PF_ABI_VERSION: a new function and a new block, every existing struct as
+ * it was.) Two forms: the TRAJECTORY form (agents_per_world == 1, any k_steps, `info` given -- SAME_STEP's final_info rows, or a block
+ * of the caller's) and the STEP form (k_steps == 1, `info` NULL or given), which is also the WORLD form for agents_per_world > 1.
+ *   - ENDED. Lane i ends an episode at step s if and only if terminated[s][i] | truncated[s][i]. Nothing else is asked: under
+ *     NEXT_STEP the reset step writes zero flags; pf_world_sync blanks the rows of latched lanes and of the reset step; an excluded
+ *     opponent lane keeps its real flags (and `valid` takes it out of the agent-level slots).
+ *   - WORDS. (word0, word1) of lane i at step s: info[s][i][0..1] as stored, in final_info's layout; with info == NULL (k_steps == 1)
+ *     the words of `state` as it stands after the env step and before any reset. PF_TASK_HOVER / WAYPOINTS / ROCKET_LANDING /
+ *     MA_HOVER: word0 = the flags word (pf_flag_bits), word1 = the targets left. PF_TASK_DOGFIGHT: word0 = the dogfight's bits word,
+ *     word1 = received_hits. The words of a lane that did not end are loaded and not selected: they reach nothing.
+ *   - BYTE of an ended episode: PF_OC_ENDED; PF_OC_TERMINATED if terminated (terminated wins over truncated, as in pf_traj_stats);
+ *     PF_OC_COLLISION / PF_OC_OOB / PF_OC_COMPLETE / PF_OC_NONFINITE from word0's PF_F_INFO_COLLISION / PF_F_INFO_OOB /
+ *     PF_F_INFO_COMPLETE / PF_F_NONFINITE; on the dogfight PF_OC_COLLISION / PF_OC_OOB / PF_OC_COMPLETE / PF_OC_DEAD from its
+ *     collision / out_of_bounds / team_win / dead bits, and never PF_OC_NONFINITE. outcome_out[s][i] = the byte where the lane
+ *     ended, 0 elsewhere -- for invalid lanes and for lanes whose group is out of range as well.
+ *   - AGENT-LEVEL SLOTS, counted where ended && valid[s][i] (valid NULL = 1), into counts[group[i]] (group NULL = 0):
+ *       0 episodes   1 terminated   2 truncated   3 collision   4 out of bounds   5 complete / team_win   6 dead   7 nonfinite
+ *       8 the sum of num_targets - word1 on PF_TASK_WAYPOINTS, of received_hits (word1) on the dogfight, 0 on the other tasks
+ *       9 ended with none of the bits 4..64: ran to the limit cleanly
+ *     Bits may co-occur; each slot counts on its own.
+ *   - WORLD-LEVEL SLOTS, agents_per_world = A > 1 (worlds of A adjacent lanes, lane = world * A + agent, as in pf_world_sync;
+ *     k_steps == 1):   10 worlds   11 team 0 wins   12 team 1 wins   13 draws   14-15 zero.
+ *     A lane that ends, valid or not, ASSIGNS its byte to world_latch[i]. Where world_reset[i] != 0 on a world's first lane, the
+ *     world that finished before this step is tallied into the row of that first lane's group: slot 10 always; on PF_TASK_DOGFIGHT
+ *     team 0 = lanes [0, df_team_size) of the world, team 1 the rest, team t won if some lane of t latched PF_OC_COMPLETE and no
+ *     lane of the other team did, otherwise the world is a draw; other tasks have no teams and slots 11-13 stay 0. Nothing is ever
+ *     cleared: every lane of a world ends, and so rewrites its byte, before pf_world_sync names the world again. A world reset from
+ *     outside (pf_env_reset with a mask of the caller's) is not tallied.
+ *   - NO LANE READS A LATCH BYTE THAT ANOTHER LANE WRITES IN THE SAME LAUNCH. The lanes that write belong to worlds that are not
+ *     being reset (a lane stores only where world_reset[i] == 0; under pf_world_sync's protocol a lane of a world that is being reset
+ *     has blank flags anyway), the bytes that are read belong to worlds that are (world_reset on the first lane), and the mask is
+ *     the same on every lane of a world. This holds for every A, 6 included, and wherever a world straddles a wavefront or a
+ *     workgroup: the argument never looks at where a world begins. So there is no staging buffer and no copy.
+ *   - GROUPS. group[i] is not range-checked on the host (that would read device memory): the kernel takes a lane whose group is
+ *     outside 0..n_groups-1 out of every count, and does not tally a world whose first lane is such a lane.
+ *   - ARITHMETIC. Integer sums, ADDED to counts in place (a zeroed block = empty): per-workgroup partial sums, then vector atomics
+ *     on the int64 block. The counts do not depend on launch shape, stream or order.
+ *   - ERRORS. PF_ERR_ARG, pf_last_error naming the argument, before any launch: a NULL ctx, argument block, terminated, truncated or
+ *     counts; k_steps < 1; info == NULL with k_steps != 1 or with state == NULL; n_groups outside 1..PF_OUTCOME_MAX_GROUPS;
+ *     agents_per_world outside 1..64 or not dividing n; agents_per_world > 1 with k_steps != 1 or without world_reset or
+ *     world_latch; agents_per_world == 1 with world_reset given. PF_ERR_UNSUPPORTED: a context without an env task.
+ *   - Enqueued on `stream`: one launch, no host synchronisation, no allocation, no copy -- capturable in a HIP graph. One thread per
+ *     lane; in the trajectory form the loads of a window of steps are issued before their first use. The call keeps nothing in the
+ *     context: calls with distinct outputs may run on different streams. */
+#define PF_OUTCOME_SLOTS 16
+#define PF_OUTCOME_MAX_GROUPS 16
+enum pf_outcome_bit { PF_OC_ENDED = 1, PF_OC_TERMINATED = 2, PF_OC_COLLISION = 4, PF_OC_OOB = 8,
+                      PF_OC_COMPLETE = 16 /* env_complete; dogfight: team_win */, PF_OC_DEAD = 32 /* dogfight only */,
+                      PF_OC_NONFINITE = 64 };
+typedef struct pf_outcome_args {
+  const uint8_t* terminated;   /* [k][n] */
+  const uint8_t* truncated;    /* [k][n] */
+  const uint8_t* valid;        /* [k][n] or NULL (= all 1): whose ended episodes enter the agent-level slots */
+  const int32_t* info;         /* [k][n][2] (word0, word1) in final_info's layout, or NULL = read the live state */
+  const float*   state;        /* the context's state tensor; required when info == NULL */
+  const int32_t* group;        /* [n] in 0..n_groups-1, or NULL (= 0) */
+  int32_t        n_groups;     /* 1..PF_OUTCOME_MAX_GROUPS */
+  const uint8_t* world_reset;  /* [n]: pf_world_sync's reset_out of this step; required iff agents_per_world > 1 */
+  uint8_t*       world_latch;  /* [n] in/out, the caller's; required iff agents_per_world > 1 */
+  uint8_t*       outcome_out;  /* [k][n] or NULL */
+  int64_t*       counts;       /* [n_groups][PF_OUTCOME_SLOTS], ADDED to in place (zeroed block = empty) */
+} pf_outcome_args;
+size_t pf_sizeof_outcome(void);
+int pf_episode_outcomes(pf_ctx* ctx, const pf_outcome_args* a, int k_steps, int agents_per_world, void* stream);
+
 /* The reference's LOWER boundary for one drone: applyExternalForce / applyExternalTorque on the base link in
  * LINK_FRAME followed by stepSimulation (core/drones/quadx.py:502-510, core/aviary.py:516), n_ticks times with
  * the wrench b->wrench held: the free-body tick alone (collision detection, gyroscopic term, +-max_coord_vel

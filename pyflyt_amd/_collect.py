@@ -7,6 +7,7 @@ from __future__ import annotations
 import torch
 
 from . import _checks as K
+from . import _lib as L
 from .engine import BatchEngine
 from .moments import EpisodeStats
 
@@ -20,12 +21,13 @@ class ClosedLoopEnv(EpisodeStats):
     def close(self):
         self.engine.close()
 
-    def _collect_args(self, policy, value_fn, gamma, lam, stats, normalize_reward):
+    def _collect_args(self, policy, value_fn, gamma, lam, stats, normalize_reward, outcomes=False):
         """collect()'s refusals, in their order, before anything reads the engine; returns whether pf_traj_stats runs."""
         if self._needs_reset:
             raise RuntimeError("call reset() before collect()")
         K.boolean(stats, "stats")
         K.boolean(normalize_reward, "normalize_reward")
+        K.boolean(outcomes, "outcomes")
         BatchEngine._check_policy(policy)
         if not callable(value_fn):
             raise ValueError(f"value_fn must be callable (a float32 [M, D] tensor -> [M] or [M, 1]), got {type(value_fn).__name__}")
@@ -33,11 +35,12 @@ class ClosedLoopEnv(EpisodeStats):
         K.unit_interval(lam, "lam")
         return stats or normalize_reward
 
-    def _collect_batch(self, t, policy, value_fn, gamma, lam, stats, normalize_reward, infos, episode_start=None, valid=None):
+    def _collect_batch(self, t, policy, value_fn, gamma, lam, stats, normalize_reward, infos, episode_start=None, valid=None, outcomes=False):
         """The PPO batch of the trajectory `t` (BatchEngine.collect_rollout's dict, or collect_rollout_worlds'): the values of all
         k + 1 observation rows and, where `t` has them (SAME_STEP), of the final_obs rows; with `stats` pf_traj_stats before pf_gae.
         `episode_start` [n]: NEXT_STEP only, for both kernels. `valid` [k, n]: the mask of a trajectory that brings its own
-        (pf_world_sync's: pf_traj_stats_masked, and what the batch returns); None = pf_gae's."""
+        (pf_world_sync's: pf_traj_stats_masked, and what the batch returns); None = pf_gae's. `outcomes`: the closed loop ran with
+        them, and the batch gains outcome [k, n] uint8 and outcome_counts [G, 16] int64."""
         eng = self.engine
 
         def value(rows, what):
@@ -53,10 +56,12 @@ class ClosedLoopEnv(EpisodeStats):
             final_values = value(t["final_obs"], "final observations") if t["final_obs"] is not None else None
         has_std = policy.log_std is not None
         extra, reward = {}, t["reward"]
+        if outcomes:
+            extra = dict(outcome=t["outcome"], outcome_counts=t["outcome_counts"])
         if stats:
             ep_ret, ep_len, summary = eng.traj_stats(t["reward"], t["terminated"], t["truncated"], gamma=gamma, episode_start=episode_start,
                                                      obs=t["obs_all"][:-1], valid=valid)
-            extra = dict(episode_return=ep_ret, episode_length=ep_len, episode_summary=summary)
+            extra.update(episode_return=ep_ret, episode_length=ep_len, episode_summary=summary)
             if normalize_reward:
                 reward = extra["reward_scaled"] = t["reward"] / (self.ret_rms.var + 1e-8).sqrt()
         adv, ret, logp, gae_valid = eng.gae(reward, t["terminated"], t["truncated"], values, gamma=gamma, lam=lam, final_values=final_values,
@@ -65,6 +70,21 @@ class ClosedLoopEnv(EpisodeStats):
         return dict(obs=t["obs_all"][:-1], actions=t["actions"], mean=t["mean"], logp=logp, values=values[:-1], advantages=adv, returns=ret,
                     valid=gae_valid if valid is None else valid, reward=t["reward"], terminated=t["terminated"], truncated=t["truncated"],
                     last_value=values[-1], infos=infos, **extra)
+
+    def episode_outcomes_dict(self, counts=None):
+        """A block of outcome counts ([G, 16] int64: a batch's outcome_counts; default: that of the last rollout() / collect() with
+        outcomes=True) as Python numbers by slot name, one dict per group (THE place that synchronises with the device): episodes,
+        terminated, truncated, collision, out_of_bounds, complete (env_complete; the dogfight's team_win), dead, nonfinite,
+        second_word_sum (targets reached on the waypoint envs, received hits on the dogfight, 0 elsewhere), clean (ran to the limit
+        with no cause bit), and per world: worlds, team0_wins, team1_wins, draws."""
+        if counts is None:
+            counts = self.engine._oc_last
+            if counts is None:
+                raise RuntimeError("no rollout() or collect() with outcomes=True has run yet")
+        if not torch.is_tensor(counts) or counts.dtype != torch.int64 or counts.dim() != 2 or counts.shape[1] != L.PF_OUTCOME_SLOTS:
+            raise ValueError(f"counts must be an int64 tensor of shape (G, {L.PF_OUTCOME_SLOTS}), got "
+                             f"{(counts.dtype, tuple(counts.shape)) if torch.is_tensor(counts) else type(counts).__name__}")
+        return [dict(zip(L.OUTCOME_SLOT_NAMES, row)) for row in counts.tolist()]
 
     def _reseed(self, seed, keep=()):
         """reset(seed=other): a new engine for the new seed. traj_stats' running moments outlive the old engine (its carries do not),

@@ -82,6 +82,10 @@ PfAdam, PF_ADAM_MAX_TENSORS = _STRUCTS["pf_adam_args"], _DEFINES["PF_ADAM_MAX_TE
 PfWorldSync = _STRUCTS["pf_world_sync_args"]
 PfTrajStatsMasked = _STRUCTS["pf_traj_stats_masked_args"]
 PfPpoGradArgs = _STRUCTS["pf_ppo_grad_args"]
+PfOutcome, PF_OUTCOME_SLOTS, PF_OUTCOME_MAX_GROUPS = _STRUCTS["pf_outcome_args"], _DEFINES["PF_OUTCOME_SLOTS"], _DEFINES["PF_OUTCOME_MAX_GROUPS"]
+# pf_episode_outcomes' slots by name (include/pyflyt_amd.h): 0-9 per agent, 10-13 per world
+OUTCOME_SLOT_NAMES = ("episodes", "terminated", "truncated", "collision", "out_of_bounds", "complete", "dead", "nonfinite", "second_word_sum", "clean",
+                      "worlds", "team0_wins", "team1_wins", "draws")
 for _k, _v in _ENUMS.items():  # PF_F_TERMINATED -> F_TERMINATED etc. stay spelled out above; expose the rest as PF_*
     globals().setdefault(_k, _v)
 
@@ -163,13 +167,15 @@ def lib():
     L.pf_adam_step.argtypes = [C.c_void_p, C.POINTER(PfAdam), C.c_void_p, C.c_size_t, C.c_void_p]
     L.pf_sizeof_world_sync.restype = C.c_size_t
     L.pf_world_sync.argtypes = [C.c_void_p, C.POINTER(PfWorldSync), C.c_int, C.c_void_p]
+    L.pf_sizeof_outcome.restype = C.c_size_t
+    L.pf_episode_outcomes.argtypes = [C.c_void_p, C.POINTER(PfOutcome), C.c_int, C.c_int, C.c_void_p]
     L.pf_sizeof_params.restype = C.c_size_t
     L.pf_sizeof_buffers.restype = C.c_size_t
     if L.pf_sizeof_params() != C.sizeof(PfParams) or L.pf_sizeof_buffers() != C.sizeof(PfBuffers) or L.pf_sizeof_policy() != C.sizeof(PfPolicy) \
             or L.pf_sizeof_gae() != C.sizeof(PfGae) or L.pf_sizeof_traj_stats() != C.sizeof(PfTrajStats) \
             or L.pf_sizeof_ppo_loss() != C.sizeof(PfPpoLoss) or L.pf_sizeof_mlp() != C.sizeof(PfMlp) or L.pf_sizeof_adam() != C.sizeof(PfAdam) \
             or L.pf_sizeof_world_sync() != C.sizeof(PfWorldSync) or L.pf_sizeof_ppo_grad() != C.sizeof(PfPpoGradArgs) \
-            or L.pf_sizeof_traj_stats_masked() != C.sizeof(PfTrajStatsMasked):
+            or L.pf_sizeof_traj_stats_masked() != C.sizeof(PfTrajStatsMasked) or L.pf_sizeof_outcome() != C.sizeof(PfOutcome):
         raise PyFlytAmdError("struct layout mismatch between pyflyt_amd/_lib.py and include/pyflyt_amd.h")
     if L.pf_abi_version() != PF_ABI_VERSION:
         raise PyFlytAmdError("ABI version mismatch between pyflyt_amd/_lib.py and libpyflyt_amd.so")

@@ -182,6 +182,7 @@ size_t pf_sizeof_mlp(void) { return sizeof(pf_mlp); }
 size_t pf_sizeof_ppo_grad(void) { return sizeof(pf_ppo_grad_args); }
 size_t pf_sizeof_adam(void) { return sizeof(pf_adam_args); }
 size_t pf_sizeof_world_sync(void) { return sizeof(pf_world_sync_args); }
+size_t pf_sizeof_outcome(void) { return sizeof(pf_outcome_args); }
 const char* pf_last_error(const pf_ctx* ctx) { return ctx ? ctx->err : g_err; }
 
 int pf_ctx_create(const pf_params* params, int n_lanes, int device, uint64_t lane_offset, pf_ctx** out) {

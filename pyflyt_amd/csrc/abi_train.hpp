@@ -1,5 +1,5 @@
 // abi_train.hpp -- the C ABI's training side: pf_policy_act, pf_gae, pf_traj_stats / pf_traj_stats_masked, pf_ppo_loss, pf_mlp_forward / pf_mlp_backward, pf_ppo_grad,
-// pf_adam_step and pf_world_sync, each behind the checks and launches it shares with another. Host code.
+// pf_adam_step, pf_world_sync and pf_episode_outcomes, each behind the checks and launches it shares with another. Host code.
 #pragma once
 #include <cmath>
 
@@ -13,6 +13,7 @@
 #include "ppo_grad.hpp"
 #include "adam.hpp"
 #include "world_sync.hpp"
+#include "outcomes.hpp"
 
 // the env's action width: what pf_policy_act writes per row and pf_gae's log-probabilities sum over
 static int env_action_dim(const pf_params& P) { return P.task == PF_TASK_ROCKET_LANDING ? pf::kRlActionDim : (P.task == PF_TASK_DOGFIGHT && P.df_action_dim == 6) ? 6 : 4; }
@@ -468,5 +469,32 @@ int pf_world_sync(pf_ctx* ctx, const pf_world_sync_args* a, int agents_per_world
   PF_HIP(ctx, hipGetLastError());
   PF_HIP(ctx, hipMemcpyAsync(a->done, ctx->sync_latch, (size_t)ctx->n, hipMemcpyDeviceToDevice, s));
   return PF_OK;
+}
+int pf_episode_outcomes(pf_ctx* ctx, const pf_outcome_args* a, int k_steps, int agents_per_world, void* stream) {
+  static const char* who = "pf_episode_outcomes";
+  if (int rc = traj_call_check(ctx, who, a, k_steps)) return rc;
+  const arg_ptr required[] = {{"terminated", a->terminated}, {"truncated", a->truncated}, {"counts", a->counts}, {nullptr, nullptr}};
+  if (int rc = require_args(ctx, who, required)) return rc;
+  if (!a->info && k_steps != 1) return arg_fail(ctx, who, "info is required for k_steps > 1 (the live state holds the words of one step)");
+  if (!a->info && !a->state) return arg_fail(ctx, who, "state (the context's state tensor) is required when info is NULL");
+  if (a->n_groups < 1 || a->n_groups > PF_OUTCOME_MAX_GROUPS) return arg_fail(ctx, who, "n_groups must be in 1..PF_OUTCOME_MAX_GROUPS (16)");
+  const int A = agents_per_world;
+  if (A < 1 || A > pf::kWorldSyncMaxA) return arg_fail(ctx, who, "agents_per_world must be in 1..64");
+  if (ctx->n % A != 0) return arg_fail(ctx, who, "agents_per_world must divide the context's lane count n");
+  if (A > 1 && k_steps != 1) return arg_fail(ctx, who, "k_steps must be 1 with agents_per_world > 1 (the world form runs once per step)");
+  if (A > 1 && !a->world_reset) return arg_fail(ctx, who, "world_reset (pf_world_sync's reset_out of this step) is required with agents_per_world > 1");
+  if (A > 1 && !a->world_latch) return arg_fail(ctx, who, "world_latch is required with agents_per_world > 1");
+  if (A == 1 && a->world_reset) return arg_fail(ctx, who, "world_reset must be NULL with agents_per_world == 1 (there are no worlds to tally)");
+  if (int rc = ensure_device(ctx)) return rc;
+  const pf_params& P = ctx->P;
+  const bool dogfight = P.task == PF_TASK_DOGFIGHT;
+  // the live words: the dogfight's side group 6 (bits word 3, received_hits word 2); elsewhere the int group (flags word 1, targets left word 3)
+  const int g = dogfight ? 6 : (P.vehicle == PF_FIXEDWING ? 5 : 6), w0 = dogfight ? 3 : 1, w1 = dogfight ? 2 : 3;
+  const int32_t* words = a->info ? nullptr : reinterpret_cast<const int32_t*>(a->state) + (size_t)g * (size_t)ctx->n * 4;
+  const pf::OutcomeK K{a->terminated, a->truncated, a->valid, a->info, words ? words + w0 : nullptr, words ? words + w1 : nullptr, a->group,
+                       a->world_reset, a->world_latch, a->outcome_out, reinterpret_cast<unsigned long long*>(a->counts), a->n_groups, dogfight ? 1 : 0,
+                       P.task == PF_TASK_WAYPOINTS ? P.num_targets : 0, dogfight ? P.df_team_size : A};
+  hipLaunchKernelGGL(pf::outcomes_kernel, dim3((ctx->n + pf::kOcBlock - 1) / pf::kOcBlock), dim3(pf::kOcBlock), 0, (hipStream_t)stream, K, ctx->n, k_steps, A);
+  return launched(ctx);
 }
 }  // extern "C"

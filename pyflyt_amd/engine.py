@@ -303,15 +303,19 @@ class BatchEngine(TrainOps):
         self._check_policy(policy)
         return policy.fill(L.PfPolicy(), self)
 
-    def rollout_policy(self, policy, k_steps: int, step_index0: int = 0, store_mean: bool = False):
+    def rollout_policy(self, policy, k_steps: int, step_index0: int = 0, store_mean: bool = False, outcomes: bool = False, group=None, n_groups: int = 1):
         """pf_rollout_policy: `k_steps` env steps in one launch with every action computed on the device by `policy` (an MLPPolicy)
         from the observation the env has just written -- the closed loop of an on-policy collector. The first step acts on the
         engine's current observation (self.obs after a reset or a step, the last row of the previous rollout). Returns
         (obs [k, n, D], reward [k, n], terminated [k, n], truncated [k, n], actions [k, n, 4]) -- the same tensors as rollout(),
         overwritten by the next call -- and, with store_mean, the policy's means [k, n, 4] as a sixth. `step_index0` keys the
         exploration noise: advance it by k between calls. QuadX-Hover / QuadX-Waypoints on the specialised kernel; everything else
-        raises PyFlytAmdError with the library's message -- rollout_policy_steps is the same loop on every env."""
-        return self._rollout_with(self._launch_policy, self._policy_block(policy), int(k_steps), step_index0, store_mean)
+        raises PyFlytAmdError with the library's message -- rollout_policy_steps is the same loop on every env.
+        outcomes=True (SAME_STEP only: ValueError otherwise, see _fused_policy) adds one pf_episode_outcomes call on the final_info
+        rows behind the launch and appends (outcome [k, n] uint8, outcome_counts [n_groups, 16] int64) to what is returned."""
+        K.boolean(outcomes, "outcomes")
+        self._fused_policy(True, outcomes)
+        return self._rollout_with(self._launch_policy, self._policy_block(policy), int(k_steps), step_index0, store_mean, outcomes, group, n_groups)
 
     def policy_act(self, policy, step_index: int = 0, obs=None, out=None, mean_out=None):
         """pf_policy_act: `policy` (an MLPPolicy) on `obs` [n, D] (default: the engine's current observation) in one launch, on any
@@ -329,33 +333,40 @@ class BatchEngine(TrainOps):
         self._launch(self.lib.pf_policy_act, C.byref(q), _ptr(out), int(step_index) & 0xFFFFFFFF)
         return out if mean_out is None else (out, mean_out)
 
-    def rollout_policy_steps(self, policy, k_steps: int, step_index0: int = 0, store_mean: bool = False):
+    def rollout_policy_steps(self, policy, k_steps: int, step_index0: int = 0, store_mean: bool = False, outcomes: bool = False, group=None, n_groups: int = 1):
         """rollout_policy, step by step: k x (pf_policy_act, pf_env_step) into the same trajectory tensors, the same return value.
         Two launches per step instead of one for the whole rollout, on every single-agent env: QuadX, Fixedwing-Waypoints and
         Rocket-Landing, the cascaded flight modes, the generic kernel, the 8-point manifold. Each env step writes straight into its
         trajectory rows (final_obs / final_info rows included under SAME_STEP): nothing is copied. Where rollout_policy runs, the
         results are bit-identical. Needs an auto-reset mode and PF_NOISE_OFF / PF_NOISE_PHILOX (ValueError otherwise) -- so the
         multi-agent tasks (dogfight, multi-agent hover), which exist with auto-reset OFF only, are refused here: their loop is
-        rollout_policy_worlds (whole worlds reset on the device), or policy_act and env_step with the culling by hand."""
+        rollout_policy_worlds (whole worlds reset on the device), or policy_act and env_step with the culling by hand.
+        outcomes=True: every step enqueues pf_episode_outcomes behind pf_env_step (three launches per step), on the step's flag rows
+        and on its final_info row under SAME_STEP, on the live state otherwise; (outcome [k, n] uint8, outcome_counts [n_groups, 16]
+        int64, zeroed when the call begins) are appended to what is returned. group [n] int32 in 0..n_groups-1: the row a lane counts in."""
+        K.boolean(outcomes, "outcomes")
         q, k, _ = self._closed_loop(policy, k_steps, False)
-        return self._rollout_with(self._launch_steps, q, k, step_index0, store_mean)
+        return self._rollout_with(self._launch_steps, q, k, step_index0, store_mean, outcomes, group, n_groups)
 
-    def _rollout_with(self, launch, q, k, step_index0, store_mean):
+    def _rollout_with(self, launch, q, k, step_index0, store_mean, outcomes=False, group=None, n_groups=1):
         """Either closed loop into the trajectory tensors the rollouts share, and what both return. (The means are as wide as the
         action: 4 wherever the fused launch exists.)"""
+        if outcomes:
+            self._outcome_shape(1, True, n_groups, 1, False, False)
         t = self._traj_tensors(k)
         mean = self._traj_mean(t) if store_mean else None
-        launch(q, t, k, step_index0, mean)
+        launch(q, t, k, step_index0, mean, oc=self._outcome_block(t, k, group, n_groups) if outcomes else None)
         out = (t["obs"], t["reward"], t["terminated"], t["truncated"], t["actions"])
-        return out + (mean,) if store_mean else out
+        out = out + (mean,) if store_mean else out
+        return out + (t["outcome"], t["outcome_counts"]) if outcomes else out
 
-    def _closed_loop(self, policy, k_steps, fused):
+    def _closed_loop(self, policy, k_steps, fused, outcomes=False):
         """What rollout_policy_steps and collect_rollout ask before they touch a tensor; returns (the pf_policy block, k, fused)."""
         self._check_policy(policy)
         k = int(k_steps)
         if k < 1:
             raise ValueError(f"k_steps must be >= 1, got {k_steps}")
-        fused = self._fused_policy(fused)
+        fused = self._fused_policy(fused, outcomes)
         if not fused:
             self._check_stepwise()
         return policy.fill(L.PfPolicy(), self), k, fused
@@ -369,22 +380,35 @@ class BatchEngine(TrainOps):
         if self.params.noise_mode == L.NOISE_INJECT:
             raise ValueError("the stepwise policy rollout runs under PF_NOISE_OFF / PF_NOISE_PHILOX (PF_NOISE_INJECT passes per-step noise tensors; use policy_act and env_step)")
 
-    def _fused_policy(self, fused):
+    def _fused_policy(self, fused, outcomes=False):
         """Which closed loop a `fused` argument selects: None = the fused launch where the library has one for the vehicle and task
-        (QuadX-Hover / QuadX-Waypoints, with all its refusals), the stepwise path everywhere else."""
+        (QuadX-Hover / QuadX-Waypoints, with all its refusals), the stepwise path everywhere else. With `outcomes` the fused launch
+        serves under SAME_STEP only, where the final_info rows keep every ended episode's words: elsewhere it holds the flags in
+        registers and its next reset overwrites the words behind them inside the launch, so None selects the stepwise loop (the
+        same bits, two launches per step more) and True is refused."""
+        if fused is not None and not isinstance(fused, bool):
+            raise ValueError(f"fused must be None, True or False, got {fused!r}")
+        if outcomes and self.params.autoreset != L.AUTORESET_SAME_STEP:
+            if fused:
+                raise ValueError("fused=True with outcomes=True needs SAME_STEP auto-reset: under NEXT_STEP the fused launch keeps the flags in registers "
+                                 "and its resets overwrite the words behind them before anything could read them; fused=None or False runs the "
+                                 "stepwise loop, whose results are bit-identical")
+            return False
         if fused is None:
             return self.params.vehicle == L.QUADX and self.params.task in (L.TASK_HOVER, L.TASK_WAYPOINTS)
-        if not isinstance(fused, bool):
-            raise ValueError(f"fused must be None, True or False, got {fused!r}")
         return fused
 
-    def _launch_steps(self, q, t, k, step_index0, mean, A=None, qo=None, opp_lanes=None):
+    def _launch_steps(self, q, t, k, step_index0, mean, A=None, qo=None, opp_lanes=None, oc=None):
         """THE stepwise closed loop: k x (pf_policy_act, pf_env_step) into the trajectory tensors `t`, acting first on the engine's
         current observation -- the act of step s reads the row the env wrote at step s - 1, the env's buffer block (a private copy:
         nothing else sees the row cursor) points at the rows of step s, final_obs / final_info rows included where `t` has them.
         With `A` the lanes are worlds of A (auto-reset OFF): every step adds pf_world_sync on its row and pf_env_reset of the worlds
         that were waiting, whose block points at the observation row of the step; with `qo` and `opp_lanes` the opponent's
-        pf_policy_act (the same step index) and one merge come between the act and the step. One device selection and one stream
+        pf_policy_act (the same step index) and one merge come between the act and the step -- `qo` a list of (pf_policy block, the
+        [n, 1] bool lanes it flies): one act over all rows and one merge EACH. With `oc` (a pf_outcome_args block: _outcome_block)
+        every step ends with pf_episode_outcomes on its flag rows into t["outcome"][s] -- behind pf_env_step, and for worlds behind
+        pf_world_sync (it reads valid[s] and the reset mask) and in front of the masked pf_env_reset (it reads the live state); the
+        words are the step's final_info row where `t` has one. One device selection and one stream
         handle for all the calls; no allocation inside the loop, nothing synchronises."""
         b = self._block(self._buffers())
         lib, ctx, check, qref, bref = self.lib, self._ctx, L.check, C.byref(q), C.byref(b)
@@ -403,7 +427,13 @@ class BatchEngine(TrainOps):
         opp = None
         if qo is not None:
             opp = self._lazy("_opp_act", lambda: torch.empty(n, W, dtype=torch.float32, device=self.device), keep=lambda o: o.shape[1] == W)
-            qo.mean_out, p_opp, oref, pick = None, C.c_void_p(opp.data_ptr()), C.byref(qo), opp_lanes.bool().view(n, 1)
+            p_opp = C.c_void_p(opp.data_ptr())
+            for block, _ in qo:
+                block.mean_out = None
+        if oc is not None:
+            outcome, ocref, p_out = lib.pf_episode_outcomes, C.byref(oc), t["outcome"].data_ptr()
+            if A is not None:
+                oc.world_reset, oc.world_latch = t["reset"].data_ptr(), self.world_outcome.data_ptr()
         cur = self._cur_obs.data_ptr()
         with torch.cuda.device(self.device):
             stream = self._stream()
@@ -416,10 +446,11 @@ class BatchEngine(TrainOps):
                 if rc:
                     check(rc, ctx)
                 if opp is not None:
-                    qo.obs0 = cur
-                    check(act(ctx, oref, p_opp, step_index, stream), ctx)
                     row = t["actions"][s]
-                    torch.where(pick, opp, row, out=row)  # (the merge: one launch on the same stream)
+                    for block, pick in qo:
+                        block.obs0 = cur
+                        check(act(ctx, C.byref(block), p_opp, step_index, stream), ctx)
+                        torch.where(pick, opp, row, out=row)  # (the merge: one launch on the same stream)
                 cur = p_obs + 4 * n * D * s
                 b.actions, b.obs, b.reward = a, cur, p_rew + 4 * n * s
                 b.terminated, b.truncated = p_term + n * s, p_trunc + n * s
@@ -431,6 +462,14 @@ class BatchEngine(TrainOps):
                 if A is not None:
                     w.terminated, w.truncated, w.reward, w.valid_out = b.terminated, b.truncated, b.reward, p_valid + n * s
                     check(sync(ctx, wref, A, stream), ctx)
+                if oc is not None:
+                    oc.terminated, oc.truncated, oc.outcome_out = b.terminated, b.truncated, p_out + n * s
+                    oc.valid = p_valid + n * s if A is not None else None
+                    oc.info = p_finfo + 8 * n * s if p_finfo is not None else None
+                    rc = outcome(ctx, ocref, 1, A or 1, stream)
+                    if rc:
+                        check(rc, ctx)
+                if A is not None:
                     br.obs = cur
                     check(reset(ctx, brref, p_mask, stream), ctx)
         if A is None:
@@ -441,13 +480,17 @@ class BatchEngine(TrainOps):
             self.obs.copy_(t["obs"][k - 1])
             self._cur_obs = self.obs
 
-    def _launch_policy(self, q, t, k, step_index0, mean):
-        """pf_rollout_policy into the trajectory tensors `t`, acting first on the engine's current observation."""
+    def _launch_policy(self, q, t, k, step_index0, mean, oc=None):
+        """pf_rollout_policy into the trajectory tensors `t`, acting first on the engine's current observation. With `oc` (SAME_STEP:
+        _fused_policy) one pf_episode_outcomes call in the trajectory form behind it, on the final_info rows."""
         q.obs0 = self._cur_obs.data_ptr()
         q.mean_out = mean.data_ptr() if mean is not None else None
         b = self._point_at(self._buffers(actions_out=t["actions"]), t)
         self._launch(self.lib.pf_rollout_policy, C.byref(b), C.byref(q), k, int(step_index0) & 0xFFFFFFFF)
         self._cur_obs = t["obs"][k - 1]
+        if oc is not None:
+            oc.terminated, oc.truncated, oc.info, oc.outcome_out = _ptr(t["terminated"]), _ptr(t["truncated"]), _ptr(t["final_info"]), _ptr(t["outcome"])
+            self._launch(self.lib.pf_episode_outcomes, C.byref(oc), k, 1)
 
     def _collect_into(self, t, launch):
         """What the collect_* calls share: row 0 of `t`'s obs_all becomes a copy of the engine's current observation (the previous
@@ -463,18 +506,25 @@ class BatchEngine(TrainOps):
             raise
         return t
 
-    def collect_rollout(self, policy, k_steps: int, step_index0: int = 0, fused=None):
+    def collect_rollout(self, policy, k_steps: int, step_index0: int = 0, fused=None, outcomes: bool = False, group=None, n_groups: int = 1):
         """rollout_policy for a learner: the same launch (`fused`: None = where the library has it, QuadX-Hover / QuadX-Waypoints, and
         rollout_policy_steps' k x (pf_policy_act, pf_env_step) on every other env; True = the fused launch or its refusal; False =
         the stepwise path -- the act of step s reads row s, the env writes row s + 1) into trajectory tensors of its own whose observations live in ONE buffer
         `obs_all` [k + 1, n, D]. Row 0 is the observation the first step acts on (an n x D copy of the engine's current observation),
         the launch writes rows 1 .. k: obs_all[:-1] are the policy's inputs and obs_all[1:] the next observations, both views -- the
         trajectory is never copied. Returns the dict of tensors (obs_all, obs = obs_all[1:], reward, terminated, truncated, actions,
-        mean, final_obs / final_info under SAME_STEP), overwritten by the next call with the same k_steps."""
-        q, k, fused = self._closed_loop(policy, k_steps, fused)
+        mean, final_obs / final_info under SAME_STEP), overwritten by the next call with the same k_steps. outcomes=True adds
+        outcome [k, n] uint8 and outcome_counts [n_groups, 16] int64 (this call's episodes) as rollout_policy_steps does -- or, where
+        the fused launch serves (SAME_STEP), one pf_episode_outcomes call on the final_info rows behind it; with fused=None outside
+        SAME_STEP the stepwise loop runs (_fused_policy)."""
+        K.boolean(outcomes, "outcomes")
+        q, k, fused = self._closed_loop(policy, k_steps, fused, outcomes)
+        if outcomes:
+            self._outcome_shape(1, True, n_groups, 1, False, False)
         t = self._lazy("_ctraj", lambda: self._new_traj(k, k + 1, mean=True), keep=lambda t: t["k"] == k)
+        oc = self._outcome_block(t, k, group, n_groups) if outcomes else None
         launch = self._launch_policy if fused else self._launch_steps
-        return self._collect_into(t, lambda t: launch(q, t, k, step_index0, t["mean"]))
+        return self._collect_into(t, lambda t: launch(q, t, k, step_index0, t["mean"], oc=oc))
 
     # ------------------------------------------------------------------ multi-agent worlds
     @property
@@ -515,9 +565,10 @@ class BatchEngine(TrainOps):
         self._launch(self.lib.pf_world_sync, C.byref(a), A)
         return valid_out, reset_out
 
-    def _closed_loop_worlds(self, policy, k_steps, agents_per_world, opponent, opponent_lanes):
+    def _closed_loop_worlds(self, policy, k_steps, agents_per_world, opponent, opponent_lanes, outcomes=False, group=None, n_groups=1):
         """What rollout_policy_worlds and collect_rollout_worlds refuse before they touch a tensor; returns (the policy's pf_policy
-        block, the opponent's or None, k, A)."""
+        block, the opponents' [(pf_policy block, the [n, 1] bool lanes it flies)] or None, k, A). `opponent`: one MLPPolicy, which flies
+        opponent_lanes, or a list of 1..16 (a pool): entry p flies the opponent_lanes whose group is p (a list of one: all of them)."""
         if self.params.task == L.TASK_NONE:
             raise ValueError("the world rollout needs an engine with an env task")
         if self.params.autoreset != L.AUTORESET_OFF:
@@ -531,15 +582,26 @@ class BatchEngine(TrainOps):
         A = self._check_world(agents_per_world)
         if (opponent is None) != (opponent_lanes is None):
             raise ValueError("opponent and opponent_lanes come together or not at all")
+        K.boolean(outcomes, "outcomes")
+        pool = list(opponent) if isinstance(opponent, (list, tuple)) else None
+        if pool is not None and not 1 <= len(pool) <= L.PF_OUTCOME_MAX_GROUPS:
+            raise ValueError(f"opponent: a pool holds 1..{L.PF_OUTCOME_MAX_GROUPS} policies, got {len(pool)}")
+        if pool is not None and len(pool) > 1 and (group is None or n_groups != len(pool)):
+            raise ValueError(f"opponent: a pool of {len(pool)} needs group (which opponent flies a lane) and n_groups = {len(pool)}, got n_groups = {n_groups!r}")
+        if outcomes or group is not None:
+            self._outcome_shape(1, True, n_groups, A, True, True)
         q = self._policy_block(policy)
         qo = None
         if opponent is not None:
-            qo = self._policy_block(opponent)
+            blocks = [self._policy_block(p) for p in (pool if pool is not None else [opponent])]
             K.tensor(self.device, opponent_lanes, "opponent_lanes", (self.n,), K.FLAGS, required="{name} must be a bool / uint8 tensor of shape {shape}")
+            K.tensor(self.device, group, "group", (self.n,), torch.int32)
+            lanes = opponent_lanes.bool()
+            qo = [(b, (lanes if len(blocks) == 1 else lanes & (group == p)).view(self.n, 1)) for p, b in enumerate(blocks)]
         return q, qo, k, A
 
     def rollout_policy_worlds(self, policy, k_steps: int, agents_per_world: int, step_index0: int = 0, opponent=None, opponent_lanes=None,
-                              store_mean: bool = False):
+                              store_mean: bool = False, outcomes: bool = False, group=None, n_groups: int = 1):
         """The closed loop of the multi-agent envs (dogfight, multi-agent hover: auto-reset OFF), with worlds of `agents_per_world`
         adjacent lanes reset on the device once every agent of them has finished. Step s enqueues pf_policy_act(policy,
         step_index0 + s) on the current observation into actions[s] (and mean[s]); pf_env_step into row s; pf_world_sync on row s,
@@ -550,22 +612,31 @@ class BatchEngine(TrainOps):
         and one merge put the opponent's actions on those lanes, which are never valid: six launches and the copy. The last observation row is copied into self.obs, which is the engine's
         current observation afterwards: env_step and a masked env_reset go on from it as after a step. Returns (obs [k, n, D],
         reward, terminated, truncated [k, n], actions [k, n, action width], valid [k, n] bool) and, with store_mean, the policy's
-        means as a seventh: tensors the engine owns, overwritten by the next call with the same k. The latch is world_done."""
-        q, qo, k, A = self._closed_loop_worlds(policy, k_steps, agents_per_world, opponent, opponent_lanes)
+        means as a seventh: tensors the engine owns, overwritten by the next call with the same k. The latch is world_done.
+        `opponent` may be a list of 1..16 policies (a pool): entry p flies the opponent_lanes whose `group` ([n] int32) is p, at the
+        price of one pf_policy_act over ALL rows and one merge per entry -- P full launches, not P partial ones. outcomes=True: every
+        step enqueues pf_episode_outcomes between pf_world_sync and the reset (one launch more per step) and (outcome [k, n] uint8,
+        outcome_counts [n_groups, 16] int64, zeroed when the call begins, row = group) are appended to what is returned; the world
+        latch is world_outcome."""
+        q, qo, k, A = self._closed_loop_worlds(policy, k_steps, agents_per_world, opponent, opponent_lanes, outcomes, group, n_groups)
         t = self._lazy("_wtraj", lambda: self._new_world_traj(k, k), keep=lambda t: t["k"] == k)
         mean = self._traj_mean(t) if store_mean else None
-        self._launch_steps(q, t, k, step_index0, mean, A, qo, opponent_lanes)
+        self._launch_steps(q, t, k, step_index0, mean, A, qo, opponent_lanes, self._outcome_block(t, k, group, n_groups) if outcomes else None)
         out = (t["obs"], t["reward"], t["terminated"], t["truncated"], t["actions"], t["valid"])
-        return out + (mean,) if store_mean else out
+        out = out + (mean,) if store_mean else out
+        return out + (t["outcome"], t["outcome_counts"]) if outcomes else out
 
-    def collect_rollout_worlds(self, policy, k_steps: int, agents_per_world: int, step_index0: int = 0, opponent=None, opponent_lanes=None):
+    def collect_rollout_worlds(self, policy, k_steps: int, agents_per_world: int, step_index0: int = 0, opponent=None, opponent_lanes=None,
+                               outcomes: bool = False, group=None, n_groups: int = 1):
         """rollout_policy_worlds for a learner, as collect_rollout is rollout_policy_steps': the same loop into trajectory tensors of
         its own whose observations live in ONE buffer obs_all [k + 1, n, D] -- row 0 a copy of the engine's current observation,
         rows 1 .. k written by the env steps (and, on reset steps, by the resets). Returns collect_rollout's dict (obs_all, obs =
-        obs_all[1:], reward, terminated, truncated, actions, mean) plus valid [k, n] bool."""
-        q, qo, k, A = self._closed_loop_worlds(policy, k_steps, agents_per_world, opponent, opponent_lanes)
+        obs_all[1:], reward, terminated, truncated, actions, mean) plus valid [k, n] bool, and with outcomes=True outcome and
+        outcome_counts (opponent pools, group and n_groups as in rollout_policy_worlds)."""
+        q, qo, k, A = self._closed_loop_worlds(policy, k_steps, agents_per_world, opponent, opponent_lanes, outcomes, group, n_groups)
         t = self._lazy("_wctraj", lambda: self._new_world_traj(k, k + 1), keep=lambda t: t["k"] == k)
-        return self._collect_into(t, lambda t: self._launch_steps(q, t, k, step_index0, self._traj_mean(t), A, qo, opponent_lanes))
+        oc = self._outcome_block(t, k, group, n_groups) if outcomes else None
+        return self._collect_into(t, lambda t: self._launch_steps(q, t, k, step_index0, self._traj_mean(t), A, qo, opponent_lanes, oc))
 
     def _new_world_traj(self, k, obs_rows):
         t = self._new_traj(k, obs_rows, mean=False)

@@ -192,7 +192,7 @@ class _VecEnvBase(ClosedLoopEnv):
             return self._obs(self.engine.obs), r[1], r[2], r[3], r[4]
         return self._ret
 
-    def rollout(self, policy, k_steps: int, store_mean: bool = False, fused=None):
+    def rollout(self, policy, k_steps: int, store_mean: bool = False, fused=None, outcomes: bool = False):
         """`k_steps` closed-loop env steps, every action computed on the device by `policy` (a pyflyt_amd.MLPPolicy) from the
         observation the env has just returned. Returns the trajectories (obs [k, n, D] -- the engine's flat observation rows, what
         the policy reads --, reward, terminated, truncated, actions [k, n, action width]) and the infos of the LAST step (with
@@ -202,14 +202,19 @@ class _VecEnvBase(ClosedLoopEnv):
         refusals, and the stepwise path on every other vehicle or task; True = the fused launch, or the library's refusal;
         False = the stepwise path, k x (pf_policy_act, pf_env_step) (BatchEngine.rollout_policy_steps), on any env -- how a
         cascaded flight mode, the generic kernel or the 8-point manifold get a closed loop. The stepwise path needs an auto-reset
-        mode (ValueError). Where both exist they give the same bits."""
+        mode (ValueError). Where both exist they give the same bits.
+        outcomes=True: why the episodes that finish inside the call end -- outcome [k, n] uint8 (pf_outcome_bit: 0 where no episode
+        ended) and outcome_counts [1, 16] int64 on the device (episode_outcomes_dict() reads it back) come in front of the infos. One
+        pf_episode_outcomes launch per step on the stepwise path; behind the fused launch, one on the final_info rows under
+        SAME_STEP. Under NEXT_STEP the fused launch has nothing left to read (collect() says why): fused=None then takes the stepwise
+        path, and fused=True is a ValueError."""
         if self._needs_reset:
             raise RuntimeError("call reset() before rollout()")
         k = int(k_steps)
-        if self.engine._fused_policy(fused):
-            out = self.engine.rollout_policy(policy, k, step_index0=self._policy_step, store_mean=store_mean)
+        if self.engine._fused_policy(fused, outcomes):
+            out = self.engine.rollout_policy(policy, k, step_index0=self._policy_step, store_mean=store_mean, outcomes=outcomes)
         else:
-            out = self.engine.rollout_policy_steps(policy, k, step_index0=self._policy_step, store_mean=store_mean)
+            out = self.engine.rollout_policy_steps(policy, k, step_index0=self._policy_step, store_mean=store_mean, outcomes=outcomes)
         self._after_policy_steps(k)
         return out + (self._infos_obj,)
 
@@ -222,7 +227,7 @@ class _VecEnvBase(ClosedLoopEnv):
             self._final_infos.invalidate()
 
     def collect(self, policy, value_fn, k_steps: int, gamma: float = 0.99, lam: float = 0.95, stats: bool = False, normalize_reward: bool = False,
-                fused=None):
+                fused=None, outcomes: bool = False):
         """One PPO batch from `k_steps` closed-loop env steps: the closed loop of rollout() (`fused` as there: one launch on
         QuadX-Hover / QuadX-Waypoints, the stepwise path on every other env), the caller's value network, and
         pf_gae (BatchEngine.gae) -- obs -> policy -> env -> batch ready for the loss, without a host synchronisation.
@@ -241,18 +246,25 @@ class _VecEnvBase(ClosedLoopEnv):
         normalize_reward=True implies stats, hands pf_gae reward / sqrt(ret_rms.var + 1e-8) with the moments AFTER this batch's
         update, and adds it as reward_scaled; reward stays raw. The episode accounting is carried from one collect(stats=True) to the
         next and sees only their steps: a step(), rollout() or collect() without stats in between advances the env behind its back,
-        and the first episode_return / episode_length after it would lack those steps -- reset() the env before switching."""
-        stats = self._collect_args(policy, value_fn, gamma, lam, stats, normalize_reward)
+        and the first episode_return / episode_length after it would lack those steps -- reset() the env before switching.
+        outcomes=True adds outcome [k, n] uint8 (pf_outcome_bit of every episode that ended: ended, terminated, collision, out of
+        bounds, env_complete, nonfinite) and outcome_counts [1, 16] int64 on the device, the counts of THIS call's episodes by slot
+        (episode_outcomes_dict() reads them back by name; slot 8 is the sum of num_targets_reached on the waypoint envs). On the
+        stepwise path each step enqueues one pf_episode_outcomes launch behind pf_env_step. The fused launch keeps the flags in
+        registers and resets lanes inside the launch: under SAME_STEP its final_info rows hold every ended episode's words and one
+        call behind the launch reads them; under NEXT_STEP nothing holds them, so fused=None runs the stepwise loop (the same bits,
+        at the stepwise loop's price) and fused=True with outcomes=True is a ValueError."""
+        stats = self._collect_args(policy, value_fn, gamma, lam, stats, normalize_reward, outcomes)
         eng, k = self.engine, int(k_steps)
-        if not eng._fused_policy(fused):  # (refused before the flags are read or anything is launched)
+        if not eng._fused_policy(fused, outcomes):  # (refused before the flags are read or anything is launched)
             eng._check_stepwise()
         episode_start = None
         if eng.params.autoreset == L.AUTORESET_NEXT_STEP:
             # lanes whose last step ended an episode: the launch's first step only resets them (read before the launch rewrites the flags)
             episode_start = (eng.flags() & (L.F_TERMINATED | L.F_TRUNCATED)) != 0
-        t = eng.collect_rollout(policy, k, step_index0=self._policy_step, fused=fused)
+        t = eng.collect_rollout(policy, k, step_index0=self._policy_step, fused=fused, outcomes=outcomes)
         self._after_policy_steps(k)
-        return self._collect_batch(t, policy, value_fn, gamma, lam, stats, normalize_reward, self._infos_obj, episode_start=episode_start)
+        return self._collect_batch(t, policy, value_fn, gamma, lam, stats, normalize_reward, self._infos_obj, episode_start=episode_start, outcomes=outcomes)
 
     def sample_actions(self, step_index: int = 0):
         """Device-side uniform sample of the action box (the role of action_space.sample())."""

@@ -8,6 +8,10 @@ The batch is flat: a tensor is [k, n, ...] with n = num_envs * agents and lane =
 ...) reads it per copy and agent. `valid` is pf_world_sync's: False on the steps an agent sat out after its episode had ended, on
 the step that reset its copy, and on an opponent's lanes. pf_gae's own `valid` is all ones under auto-reset OFF and is not returned.
 
+rollout(outcomes=True) / collect(outcomes=True) add pf_episode_outcomes to every step, between pf_world_sync and the reset: outcome
+[k, n] uint8 says why each episode ended, outcome_counts [G, 16] int64 counts this call's episodes and finished copies per group
+(episode_outcomes_dict() reads a block back by name; _collect.ClosedLoopEnv).
+
 collect(stats=True) hands that `valid` to pf_traj_stats_masked (BatchEngine.traj_stats(valid=...)): the episode accounting and the running
 moments behind obs_rms / ret_rms (moments.EpisodeStats, the vector envs' copy) see the valid steps and nothing else.
 """
@@ -59,31 +63,33 @@ class WorldRollout(ClosedLoopEnv):
 
     # ------------------------------------------------------------------ closed-loop rollouts
     def _world_args(self, opponent):
-        """(opponent, opponent_lanes) for the engine: none here; the dogfight has team 1."""
+        """(opponent, opponent_lanes, group, n_groups) for the engine: no opponent and one group here; the dogfight has team 1, and
+        a pool of opponents cuts its copies into one group each."""
         if opponent is not None:
             raise ValueError("this env has no opponent (one team)")
-        return None, None
+        return None, None, None, 1
 
     def _after_worlds(self, k):
         self._policy_step = (self._policy_step + k) & 0xFFFFFFFF
         self.step_count += k
         self.agents = self.possible_agents[:]  # (as after reset_envs: finished copies restart on the device, no agent is culled for good)
 
-    def _world_rollout(self, policy, k_steps, opponent, store_mean):
+    def _world_rollout(self, policy, k_steps, opponent, store_mean, outcomes=False):
         if self._needs_reset:
             raise RuntimeError("call reset() before rollout()")
         k = int(k_steps)
-        opponent, lanes = self._world_args(opponent)
+        opponent, lanes, group, n_groups = self._world_args(opponent)
         out = self.engine.rollout_policy_worlds(policy, k, self.num_possible_agents, step_index0=self._policy_step, opponent=opponent,
-                                                opponent_lanes=lanes, store_mean=bool(store_mean))
+                                                opponent_lanes=lanes, store_mean=bool(store_mean), outcomes=outcomes, group=group, n_groups=n_groups)
         self._after_worlds(k)
         return out
 
-    def _world_collect(self, policy, value_fn, k_steps, gamma, lam, opponent, stats=False, normalize_reward=False):
-        stats = self._collect_args(policy, value_fn, gamma, lam, stats, normalize_reward)
+    def _world_collect(self, policy, value_fn, k_steps, gamma, lam, opponent, stats=False, normalize_reward=False, outcomes=False):
+        stats = self._collect_args(policy, value_fn, gamma, lam, stats, normalize_reward, outcomes)
         k = int(k_steps)
-        opponent, lanes = self._world_args(opponent)
+        opponent, lanes, group, n_groups = self._world_args(opponent)
         t = self.engine.collect_rollout_worlds(policy, k, self.num_possible_agents, step_index0=self._policy_step, opponent=opponent,
-                                               opponent_lanes=lanes)
+                                               opponent_lanes=lanes, outcomes=outcomes, group=group, n_groups=n_groups)
         self._after_worlds(k)
-        return self._collect_batch(t, policy, value_fn, gamma, lam, stats, normalize_reward, LazyInfos(self._flat_infos()), valid=t["valid"])
+        return self._collect_batch(t, policy, value_fn, gamma, lam, stats, normalize_reward, LazyInfos(self._flat_infos()), valid=t["valid"],
+                                   outcomes=outcomes)

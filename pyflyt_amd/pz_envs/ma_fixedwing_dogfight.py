@@ -30,6 +30,7 @@ import numpy as np
 import torch
 
 from .. import _lib as L
+from ..dist import strong_shard
 from ..engine import BatchEngine
 from ..params import build_params
 from ..spaces import Box
@@ -143,12 +144,26 @@ class MAFixedwingDogfightEnv(WorldRollout):
     # ------------------------------------------------------------------ closed-loop rollouts (pz_envs/_world_rollout.py)
     _team1 = None  # [n] bool: the lanes of team 1 (agent index >= team_size), made when an opponent first flies them
 
+    _pool_groups = None  # {P: [n] int32}: the segment index of every lane for a pool of P opponents
+
     def _world_args(self, opponent):
         if opponent is None:
-            return None, None
+            return None, None, None, 1
         if self._team1 is None:
             self._team1 = torch.as_tensor(self.team_flag, device=self.device).repeat(self.num_envs).contiguous()
-        return opponent, self._team1
+        if not isinstance(opponent, (list, tuple)):
+            return opponent, self._team1, None, 1
+        P, A = len(opponent), self.num_possible_agents
+        if not 1 <= P <= L.PF_OUTCOME_MAX_GROUPS or P > self.num_envs:
+            raise ValueError(f"opponent: a pool holds 1..{L.PF_OUTCOME_MAX_GROUPS} policies and at most one per copy ({self.num_envs}), got {P}")
+        if P == 1:
+            return list(opponent), self._team1, None, 1
+        groups = self._pool_groups = self._pool_groups or {}
+        if P not in groups:
+            # contiguous, near-equal segments of whole copies: dist.strong_shard's rule with unit = agents
+            shards = [strong_shard(self.num_envs * A, p, P, unit=A) for p in range(P)]
+            groups[P] = torch.repeat_interleave(torch.arange(P, dtype=torch.int32), torch.tensor([sh.lanes for sh in shards])).to(self.device)
+        return list(opponent), self._team1, groups[P], P
 
     def _flat_infos(self):
         side = self.engine.state[6]
@@ -157,7 +172,7 @@ class MAFixedwingDogfightEnv(WorldRollout):
                 "collision": lambda: (bits() & _DF_COLLISION) != 0, "out_of_bounds": lambda: (bits() & _DF_OOB) != 0,
                 "team_win": lambda: (bits() & _DF_TEAM_WIN) != 0}
 
-    def rollout(self, policy, k_steps: int, opponent=None, store_mean: bool = False):
+    def rollout(self, policy, k_steps: int, opponent=None, store_mean: bool = False, outcomes: bool = False):
         """`k_steps` closed-loop env steps of every copy, every action computed on the device by `policy` (a pyflyt_amd.MLPPolicy over
         the flattened observation) -- the loop of policy_act, step(), culling and reset_envs() without the host: a copy whose
         aircraft have ALL finished is reset on the device in the next step, which is no transition for any of them
@@ -170,11 +185,22 @@ class MAFixedwingDogfightEnv(WorldRollout):
         `opponent`: a second MLPPolicy, frozen as far as this env is concerned, that flies team 1 (agent index >= team_size) from
         the same observations with the same noise keys; team 1's lanes are then never valid.
         The exploration noise's step index advances by k_steps per call and restarts with reset(seed=...). Afterwards `done` is
-        the latch as the last step left it, `agents` the full list (as after reset_envs), and step() / reset_envs() go on from there."""
-        return self._world_rollout(policy, k_steps, opponent, store_mean)
+        the latch as the last step left it, `agents` the full list (as after reset_envs), and step() / reset_envs() go on from there.
+        `opponent` may also be a list of 1 to 16 MLPPolicy, a pool (a league's past snapshots): the copies are cut into contiguous,
+        near-equal segments of whole copies (dist.strong_shard's rule), segment p's team 1 is flown by entry p, and p is the lanes'
+        group in outcome_counts. Every entry costs one pf_policy_act over ALL rows and one merge onto its segment: P full launches
+        and P merges per step, not P partial ones. opponent=[p] is opponent=p, bit for bit.
+        outcomes=True appends outcome [k, n] uint8 (pf_outcome_bit of every episode that ended: collision, out of bounds, team_win
+        as PF_OC_COMPLETE, dead; team 1's lanes included) and outcome_counts [G, 16] int64 on the device, G = 1 or the pool's size:
+        per group this call's episodes of the VALID lanes by cause (slots 0-9; slot 8 sums received_hits) and the copies that
+        finished by result (10 worlds, 11 team 0 wins, 12 team 1 wins, 13 draws: a team won if one of its aircraft ended with
+        team_win and none of the other team's did -- an opponent's lanes decide this although they are never valid). A copy is
+        tallied in the step that resets it, so one that finishes in the call's last steps is counted by the next call; copies reset
+        by reset() / reset_envs() are not tallied. One launch more per step. episode_outcomes_dict() reads a block back by name."""
+        return self._world_rollout(policy, k_steps, opponent, store_mean, outcomes)
 
     def collect(self, policy, value_fn, k_steps: int, gamma: float = 0.99, lam: float = 0.95, opponent=None, stats: bool = False,
-                normalize_reward: bool = False):
+                normalize_reward: bool = False, outcomes: bool = False):
         """One PPO batch from rollout()'s loop, as the vector envs' collect(): `value_fn` (a float32 [M, D] tensor -> [M] or [M, 1])
         runs under torch.no_grad() on all k + 1 observation rows, pf_gae (BatchEngine.gae) supplies advantages, returns and logp.
         Returns a dict with the vector envs' keys: obs [k, n, D] the policy's inputs, actions, mean, logp (None without a log_std),
@@ -195,8 +221,9 @@ class MAFixedwingDogfightEnv(WorldRollout):
         episode accounting is carried from one collect(stats=True) to the next and sees only their steps: a step(), rollout() or
         collect() without stats in between advances the env behind its back, and the first episode_return / episode_length after
         it would lack those steps -- reset() the env before switching. reset() and reset_envs() zero the carries of the lanes they
-        reset; reset(seed=other) keeps the running moments."""
-        return self._world_collect(policy, value_fn, k_steps, gamma, lam, opponent, stats, normalize_reward)
+        reset; reset(seed=other) keeps the running moments.
+        `opponent` may be a pool and outcomes=True adds outcome and outcome_counts to the batch, both as rollout() describes them."""
+        return self._world_collect(policy, value_fn, k_steps, gamma, lam, opponent, stats, normalize_reward, outcomes)
 
     # ------------------------------------------------------------------ ma_fixedwing_base_env.py:272-334
     def step(self, actions: dict):

@@ -123,7 +123,7 @@ class MAQuadXHoverEnv(WorldRollout):
         f = self.engine.flags()
         return {"collision": lambda: (f & L.F_INFO_COLLISION) != 0, "out_of_bounds": lambda: (f & L.F_INFO_OOB) != 0}
 
-    def rollout(self, policy, k_steps: int, store_mean: bool = False):
+    def rollout(self, policy, k_steps: int, store_mean: bool = False, outcomes: bool = False):
         """`k_steps` closed-loop env steps of every copy, every action computed on the device by `policy` (a pyflyt_amd.MLPPolicy) --
         the loop of policy_act and step() without the host, for shared_world False and True alike: a copy whose drones have ALL
         finished is reset on the device in the next step, which is no transition for any of them (BatchEngine.rollout_policy_worlds,
@@ -132,10 +132,14 @@ class MAQuadXHoverEnv(WorldRollout):
         agent -- t.view(k, num_envs, agents, ...) reads them per copy and drone. They belong to the engine and are overwritten by
         the next call with the same k_steps. `valid` is False where a drone sat the step out (finished before it; its reward and
         flags read 0) and on the step that reset its copy; engine.world_done is the latch. The exploration noise's step index
-        advances by k_steps per call and restarts with reset(seed=...). Afterwards `agents` is the full list."""
-        return self._world_rollout(policy, k_steps, None, store_mean)
+        advances by k_steps per call and restarts with reset(seed=...). Afterwards `agents` is the full list.
+        outcomes=True appends outcome [k, n] uint8 (pf_outcome_bit of every episode that ended: collision, out of bounds, or neither =
+        ran to the limit) and outcome_counts [1, 16] int64 (this call's episodes by slot, and in slot 10 the copies that finished and
+        were reset; episode_outcomes_dict() reads it back): one more launch per step."""
+        return self._world_rollout(policy, k_steps, None, store_mean, outcomes)
 
-    def collect(self, policy, value_fn, k_steps: int, gamma: float = 0.99, lam: float = 0.95, stats: bool = False, normalize_reward: bool = False):
+    def collect(self, policy, value_fn, k_steps: int, gamma: float = 0.99, lam: float = 0.95, stats: bool = False, normalize_reward: bool = False,
+                outcomes: bool = False):
         """One PPO batch from rollout()'s loop, as the vector envs' collect(): `value_fn` (a float32 [M, D] tensor -> [M] or [M, 1])
         runs under torch.no_grad() on all k + 1 observation rows, pf_gae (BatchEngine.gae) supplies advantages, returns and logp.
         Returns a dict with the vector envs' keys (obs, actions, mean, logp, values, advantages, returns, valid, reward, terminated,
@@ -146,8 +150,9 @@ class MAQuadXHoverEnv(WorldRollout):
         MAFixedwingDogfightEnv.collect describes them (pf_traj_stats_masked with `valid` as the mask: the steps a finished drone sits
         out and the step that resets its copy are in no return, length or moment; a copy is reset only after every drone finished in
         a valid step, which zeroed that lane's carries). The accounting sees the steps of collect(stats=True) only: reset() before
-        mixing it with step(), rollout() or a collect() without stats."""
-        return self._world_collect(policy, value_fn, k_steps, gamma, lam, None, stats, normalize_reward)
+        mixing it with step(), rollout() or a collect() without stats.
+        outcomes=True adds outcome and outcome_counts as rollout() describes them."""
+        return self._world_collect(policy, value_fn, k_steps, gamma, lam, None, stats, normalize_reward, outcomes)
 
     # ------------------------------------------------------------------ ma_quadx_base_env.py:309-371
     def step(self, actions: dict):

@@ -41,6 +41,8 @@ class TrainOps:
     _wtraj = None     # dict: rollout_policy_worlds()'s trajectory tensors, for the last k
     _wctraj = None    # dict: collect_rollout_worlds()'s (observations in one [k + 1, n, D] buffer), for the last k
     _opp_act = None   # [n, action width] float32: rollout_policy_worlds()'s opponent actions before the merge
+    _world_outcome = None  # [n] uint8: episode_outcomes' world latch as the world rollouts keep it (BatchEngine.world_outcome)
+    _oc_last = None   # [G, 16] int64: the outcome counts of the last closed loop with outcomes=True
 
     def _lazy(self, name, make, keep=None):
         """self.<name> of the list above: made by make() at first use, and again when keep(it) is false (tensors of another size)."""
@@ -191,6 +193,83 @@ class TrainOps:
         a.summary, a.ret_moments = _ptr(ts["summary"]), _ptr(ts["ret_moments"])
         self._launch(self.lib.pf_traj_stats if valid is None else self.lib.pf_traj_stats_masked, C.byref(a), k)
         return (ts["episode_return"] if store_steps else None), (ts["episode_length"] if store_steps else None), ts["summary"]
+
+    # ------------------------------------------------------------------ why episodes end
+    def _outcome_shape(self, k, info_given, n_groups, agents_per_world, has_reset, has_latch):
+        """pf_episode_outcomes' refusals that need no tensor, in the library's order; returns A."""
+        if self.params.task == L.TASK_NONE:
+            raise ValueError("episode_outcomes needs an engine with an env task")
+        if not info_given and k != 1:
+            raise ValueError(f"info is required for a trajectory of k > 1 steps (the live state holds the words of one step), got k = {k}")
+        if isinstance(n_groups, bool) or not isinstance(n_groups, int) or not 1 <= n_groups <= L.PF_OUTCOME_MAX_GROUPS:
+            raise ValueError(f"n_groups must be an int in 1..{L.PF_OUTCOME_MAX_GROUPS}, got {n_groups!r}")
+        A = int(agents_per_world)
+        if not 1 <= A <= 64 or self.n % A != 0:
+            raise ValueError(f"agents_per_world must be in 1..64 and divide the lane count {self.n}, got {agents_per_world}")
+        if A > 1 and k != 1:
+            raise ValueError(f"the world form (agents_per_world > 1) runs once per step: k must be 1, got {k}")
+        if A > 1 and not (has_reset and has_latch):
+            raise ValueError("world_reset (world_sync's reset mask of this step) and world_latch are required with agents_per_world > 1")
+        if A == 1 and has_reset:
+            raise ValueError("world_reset must be None with agents_per_world == 1 (there are no worlds to tally)")
+        return A
+
+    def episode_outcomes(self, terminated, truncated, counts, valid=None, info=None, group=None, n_groups: int = 1, agents_per_world: int = 1,
+                         world_reset=None, world_latch=None, outcome_out=None):
+        """pf_episode_outcomes: why the episodes of a trajectory ended, counted per group of lanes into `counts` ([n_groups, 16] int64,
+        ADDED to in place; include/pyflyt_amd.h has the slots and the bits). terminated / truncated [k, n] bool / uint8 (or [n]: one
+        step) as a rollout wrote them; valid [k, n] or None: whose ended episodes are counted (pf_world_sync's); info [k, n, 2] int32
+        in final_info's layout, or None = the words of the engine's state as the env step left it (one step only); group [n] int32
+        in 0..n_groups-1 or None; outcome_out [k, n] uint8 or None: the byte of every ended episode. With agents_per_world > 1 (one
+        step): world_reset [n], this step's reset mask of world_sync, and world_latch [n] uint8, the caller's (self.world_outcome is
+        the world rollouts'). One launch, nothing synchronises. Returns counts."""
+        K.ranked(terminated, "terminated", f"{{name}} is required: a bool / uint8 tensor of shape (k, {self.n}) or ({self.n},)")
+        k = 1 if terminated.dim() == 1 else int(terminated.shape[0])
+        if k < 1:
+            raise ValueError("terminated must hold at least one step")
+        A = self._outcome_shape(k, info is not None, n_groups, agents_per_world, world_reset is not None, world_latch is not None)
+        rows = ((k, self.n), (self.n,)) if k == 1 else ((k, self.n),)
+        need = "{name} is required: a tensor of shape {shape}"
+        K.tensor(self.device, terminated, "terminated", rows, K.FLAGS, required=need)
+        K.tensor(self.device, truncated, "truncated", rows, K.FLAGS, required=need)
+        K.tensor(self.device, counts, "counts", (n_groups, L.PF_OUTCOME_SLOTS), torch.int64, required=need)
+        K.tensor(self.device, valid, "valid", rows, K.FLAGS)
+        K.tensor(self.device, info, "info", ((k, self.n, 2), (self.n, 2)) if k == 1 else ((k, self.n, 2),), torch.int32)
+        K.tensor(self.device, group, "group", (self.n,), torch.int32)
+        K.tensor(self.device, world_reset, "world_reset", (self.n,), K.FLAGS)
+        K.tensor(self.device, world_latch, "world_latch", (self.n,), torch.uint8)
+        K.tensor(self.device, outcome_out, "outcome_out", rows, torch.uint8)
+        a = L.PfOutcome()
+        a.terminated, a.truncated, a.valid, a.info = _ptr(terminated), _ptr(truncated), _ptr(valid), _ptr(info)
+        a.state = _ptr(self.state) if info is None else None
+        a.group, a.n_groups, a.world_reset, a.world_latch = _ptr(group), n_groups, _ptr(world_reset), _ptr(world_latch)
+        a.outcome_out, a.counts = _ptr(outcome_out), _ptr(counts)
+        self._launch(self.lib.pf_episode_outcomes, C.byref(a), k, A)
+        return counts
+
+    @property
+    def world_outcome(self):
+        """[n] uint8, made at first use: episode_outcomes' world latch as the world rollouts keep it, beside world_done -- the byte
+        of the episode each lane last ended. Nothing ever clears it: a world is tallied only after every one of its lanes has ended
+        again, and a world reset from outside is not tallied."""
+        return self._lazy("_world_outcome", lambda: torch.zeros(self.n, dtype=torch.uint8, device=self.device))
+
+    def _outcome_block(self, t, k, group, n_groups):
+        """What a closed loop with outcomes=True writes, kept with its trajectory tensors `t`: t["outcome"] [k, n] uint8 and
+        t["outcome_counts"] [n_groups, 16] int64, zeroed here -- the counts are of this call's episodes. Returns the filled
+        pf_outcome_args block but for the per-step pointers."""
+        K.tensor(self.device, group, "group", (self.n,), torch.int32)
+        if t.get("outcome") is None:
+            t["outcome"] = torch.empty(k, self.n, dtype=torch.uint8, device=self.device)
+        c = t.get("outcome_counts")
+        if c is None or c.shape[0] != n_groups:
+            c = t["outcome_counts"] = torch.empty(n_groups, L.PF_OUTCOME_SLOTS, dtype=torch.int64, device=self.device)
+        c.zero_()
+        self._oc_last = c
+        a = L.PfOutcome()
+        a.group, a.n_groups, a.counts = _ptr(group), n_groups, _ptr(c)
+        a.state = _ptr(self.state)
+        return a
 
     # ------------------------------------------------------------------ the loss
     @staticmethod
