@@ -813,6 +813,83 @@ size_t pf_sizeof_adam(void);
 size_t pf_adam_workspace_bytes(int64_t total_numel);
 int pf_adam_step(pf_ctx* ctx, const pf_adam_args* a, void* workspace, size_t workspace_bytes, void* stream);
 
+/* PPO's usual options, which nothing around the library can add (the means and values of pf_ppo_grad never exist as tensors):
+ * pf_ppo_loss_opt and pf_ppo_grad_opt are pf_ppo_loss and pf_ppo_grad with a clipped value loss and a penalty on means that leave the
+ * action box. Same argument blocks, workspaces and number of launches; every clause of those two contracts holds, and what the
+ * options add is stated here. (Added without a new PF_ABI_VERSION: new functions and a new block, every existing struct as it was.)
+ *   - OPTIONS OFF. With options == NULL, or with values_old == NULL and bounds_coef == 0, the call IS pf_ppo_loss / pf_ppo_grad (the
+ *     same kernels are launched): every output has their bits, stats[12..15] = 0. An option that is on leaves the other's outputs
+ *     as they are: value clipping alone gives pf_ppo_loss's grad_mean bits, the bounds loss alone its grad_value bits.
+ *   - VALUE CLIPPING (values_old given). Per row, V the new value, R the return, kv = vf_coef * w32, all float32:
+ *         e = V - V_old;  out = |e| > clip_vf;  vc = e > 0 ? V_old + clip_vf : V_old - clip_vf;
+ *         dv = V - R;  dc = vc - R;  use_c = out && dc^2 > dv^2      (decided exactly: it is |dc| > |dv|)
+ *     The row adds (use_c ? dc : dv)^2 to the value-loss sum, the square taken in double from the float32 difference:
+ *     value_loss = 1/2 sum w (...). grad_value = use_c ? 0 : kv * dv. A row inside the clip range takes pf_ppo_loss's path exactly
+ *     (there is no V_old + (V - V_old) round trip). The sums behind slot 9 stay those of V - R. stats[12] = sum w [out] over the
+ *     valid rows: a whole-number count times w, exact like slot 6. Every choice is a select: a NaN in an invalid row's values_old
+ *     reaches nothing.
+ *   - BOUNDS LOSS (bounds_coef > 0). Per row and column c < A, float32: hx = fmaxf(m_c - hi_c, 0), lx = fmaxf(lo_c - m_c, 0); the
+ *     row's term is b = sum_c (hx * hx + lx * lx), c ascending from 0. bounds_loss = sum w b over the valid rows, in double,
+ *     reported in stats[13]; loss (slot 1) gains bounds_coef * bounds_loss. grad_mean_ic gains ((2 * bounds_coef) * w32) * (hx - lx),
+ *     added in float32 to the surrogate's term on every valid row, whether or not its surrogate branch is live; invalid rows stay
+ *     exact zeros by selection. grad_log_std has no bounds term. stats[14] and stats[15] stay 0.
+ *   - pf_ppo_grad_opt is, by definition, pf_mlp_forward x 2 -> pf_ppo_loss_opt -> pf_mlp_backward x 2 on the same inputs: the network
+ *     gradients have the composition's bits; grad_log_std and the summed stats agree within the reordering of a double sum, as for
+ *     pf_ppo_grad; slots 0, 7, 8, 10, 11 and 12 are the same bits. The critic's launch reads values_old, one more [M] stream.
+ *   - ERRORS, beyond those of pf_ppo_loss / pf_ppo_grad. PF_ERR_ARG, pf_last_error naming the argument: clip_vf not finite or <= 0
+ *     while values_old is given; bounds_coef negative or not finite; a NaN bound, or lo > hi, in the first A columns (read only when
+ *     bounds_coef > 0); pf_ppo_grad_opt: values_old overlapping an output or the workspace. */
+typedef struct pf_ppo_options {
+  float clip_vf;             /* finite, > 0; read only when values_old != NULL */
+  const float* values_old;   /* [M], the batch's values; NULL = no value clipping */
+  float bounds_coef;         /* finite, >= 0; 0 = no bounds loss */
+  float bounds_lo[8], bounds_hi[8];  /* the first A are used; lo <= hi; -inf / +inf = open on that side; NaN refused */
+} pf_ppo_options;
+size_t pf_sizeof_ppo_options(void);
+int pf_ppo_loss_opt(pf_ctx* ctx, const pf_ppo_loss_args* a, const pf_ppo_options* options, size_t rows, int width, void* stream);
+int pf_ppo_grad_opt(pf_ctx* ctx, const pf_ppo_grad_args* a, const pf_ppo_options* options, int64_t rows, void* workspace, size_t workspace_bytes,
+                    void* stream);
+
+/* What a PPO recipe decides from the measured KL, on the device: one launch of one thread behind the loss, no host synchronisation,
+ * capturable. Any context. (Added without a new PF_ABI_VERSION: a new function and a new block.)
+ *   - kl = stats[5] (approx_kl of pf_ppo_loss / pf_ppo_grad and their _opt forms).
+ *   - GATE. *gate = kl <= stop_factor * target_kl ? 1 : 0. A NaN closes it; with stop_factor = +inf no number does.
+ *   - LEARNING RATE (adapt = 1). kl > lr_high * target_kl: lr = fmaxf(lr / lr_factor, lr_min); kl < lr_low * target_kl:
+ *     lr = fminf(lr * lr_factor, lr_max); otherwise, and for a NaN, lr is unchanged. lr is *lr_dev, read and written in this call;
+ *     with adapt = 0 it is not written, and the five lr_ arguments are not read.
+ *   - ARITHMETIC. The comparisons are in double on the widened float32 arguments (the product in double); the two lr operations
+ *     are float32.
+ *   - STATE. state[4], double, read and then overwritten: 0 the kl read; 1 the lr after the call (0 without lr_dev); 2 the gate;
+ *     3 the closed gates so far. A zeroed block is a fresh one.
+ *   - ERRORS. PF_ERR_ARG, pf_last_error naming the argument: a NULL ctx, argument block, stats, gate or state; target_kl not finite
+ *     or <= 0; stop_factor < 1 or NaN; adapt other than 0 / 1; with adapt = 1: a NULL lr_dev, lr_factor not finite or <= 1,
+ *     not 0 < lr_low < lr_high < inf, not 0 < lr_min <= lr_max < inf; gate, state, lr_dev and stats overlapping. */
+typedef struct pf_kl_control_args {
+  const double* stats;     /* a pf_ppo_loss / pf_ppo_grad stats block; slot 5 is read */
+  float target_kl;         /* finite, > 0 */
+  float stop_factor;       /* >= 1, +inf = the gate never closes on a number */
+  int32_t adapt;           /* 0 / 1: change *lr_dev in this call */
+  float lr_factor;         /* > 1 */
+  float lr_low, lr_high;   /* 0 < lr_low < lr_high, multiples of target_kl */
+  float lr_min, lr_max;    /* 0 < lr_min <= lr_max, finite */
+  float* lr_dev;           /* [1] in/out; required when adapt = 1 */
+  uint32_t* gate;          /* [1] out: 1 = take the step */
+  double* state;           /* [4] in/out */
+} pf_kl_control_args;
+size_t pf_sizeof_kl_control(void);
+int pf_kl_control(pf_ctx* ctx, const pf_kl_control_args* a, void* stream);
+
+/* pf_adam_step with one more device word: *gate (pf_kl_control's), read by the update kernel. Same block, workspace and launches.
+ *   - *gate != 0: parameters, moments and state[0..4] have pf_adam_step's bits.
+ *   - *gate == 0: SKIP's rule: no parameter, no moment and not t changes; slot 1 reports the norm, slot 2 a coef of 0.
+ *   - state[5] counts the calls a closed gate skipped (kept, not zeroed, by this function; pf_adam_step writes 0 there). Slot 4 stays
+ *     the count of calls skipped for a norm that is not finite, whatever the gate.
+ *   - The gate is read on the device and applied as a selection; nothing waits for the host. Once a step has pushed the KL over the
+ *     limit, later epochs on the same batch see unchanged parameters, hence the same KL, and are skipped too: early stopping
+ *     without a latch.
+ *   - ERRORS. pf_adam_step's, and PF_ERR_ARG for a NULL gate or one that overlaps a tensor, state, workspace or lr_dev. */
+int pf_adam_step_gated(pf_ctx* ctx, const pf_adam_args* a, const uint32_t* gate, void* workspace, size_t workspace_bytes, void* stream);
+
 /* The world-level auto-reset of the multi-agent envs (PF_TASK_DOGFIGHT, PF_TASK_MA_HOVER), which exist with auto-reset OFF only: run
  * between two env steps, it tells which lanes of the step just taken were real transitions, blanks the rows of the agents that had
  * finished before it, keeps the per-lane latch "this agent's episode has ended and its world has not been reset yet", and names

@@ -5,6 +5,7 @@ from __future__ import annotations
 import torch
 
 FLAGS = (torch.bool, torch.uint8)  # what a trajectory's terminated / truncated / episode_start and a mask may be
+GATE = (torch.int32, torch.uint32) if hasattr(torch, "uint32") else (torch.int32,)  # pf_kl_control's gate word, as a tensor
 NO_F32 = "{name} must be a float32 tensor of shape {shape}"  # (tensor(required=...): the commonest wording for what is no tensor at all)
 
 

@@ -82,6 +82,7 @@ PfAdam, PF_ADAM_MAX_TENSORS = _STRUCTS["pf_adam_args"], _DEFINES["PF_ADAM_MAX_TE
 PfWorldSync = _STRUCTS["pf_world_sync_args"]
 PfTrajStatsMasked = _STRUCTS["pf_traj_stats_masked_args"]
 PfPpoGradArgs = _STRUCTS["pf_ppo_grad_args"]
+PfPpoOptions, PfKlControl = _STRUCTS["pf_ppo_options"], _STRUCTS["pf_kl_control_args"]
 PfOutcome, PF_OUTCOME_SLOTS, PF_OUTCOME_MAX_GROUPS = _STRUCTS["pf_outcome_args"], _DEFINES["PF_OUTCOME_SLOTS"], _DEFINES["PF_OUTCOME_MAX_GROUPS"]
 # pf_episode_outcomes' slots by name (include/pyflyt_amd.h): 0-9 per agent, 10-13 per world
 OUTCOME_SLOT_NAMES = ("episodes", "terminated", "truncated", "collision", "out_of_bounds", "complete", "dead", "nonfinite", "second_word_sum", "clean",
@@ -165,6 +166,12 @@ def lib():
     L.pf_adam_workspace_bytes.argtypes = [C.c_int64]
     L.pf_adam_workspace_bytes.restype = C.c_size_t
     L.pf_adam_step.argtypes = [C.c_void_p, C.POINTER(PfAdam), C.c_void_p, C.c_size_t, C.c_void_p]
+    L.pf_sizeof_ppo_options.restype = C.c_size_t
+    L.pf_ppo_loss_opt.argtypes = [C.c_void_p, C.POINTER(PfPpoLoss), C.POINTER(PfPpoOptions), C.c_size_t, C.c_int, C.c_void_p]
+    L.pf_ppo_grad_opt.argtypes = [C.c_void_p, C.POINTER(PfPpoGradArgs), C.POINTER(PfPpoOptions), C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.pf_sizeof_kl_control.restype = C.c_size_t
+    L.pf_kl_control.argtypes = [C.c_void_p, C.POINTER(PfKlControl), C.c_void_p]
+    L.pf_adam_step_gated.argtypes = [C.c_void_p, C.POINTER(PfAdam), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     L.pf_sizeof_world_sync.restype = C.c_size_t
     L.pf_world_sync.argtypes = [C.c_void_p, C.POINTER(PfWorldSync), C.c_int, C.c_void_p]
     L.pf_sizeof_outcome.restype = C.c_size_t
@@ -175,7 +182,8 @@ def lib():
             or L.pf_sizeof_gae() != C.sizeof(PfGae) or L.pf_sizeof_traj_stats() != C.sizeof(PfTrajStats) \
             or L.pf_sizeof_ppo_loss() != C.sizeof(PfPpoLoss) or L.pf_sizeof_mlp() != C.sizeof(PfMlp) or L.pf_sizeof_adam() != C.sizeof(PfAdam) \
             or L.pf_sizeof_world_sync() != C.sizeof(PfWorldSync) or L.pf_sizeof_ppo_grad() != C.sizeof(PfPpoGradArgs) \
-            or L.pf_sizeof_traj_stats_masked() != C.sizeof(PfTrajStatsMasked) or L.pf_sizeof_outcome() != C.sizeof(PfOutcome):
+            or L.pf_sizeof_traj_stats_masked() != C.sizeof(PfTrajStatsMasked) or L.pf_sizeof_outcome() != C.sizeof(PfOutcome) \
+            or L.pf_sizeof_ppo_options() != C.sizeof(PfPpoOptions) or L.pf_sizeof_kl_control() != C.sizeof(PfKlControl):
         raise PyFlytAmdError("struct layout mismatch between pyflyt_amd/_lib.py and include/pyflyt_amd.h")
     if L.pf_abi_version() != PF_ABI_VERSION:
         raise PyFlytAmdError("ABI version mismatch between pyflyt_amd/_lib.py and libpyflyt_amd.so")

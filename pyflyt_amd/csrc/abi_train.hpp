@@ -12,6 +12,7 @@
 #include "mlp.hpp"
 #include "ppo_grad.hpp"
 #include "adam.hpp"
+#include "kl_control.hpp"
 #include "world_sync.hpp"
 #include "outcomes.hpp"
 
@@ -24,6 +25,22 @@ static int launch_policy_act(pf_ctx* ctx, const pf::ActK& AK, int64_t rows, void
   const int grid = tiles < (int64_t)ctx->act_grid_cap ? (int)tiles : ctx->act_grid_cap;
   hipLaunchKernelGGL(pf::policy_act_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, AK);
   return launched(ctx);
+}
+// What pf_ppo_loss and pf_ppo_grad launch first: the advantages' moments, into `fin`; vbytes / vmask: how the kernels behind it read `valid`.
+struct ppo_adv {
+  const uint8_t* vbytes;
+  uint32_t vmask;
+  double* fin;
+};
+// a head's block: MlpK, what pf_ppo_grad_args gives both heads, and the call's advantage block and rows of partials
+template <class KT>
+static KT ppo_grad_head(const pf_ppo_grad_args* a, const pf_mlp* net, float* part, int64_t rows, const ppo_adv& adv, double* stat_part) {
+  KT K;
+  static_cast<pf::MlpK&>(K) = pf::MlpK{*net, a->x, nullptr, part, (int)rows};
+  K.clip = a->clip, K.vf_coef = a->vf_coef, K.normalize = a->normalize_advantage;
+  K.log_std = a->log_std, K.actions = a->actions, K.logp_old = a->logp_old, K.advantages = a->advantages, K.returns = a->returns;
+  K.vbytes = adv.vbytes, K.vmask = adv.vmask, K.fin = adv.fin, K.stat_part = stat_part;
+  return K;
 }
 
 extern "C" {
@@ -144,12 +161,6 @@ static int ppo_coef_check(pf_ctx* ctx, const char* who, float clip, float vf_coe
   if (normalize_advantage != 0 && normalize_advantage != 1) return arg_fail(ctx, who, "normalize_advantage must be 0 or 1");
   return PF_OK;
 }
-// What pf_ppo_loss and pf_ppo_grad launch first: the advantages' moments, into `fin`; vbytes / vmask: how the kernels behind it read `valid`.
-struct ppo_adv {
-  const uint8_t* vbytes;
-  uint32_t vmask;
-  double* fin;
-};
 static ppo_adv launch_ppo_adv(pf_ctx* ctx, const float* advantages, const uint8_t* valid, size_t rows, hipStream_t s) {
   double* adv_part = ctx->ppo_scratch + pf::kPpoAdvOffset;
   // (no valid: the byte loads read the advantages' first M bytes and the mask drops them)
@@ -159,9 +170,38 @@ static ppo_adv launch_ppo_adv(pf_ctx* ctx, const float* advantages, const uint8_
   hipLaunchKernelGGL(pf::ppo_adv_finish_kernel, dim3(1), dim3(pf::kPpoBlock), 0, s, adv_part, (int)grid, r.fin);
   return r;
 }
-int pf_ppo_loss(pf_ctx* ctx, const pf_ppo_loss_args* a, size_t rows, int width, void* stream) {
-  static const char* who = "pf_ppo_loss";
-  if (!ctx || !a) return fail(ctx, PF_ERR_ARG, "pf_ppo_loss: ctx and the argument block are required");
+// What pf_ppo_loss_opt and pf_ppo_grad_opt check of their options, A = the action width. *on = an option is on (off: the call is the
+// one without options); K: the kernels' block, an option that is off filled so that nothing of it is chosen (`readable`: M floats)
+static int ppo_options_check(pf_ctx* ctx, const char* who, const pf_ppo_options* o, int A, const float* readable, pf::PpoOptK* K, bool* on) {
+  *on = false;
+  if (!o) return PF_OK;
+  if (o->values_old && !(o->clip_vf > 0.0f && o->clip_vf < INFINITY)) return arg_fail(ctx, who, "clip_vf must be finite and > 0 (values_old is given)");
+  if (!(o->bounds_coef >= 0.0f && o->bounds_coef < INFINITY)) return arg_fail(ctx, who, "bounds_coef must be finite and >= 0");
+  const bool bnd = o->bounds_coef > 0.0f;
+  for (int c = 0; bnd && c < A; ++c) {
+    if (o->bounds_lo[c] != o->bounds_lo[c]) return arg_fail(ctx, who, "bounds_lo must not hold a NaN (-infinity: open below)");
+    if (o->bounds_hi[c] != o->bounds_hi[c]) return arg_fail(ctx, who, "bounds_hi must not hold a NaN (+infinity: open above)");
+    if (o->bounds_lo[c] > o->bounds_hi[c]) return arg_fail(ctx, who, "bounds_lo must be <= bounds_hi in every column");
+  }
+  K->values_old = o->values_old ? o->values_old : readable;
+  K->vclip = o->values_old ? 1 : 0;
+  K->bnd = bnd ? 1 : 0;
+  K->clip_vf = o->values_old ? o->clip_vf : 1.0f;
+  K->bounds_coef = o->bounds_coef;
+  for (int c = 0; c < pf::kPpoMaxA; ++c) {
+    K->lo[c] = bnd && c < A ? o->bounds_lo[c] : -INFINITY;
+    K->hi[c] = bnd && c < A ? o->bounds_hi[c] : INFINITY;
+  }
+  *on = K->vclip || K->bnd;
+  return PF_OK;
+}
+// pf_ppo_loss (o = NULL) and pf_ppo_loss_opt
+static int ppo_loss_call(pf_ctx* ctx, const char* who, const pf_ppo_loss_args* a, const pf_ppo_options* o, size_t rows, int width, void* stream) {
+  if (!ctx || !a) {
+    char buf[96];
+    snprintf(buf, sizeof(buf), "%s: ctx and the argument block are required", who);
+    return fail(ctx, PF_ERR_ARG, buf);
+  }
   if (rows < 1) return arg_fail(ctx, who, "rows must be >= 1");
   if (width < 1 || width > pf::kPpoMaxA) return arg_fail(ctx, who, "width must be in 1..8");
   const arg_ptr required[] = {{"mean", a->mean}, {"log_std", a->log_std}, {"actions", a->actions}, {"logp_old", a->logp_old},
@@ -169,6 +209,9 @@ int pf_ppo_loss(pf_ctx* ctx, const pf_ppo_loss_args* a, size_t rows, int width, 
                               {"grad_value", a->grad_value}, {"grad_log_std", a->grad_log_std}, {"stats", a->stats}, {nullptr, nullptr}};
   if (int rc = require_args(ctx, who, required)) return rc;
   if (int rc = ppo_coef_check(ctx, who, a->clip, a->vf_coef, a->ent_coef, a->normalize_advantage)) return rc;
+  pf::PpoOptMainK KO;
+  bool opt = false;
+  if (int rc = ppo_options_check(ctx, who, o, width, a->returns, &KO.o, &opt)) return rc;
   if (int rc = ensure_device(ctx)) return rc;
   hipStream_t s = (hipStream_t)stream;
   const ppo_adv adv = launch_ppo_adv(ctx, a->advantages, a->valid, rows, s);
@@ -179,13 +222,33 @@ int pf_ppo_loss(pf_ctx* ctx, const pf_ppo_loss_args* a, size_t rows, int width, 
   // (one float4 per row where the rows are four wide and the caller's pointers allow it; the same arithmetic either way)
   const bool vec = width == 4 && (((uintptr_t)a->actions | (uintptr_t)a->mean | (uintptr_t)a->grad_mean) & 15) == 0;
   using pf::ppo_main_kernel;
-  void (*const by_width[pf::kPpoMaxA])(pf::PpoK, size_t, const double*, double*) = {ppo_main_kernel<1, false>, ppo_main_kernel<2, false>, ppo_main_kernel<3, false>, ppo_main_kernel<4, false>,
-                                                                                    ppo_main_kernel<5, false>, ppo_main_kernel<6, false>, ppo_main_kernel<7, false>, ppo_main_kernel<8, false>};
-  const auto main_kernel = vec ? ppo_main_kernel<4, true> : by_width[width - 1];
+  using pf::PpoK, pf::PpoOptMainK;
+  void (*const by_width[pf::kPpoMaxA])(PpoK, size_t, const double*, double*) = {
+      ppo_main_kernel<1, false, PpoK>, ppo_main_kernel<2, false, PpoK>, ppo_main_kernel<3, false, PpoK>, ppo_main_kernel<4, false, PpoK>,
+      ppo_main_kernel<5, false, PpoK>, ppo_main_kernel<6, false, PpoK>, ppo_main_kernel<7, false, PpoK>, ppo_main_kernel<8, false, PpoK>};
+  if (opt) {  // the instantiations with the options; the same choice of path
+    void (*const opt_by_width[pf::kPpoMaxA])(PpoOptMainK, size_t, const double*, double*) = {
+        ppo_main_kernel<1, false, PpoOptMainK>, ppo_main_kernel<2, false, PpoOptMainK>, ppo_main_kernel<3, false, PpoOptMainK>, ppo_main_kernel<4, false, PpoOptMainK>,
+        ppo_main_kernel<5, false, PpoOptMainK>, ppo_main_kernel<6, false, PpoOptMainK>, ppo_main_kernel<7, false, PpoOptMainK>, ppo_main_kernel<8, false, PpoOptMainK>};
+    static_cast<PpoK&>(KO) = K;
+    const auto main_opt_kernel = vec ? ppo_main_kernel<4, true, PpoOptMainK> : opt_by_width[width - 1];
+    hipLaunchKernelGGL(main_opt_kernel, dim3(grid), dim3(pf::kPpoBlock), 0, s, KO, rows, (const double*)adv.fin, main_part);
+    hipLaunchKernelGGL(pf::ppo_finish_opt_kernel, dim3(1), dim3(pf::kPpoBlock), 0, s, (const double*)main_part, (int)grid, (const double*)adv.fin, a->log_std,
+                       width, a->vf_coef, a->ent_coef, a->stats, a->grad_log_std, KO.o.vclip, KO.o.bnd, KO.o.bounds_coef);
+    return launched(ctx);
+  }
+  const auto main_kernel = vec ? ppo_main_kernel<4, true, PpoK> : by_width[width - 1];
   hipLaunchKernelGGL(main_kernel, dim3(grid), dim3(pf::kPpoBlock), 0, s, K, rows, (const double*)adv.fin, main_part);
   hipLaunchKernelGGL(pf::ppo_finish_kernel, dim3(1), dim3(pf::kPpoBlock), 0, s, (const double*)main_part, (int)grid, (const double*)adv.fin, a->log_std, width,
                      a->vf_coef, a->ent_coef, a->stats, a->grad_log_std);
   return launched(ctx);
+}
+int pf_ppo_loss(pf_ctx* ctx, const pf_ppo_loss_args* a, size_t rows, int width, void* stream) {
+  return ppo_loss_call(ctx, "pf_ppo_loss", a, nullptr, rows, width, stream);
+}
+size_t pf_sizeof_ppo_options(void) { return sizeof(pf_ppo_options); }
+int pf_ppo_loss_opt(pf_ctx* ctx, const pf_ppo_loss_args* a, const pf_ppo_options* options, size_t rows, int width, void* stream) {
+  return ppo_loss_call(ctx, "pf_ppo_loss_opt", a, options, rows, width, stream);
 }
 // ---- pf_mlp_forward, pf_mlp_backward and pf_ppo_grad: what they check of a network and of `rows`, and the pieces of their launches
 static const char* mlp_shape_error(const pf_mlp* q) {
@@ -309,8 +372,9 @@ size_t pf_ppo_grad_workspace_bytes(const pf_mlp* actor, const pf_mlp* critic, in
   const int grid = pf::mlp_grid(rows);
   return pf::ppo_grad_stat_bytes(grid) + sizeof(float) * (size_t)grid * ((size_t)pf::mlp_param_count(*actor, nullptr) + (size_t)pf::mlp_param_count(*critic, nullptr));
 }
-int pf_ppo_grad(pf_ctx* ctx, const pf_ppo_grad_args* a, int64_t rows, void* workspace, size_t workspace_bytes, void* stream) {
-  static const char* who = "pf_ppo_grad";
+// pf_ppo_grad (o = NULL) and pf_ppo_grad_opt
+static int ppo_grad_call(pf_ctx* ctx, const char* who, const pf_ppo_grad_args* a, const pf_ppo_options* o, int64_t rows, void* workspace, size_t workspace_bytes,
+                         void* stream) {
   if (!ctx) return arg_fail(ctx, who, "ctx is required");
   if (!a) return arg_fail(ctx, who, "the argument block is required");
   if (!a->actor) return arg_fail(ctx, who, "actor is required");
@@ -338,7 +402,10 @@ int pf_ppo_grad(pf_ctx* ctx, const pf_ppo_grad_args* a, int64_t rows, void* work
   if (workspace_bytes < need) return arg_fail(ctx, who, "workspace_bytes is below pf_ppo_grad_workspace_bytes(actor, critic, rows)");
   if (((uintptr_t)workspace & 7) != 0) return arg_fail(ctx, who, "workspace must be 8-byte aligned (it holds rows of double partial sums)");
   const size_t M = (size_t)rows, A = (size_t)a->actor->out_dim;
-  arg_span spans[7 + 15];
+  pf::PpoOptK KO;
+  bool opt = false;
+  if (int rc = ppo_options_check(ctx, who, o, (int)A, a->returns, &KO, &opt)) return rc;
+  arg_span spans[8 + 15];
   int ns = 0;
   spans[ns++] = {"x", a->x, sizeof(float) * M * a->actor->in_dim};
   spans[ns++] = {"log_std", a->log_std, sizeof(float) * A};
@@ -347,6 +414,7 @@ int pf_ppo_grad(pf_ctx* ctx, const pf_ppo_grad_args* a, int64_t rows, void* work
   spans[ns++] = {"advantages", a->advantages, sizeof(float) * M};
   spans[ns++] = {"returns", a->returns, sizeof(float) * M};
   if (a->valid) spans[ns++] = {"valid", a->valid, M};
+  if (o && o->values_old) spans[ns++] = {"values_old", o->values_old, sizeof(float) * M};
   const int n_read = ns;
   spans[ns++] = {"workspace", workspace, need};
   spans[ns++] = {"grad_log_std", a->grad_log_std, sizeof(float) * A};
@@ -360,10 +428,19 @@ int pf_ppo_grad(pf_ctx* ctx, const pf_ppo_grad_args* a, int64_t rows, void* work
   double* stat_part = (double*)workspace;
   float* const part0 = (float*)((char*)workspace + pf::ppo_grad_stat_bytes(grid));
   float* const part[2] = {part0, part0 + (size_t)grid * (size_t)pf::mlp_param_count(*a->actor, nullptr)};
-  const pf::PpoGradK<pf::kGradActor> KA{pf::MlpK{*a->actor, a->x, nullptr, part[0], (int)rows}, a->clip, a->vf_coef, a->normalize_advantage, a->log_std, a->actions,
-                                        a->logp_old, a->advantages, a->returns, adv.vbytes, adv.vmask, adv.fin, stat_part};
-  const pf::PpoGradK<pf::kGradCritic> KC{pf::MlpK{*a->critic, a->x, nullptr, part[1], (int)rows}, a->clip, a->vf_coef, a->normalize_advantage, a->log_std, a->actions,
-                                         a->logp_old, a->advantages, a->returns, adv.vbytes, adv.vmask, adv.fin, stat_part};
+  if (opt) {  // the heads with the options, the same seven launches
+    auto KA = ppo_grad_head<pf::PpoGradOptK<pf::kGradActor>>(a, a->actor, part[0], rows, adv, stat_part);
+    auto KC = ppo_grad_head<pf::PpoGradOptK<pf::kGradCritic>>(a, a->critic, part[1], rows, adv, stat_part);
+    KA.o = KC.o = KO;
+    hipLaunchKernelGGL(pf::mlp_backward_kernel<pf::PpoGradOptK<pf::kGradActor>>, dim3(grid), dim3(256), 0, s, KA);
+    hipLaunchKernelGGL(pf::mlp_backward_kernel<pf::PpoGradOptK<pf::kGradCritic>>, dim3(grid), dim3(256), 0, s, KC);
+    for (int k = 0; k < 2; ++k) launch_mlp_reduce(nets[k], gw[k], gb[k], part[k], grid, s);
+    hipLaunchKernelGGL(pf::ppo_finish_opt_kernel, dim3(1), dim3(pf::kPpoBlock), 0, s, (const double*)stat_part, grid, (const double*)adv.fin, a->log_std, (int)A,
+                       a->vf_coef, a->ent_coef, a->stats, a->grad_log_std, KO.vclip, KO.bnd, KO.bounds_coef);
+    return launched(ctx);
+  }
+  const auto KA = ppo_grad_head<pf::PpoGradK<pf::kGradActor>>(a, a->actor, part[0], rows, adv, stat_part);
+  const auto KC = ppo_grad_head<pf::PpoGradK<pf::kGradCritic>>(a, a->critic, part[1], rows, adv, stat_part);
   hipLaunchKernelGGL(pf::mlp_backward_kernel<pf::PpoGradK<pf::kGradActor>>, dim3(grid), dim3(256), 0, s, KA);
   hipLaunchKernelGGL(pf::mlp_backward_kernel<pf::PpoGradK<pf::kGradCritic>>, dim3(grid), dim3(256), 0, s, KC);
   for (int k = 0; k < 2; ++k) launch_mlp_reduce(nets[k], gw[k], gb[k], part[k], grid, s);
@@ -371,13 +448,21 @@ int pf_ppo_grad(pf_ctx* ctx, const pf_ppo_grad_args* a, int64_t rows, void* work
                      a->ent_coef, a->stats, a->grad_log_std);
   return launched(ctx);
 }
+int pf_ppo_grad(pf_ctx* ctx, const pf_ppo_grad_args* a, int64_t rows, void* workspace, size_t workspace_bytes, void* stream) {
+  return ppo_grad_call(ctx, "pf_ppo_grad", a, nullptr, rows, workspace, workspace_bytes, stream);
+}
+int pf_ppo_grad_opt(pf_ctx* ctx, const pf_ppo_grad_args* a, const pf_ppo_options* options, int64_t rows, void* workspace, size_t workspace_bytes, void* stream) {
+  return ppo_grad_call(ctx, "pf_ppo_grad_opt", a, options, rows, workspace, workspace_bytes, stream);
+}
 size_t pf_adam_workspace_bytes(int64_t total_numel) {
   if (total_numel < 1 || total_numel > (int64_t)INT32_MAX) return 0;
   return sizeof(double) * (pf::adam_grid_bound(total_numel) + pf::kAdamHeader);
 }
 // what pf_adam_step refuses, or null; `buf` holds a composed message
-static const char* adam_error(const pf_adam_args* a, const void* workspace, size_t workspace_bytes, char* buf, size_t len) {
+static const char* adam_error(const pf_adam_args* a, const void* workspace, size_t workspace_bytes, char* buf, size_t len, bool gated = false,
+                              const uint32_t* gate = nullptr) {
   if (!a) return "the argument block is required";
+  if (gated && !gate) return "gate is required";
   if (a->n_tensors < 1 || a->n_tensors > PF_ADAM_MAX_TENSORS) return "n_tensors must be in 1..PF_ADAM_MAX_TENSORS (32)";
   if (a->skip_nonfinite != 0 && a->skip_nonfinite != 1) return "skip_nonfinite must be 0 or 1";
   if (!a->lr_dev && !(a->lr >= 0.0f && a->lr < INFINITY)) return "lr must be finite and >= 0";
@@ -389,7 +474,7 @@ static const char* adam_error(const pf_adam_args* a, const void* workspace, size
   if (!a->state) return "state is required";
   if (!workspace) return "workspace is required";
   static const char* const kinds[4] = {"param", "grad", "exp_avg", "exp_avg_sq"};
-  arg_span spans[4 * PF_ADAM_MAX_TENSORS + 3];
+  arg_span spans[4 * PF_ADAM_MAX_TENSORS + 4];
   char names[4 * PF_ADAM_MAX_TENSORS][16];
   int ns = 0;
   int64_t total = 0;
@@ -416,15 +501,17 @@ static const char* adam_error(const pf_adam_args* a, const void* workspace, size
   spans[ns++] = {"state", a->state, sizeof(double) * 8};
   spans[ns++] = {"workspace", workspace, need};
   if (a->lr_dev) spans[ns++] = {"lr_dev", a->lr_dev, sizeof(float)};
+  if (gated) spans[ns++] = {"gate", gate, sizeof(uint32_t)};
   return spans_overlap(spans, ns, buf, len);
 }
-int pf_adam_step(pf_ctx* ctx, const pf_adam_args* a, void* workspace, size_t workspace_bytes, void* stream) {
-  static const char* who = "pf_adam_step";
+// pf_adam_step (gated = false) and pf_adam_step_gated
+static int adam_call(pf_ctx* ctx, const char* who, const pf_adam_args* a, bool gated, const uint32_t* gate, void* workspace, size_t workspace_bytes, void* stream) {
   if (!ctx) return arg_fail(ctx, who, "ctx is required");
   char buf[128];
-  if (const char* e = adam_error(a, workspace, workspace_bytes, buf, sizeof(buf))) return arg_fail(ctx, who, e);
+  if (const char* e = adam_error(a, workspace, workspace_bytes, buf, sizeof(buf), gated, gate)) return arg_fail(ctx, who, e);
   if (int rc = ensure_device(ctx)) return rc;
-  pf::AdamK K;
+  pf::AdamGatedK K;  // (the plain call passes the AdamK in it)
+  K.gate = gate;
   K.n_tensors = a->n_tensors;
   K.skip_nonfinite = a->skip_nonfinite;
   K.lr = a->lr;
@@ -447,8 +534,47 @@ int pf_adam_step(pf_ctx* ctx, const pf_adam_args* a, void* workspace, size_t wor
   K.chunks = chunks;
   const int grid = chunks < pf::kAdamMaxGrid ? chunks : pf::kAdamMaxGrid;  // (<= adam_grid_bound(total): a chunk holds an element or more)
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(pf::adam_norm_kernel, dim3(grid), dim3(pf::kAdamBlock), 0, s, K);
-  hipLaunchKernelGGL(pf::adam_update_kernel, dim3(grid), dim3(pf::kAdamBlock), 0, s, K);
+  const pf::AdamK& plain = K;
+  hipLaunchKernelGGL(pf::adam_norm_kernel, dim3(grid), dim3(pf::kAdamBlock), 0, s, plain);
+  if (gated)
+    hipLaunchKernelGGL(pf::adam_update_kernel<pf::AdamGatedK>, dim3(grid), dim3(pf::kAdamBlock), 0, s, K);
+  else
+    hipLaunchKernelGGL(pf::adam_update_kernel<pf::AdamK>, dim3(grid), dim3(pf::kAdamBlock), 0, s, plain);
+  return launched(ctx);
+}
+int pf_adam_step(pf_ctx* ctx, const pf_adam_args* a, void* workspace, size_t workspace_bytes, void* stream) {
+  return adam_call(ctx, "pf_adam_step", a, false, nullptr, workspace, workspace_bytes, stream);
+}
+int pf_adam_step_gated(pf_ctx* ctx, const pf_adam_args* a, const uint32_t* gate, void* workspace, size_t workspace_bytes, void* stream) {
+  return adam_call(ctx, "pf_adam_step_gated", a, true, gate, workspace, workspace_bytes, stream);
+}
+size_t pf_sizeof_kl_control(void) { return sizeof(pf_kl_control_args); }
+int pf_kl_control(pf_ctx* ctx, const pf_kl_control_args* a, void* stream) {
+  static const char* who = "pf_kl_control";
+  if (!ctx) return arg_fail(ctx, who, "ctx is required");
+  if (!a) return arg_fail(ctx, who, "the argument block is required");
+  const arg_ptr required[] = {{"stats", a->stats}, {"gate", a->gate}, {"state", a->state}, {nullptr, nullptr}};
+  if (int rc = require_args(ctx, who, required)) return rc;
+  if (!(a->target_kl > 0.0f && a->target_kl < INFINITY)) return arg_fail(ctx, who, "target_kl must be finite and > 0");
+  if (!(a->stop_factor >= 1.0f)) return arg_fail(ctx, who, "stop_factor must be >= 1 (+infinity: the gate never closes on a number)");
+  if (a->adapt != 0 && a->adapt != 1) return arg_fail(ctx, who, "adapt must be 0 or 1");
+  if (a->adapt) {
+    if (!a->lr_dev) return arg_fail(ctx, who, "lr_dev is required with adapt = 1");
+    if (!(a->lr_factor > 1.0f && a->lr_factor < INFINITY)) return arg_fail(ctx, who, "lr_factor must be finite and > 1");
+    if (!(a->lr_low > 0.0f && a->lr_low < a->lr_high && a->lr_high < INFINITY)) return arg_fail(ctx, who, "lr_low and lr_high must be finite with 0 < lr_low < lr_high");
+    if (!(a->lr_min > 0.0f && a->lr_min <= a->lr_max && a->lr_max < INFINITY)) return arg_fail(ctx, who, "lr_min and lr_max must be finite with 0 < lr_min <= lr_max");
+  }
+  arg_span spans[4];
+  int ns = 0;
+  spans[ns++] = {"stats", a->stats, sizeof(double) * 16};
+  spans[ns++] = {"gate", a->gate, sizeof(uint32_t)};
+  spans[ns++] = {"state", a->state, sizeof(double) * 4};
+  if (a->lr_dev) spans[ns++] = {"lr_dev", a->lr_dev, sizeof(float)};
+  char buf[128];
+  if (const char* e = spans_overlap(spans, ns, buf, sizeof(buf))) return arg_fail(ctx, who, e);
+  if (int rc = ensure_device(ctx)) return rc;
+  const pf::KlControlK K{a->stats, a->target_kl, a->stop_factor, a->adapt, a->lr_factor, a->lr_low, a->lr_high, a->lr_min, a->lr_max, a->lr_dev, a->gate, a->state};
+  hipLaunchKernelGGL(pf::kl_control_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, K);
   return launched(ctx);
 }
 int pf_world_sync(pf_ctx* ctx, const pf_world_sync_args* a, int agents_per_world, void* stream) {

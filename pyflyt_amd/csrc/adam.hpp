@@ -49,6 +49,12 @@ struct AdamK {
   const float* grad[PF_ADAM_MAX_TENSORS];
   float* exp_avg[PF_ADAM_MAX_TENSORS];
   float* exp_avg_sq[PF_ADAM_MAX_TENSORS];
+  static constexpr bool kGated = false;
+};
+// pf_adam_step_gated's: one more device word, read by the update kernel (adam_norm_kernel takes the AdamK in it as it is)
+struct AdamGatedK : AdamK {
+  const uint32_t* gate;
+  static constexpr bool kGated = true;
 };
 
 // the most workgroups a call over `total` elements can take: a chunk holds at least one element and at most kAdamChunk
@@ -125,7 +131,10 @@ __global__ void __launch_bounds__(kAdamBlock) adam_norm_kernel(const AdamK K) {
   }
 }
 
-__global__ void __launch_bounds__(kAdamBlock) adam_update_kernel(const AdamK K) {
+// KT: AdamK, or AdamGatedK (pf_adam_step_gated: a closed gate is SKIP's rule, counted in slot 5)
+template <class KT>
+__global__ void __launch_bounds__(kAdamBlock) adam_update_kernel(const KT K) {
+  constexpr bool GATED = KT::kGated;
   const int t = (int)threadIdx.x, grid = (int)gridDim.x;
   const double* __restrict__ part = K.work;
   double sum = 0.0;
@@ -141,7 +150,10 @@ __global__ void __launch_bounds__(kAdamBlock) adam_update_kernel(const AdamK K) 
   const double t_old = part[grid], skipped = part[grid + 1], b1t = part[grid + 2], b2t = part[grid + 3];
   const double lr = K.lr_dev ? (double)*K.lr_dev : (double)K.lr;
   const double norm = sqrt(sum);
-  const bool skip = K.skip_nonfinite != 0 && !(norm - norm == 0.0);  // (not finite: an infinity or a NaN)
+  const bool nonfinite = K.skip_nonfinite != 0 && !(norm - norm == 0.0);  // (not finite: an infinity or a NaN)
+  bool closed = false;
+  if constexpr (GATED) closed = *K.gate == 0u;
+  const bool skip = nonfinite || closed;
   const double c = (double)K.max_grad_norm / (norm + 1e-6);
   const double coef = c < 1.0 ? c : (c != c ? c : 1.0);              // min(1, c), a NaN passed on as torch's clamp does
   if (blockIdx.x == 0 && t == 0) {
@@ -150,8 +162,14 @@ __global__ void __launch_bounds__(kAdamBlock) adam_update_kernel(const AdamK K) 
     st[1] = norm;
     st[2] = skip ? 0.0 : coef;
     st[3] = lr;
-    st[4] = skip ? skipped + 1.0 : skipped;
-    st[5] = st[6] = st[7] = 0.0;
+    st[4] = nonfinite ? skipped + 1.0 : skipped;
+    if constexpr (GATED) {
+      const double gated = st[5];  // (this thread is the only one of the call that touches `state` after the norm kernel)
+      st[5] = closed ? gated + 1.0 : gated;
+      st[6] = st[7] = 0.0;
+    } else {
+      st[5] = st[6] = st[7] = 0.0;
+    }
   }
   if (skip) return;
   const float coef32 = (float)coef;

@@ -24,6 +24,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <type_traits>
 
 #include "../../include/pyflyt_amd.h"
 #include "uav_device.hpp"
@@ -51,12 +52,26 @@ struct PpoGradSums {
   float r_lo = INFINITY, r_hi = -INFINITY;
 };
 
-template <int HEAD>
-struct PpoGradK : MlpK {
+// the options' sums (pf_ppo_grad_opt): the critic: o[0] the sum of the chosen squared value error, n_out the rows outside the clip
+// range; the actor: o[0] = sum b
+struct PpoGradOptSums : PpoGradSums {
+  double o[1] = {0.0};
+  uint32_t n_out = 0;
+};
+template <bool OPT>
+struct PpoGradOpt {};  // (an empty base: a head without options has the arguments it always had)
+template <>
+struct PpoGradOpt<true> {
+  PpoOptK o;
+};
+
+// OPT: the heads of pf_ppo_grad_opt, instantiations of their own (PpoGradOptK below); PpoGradK is the head without
+template <int HEAD, bool OPT>
+struct PpoGradHead : MlpK, PpoGradOpt<OPT> {
   static constexpr int kHead = HEAD;
   static constexpr int kLdsFloats = kGradLdsFloats;
   typedef PpoGradRows Rows;
-  typedef PpoGradSums Sums;
+  typedef std::conditional_t<OPT, PpoGradOptSums, PpoGradSums> Sums;
   float clip, vf_coef;
   int32_t normalize;
   const float* log_std;
@@ -105,6 +120,7 @@ struct PpoGradK : MlpK {
         r.q = advantages[g];
       } else {
         r.p = returns[g];
+        if constexpr (OPT) r.q = this->o.values_old[g];  // (the critic's free word of the row block)
       }
       r.b = vbytes[g];
     }
@@ -119,7 +135,7 @@ struct PpoGradK : MlpK {
     }
     if (t < kActRows) {
       HS[kGradLdsRow + t] = r.p;
-      if constexpr (HEAD == kGradActor) HS[kGradLdsRow + kActRows + t] = r.q;
+      if constexpr (HEAD == kGradActor || OPT) HS[kGradLdsRow + kActRows + t] = r.q;
       HS[kGradLdsRow + 2 * kActRows + t] = __uint_as_float(r.b);
     }
   }
@@ -149,6 +165,10 @@ struct PpoGradK : MlpK {
           inv[c] = HS[kGradLdsInv + c];
         }
         ppo_actor_row<kPpoMaxA>(m, x, ls, inv, A, HS[kGradLdsRow + lane], HS[kGradLdsRow + kActRows + lane], live, normalize != 0, cf, gm, gt, surr, r, d);
+        if constexpr (OPT) {
+          const PpoOptK& o = this->o;
+          S.o[0] = S.o[0] + (double)ppo_bounds_row<kPpoMaxA>(m, A, live && o.bnd != 0, (2.0f * o.bounds_coef) * w32, o.lo, o.hi, gm);
+        }
 #pragma unroll
         for (int c = 0; c < kPpoMaxA; ++c) {
           g[c] = gm[c];
@@ -156,7 +176,11 @@ struct PpoGradK : MlpK {
         }
         ppo_actor_terms(live, surr, r, d, clip, S.s[0], S.s[1], S.n_clip, S.r_lo, S.r_hi);
       } else {
-        const float gv = ppo_critic_row(g[0], HS[kGradLdsRow + lane], vf_coef * w32, live, S.s[0], S.s[1], S.s[2], S.s[3]);
+        float gv = ppo_critic_row(g[0], HS[kGradLdsRow + lane], vf_coef * w32, live, S.s[0], S.s[1], S.s[2], S.s[3]);
+        if constexpr (OPT) {
+          const PpoOptK& o = this->o;
+          gv = ppo_vclip_row(gv, g[0], HS[kGradLdsRow + lane], HS[kGradLdsRow + kActRows + lane], o.clip_vf, live && o.vclip != 0, S.o[0], S.n_out);
+        }
         g[0] = gv;
 #pragma unroll
         for (int c = 1; c < kActMaxA; ++c) g[c] = 0.0f;
@@ -167,9 +191,10 @@ struct PpoGradK : MlpK {
   // wave 0's sums over its 64 lanes -> this head's columns of the workgroup's row of partials (lane j writes column j)
   PF_DEV void write_sums(const int t, const Sums& S) const {
     if (t >= 64) return;
-    double q[kPpoQ];
+    constexpr int QN = OPT ? kPpoStride : kPpoQ;
+    double q[QN];
 #pragma unroll
-    for (int j = 0; j < kPpoQ; ++j) q[j] = 0.0;
+    for (int j = 0; j < QN; ++j) q[j] = 0.0;
     bool mine;
     if constexpr (HEAD == kGradActor) {
       q[0] = ts_wave_sum(S.s[0]);
@@ -180,19 +205,32 @@ struct PpoGradK : MlpK {
 #pragma unroll
       for (int c = 0; c < kPpoMaxA; ++c) q[kPpoSums + 2 + c] = ts_wave_sum(S.gls[c]);
       mine = t == 0 || t == 2 || t == 3 || (t >= kPpoSums && t < kPpoQ);
+      if constexpr (OPT) {
+        q[kPpoColBnd] = ts_wave_sum(S.o[0]);
+        mine = mine || t == kPpoColBnd;
+      }
     } else {
       q[1] = ts_wave_sum(S.s[0]);
       q[4] = ts_wave_sum(S.s[1]);
       q[5] = ts_wave_sum(S.s[2]);
       q[6] = ts_wave_sum(S.s[3]);
       mine = t == 1 || t == 4 || t == 5 || t == 6;
+      if constexpr (OPT) {
+        q[kPpoColVc] = ts_wave_sum(S.o[0]);
+        q[kPpoColOut] = ts_wave_sum((double)S.n_out);
+        mine = mine || t == kPpoColVc || t == kPpoColOut;
+      }
     }
     double v = q[0];
 #pragma unroll
-    for (int j = 1; j < kPpoQ; ++j) v = t == j ? q[j] : v;
+    for (int j = 1; j < QN; ++j) v = t == j ? q[j] : v;
     if (mine) stat_part[(size_t)blockIdx.x * kPpoStride + t] = v;
   }
 };
+template <int HEAD>
+struct PpoGradK : PpoGradHead<HEAD, false> {};
+template <int HEAD>
+struct PpoGradOptK : PpoGradHead<HEAD, true> {};
 
 // the workspace, in this order: the rows of double partials, the actor's blocks of float partials, the critic's
 inline size_t ppo_grad_stat_bytes(int grid) { return sizeof(double) * (size_t)grid * kPpoStride; }

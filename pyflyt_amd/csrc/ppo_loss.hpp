@@ -78,7 +78,23 @@ struct PpoK {
   uint32_t vmask;
   float* grad_mean;
   float* grad_value;
+  static constexpr bool kOpt = false;
 };
+// what pf_ppo_loss_opt / pf_ppo_grad_opt add (include/pyflyt_amd.h: VALUE CLIPPING, BOUNDS LOSS). The kernels that take it are
+// instantiations of their own, so the ones above never see it; an option that is off in such a call is a launch-uniform select
+struct PpoOptK {
+  const float* values_old;  // [M]; with vclip = 0 any M readable floats (the host gives `returns`), loaded and never chosen
+  int32_t vclip, bnd;       // 0 / 1: value clipping, the bounds loss
+  float clip_vf, bounds_coef;
+  float lo[kPpoMaxA], hi[kPpoMaxA];  // -inf / +inf from the action width on
+};
+struct PpoOptMainK : PpoK {
+  PpoOptK o;
+  static constexpr bool kOpt = true;
+};
+// the columns of a row of partials the options fill: sum of the chosen squared value error, rows with |V - V_old| > clip_vf, sum b
+constexpr int kPpoColVc = kPpoQ, kPpoColOut = kPpoQ + 1, kPpoColBnd = kPpoQ + 2;
+static_assert(kPpoColBnd < kPpoStride, "the options' sums fit the spare columns");
 
 __global__ __launch_bounds__(kPpoBlock) void ppo_adv_kernel(const float* __restrict__ adv, const uint8_t* __restrict__ vbytes, uint32_t vmask,
                                                              size_t rows, double* __restrict__ partials) {
@@ -201,13 +217,50 @@ PF_DEV float ppo_critic_row(const float vl, const float rt, const float kv, cons
   return live ? kv * dv : 0.0f;
 }
 
+// The options' halves, run behind the two above on the same row (so a call without them is the functions above and nothing else).
+// The bounds loss: b = sum_c (hx^2 + lx^2) over the first `width` columns, returned for a live row (0 otherwise), and its gradient
+// kb (hx - lx), kb = (2 bounds_coef) w32, added to gm on every live row
+template <int W>
+PF_DEV float ppo_bounds_row(const float (&m)[W], const int width, const bool use, const float kb, const float (&lo)[kPpoMaxA],
+                            const float (&hi)[kPpoMaxA], float (&gm)[W]) {
+  float b = 0.0f;
+#pragma unroll
+  for (int c = 0; c < W; ++c) {
+    const float hx = fmaxf(m[c] - hi[c], 0.0f), lx = fmaxf(lo[c] - m[c], 0.0f);
+    const bool on = use && c < width;
+    b = on ? b + (hx * hx + lx * lx) : b;
+    gm[c] = on ? gm[c] + kb * (hx - lx) : gm[c];
+  }
+  return b;
+}
+// Value clipping: gv = ppo_critic_row's gradient of the row; returns 0 where the clipped branch is the larger one. s_c2: the sum of
+// the chosen square; n_out: the live rows with |V - V_old| > clip_vf. |dc| > |dv| is dc^2 > dv^2 decided exactly
+PF_DEV float ppo_vclip_row(const float gv, const float vl, const float rt, const float vo, const float clip_vf, const bool use, double& s_c2,
+                           uint32_t& n_out) {
+  const float e = vl - vo;
+  const bool out = fabsf(e) > clip_vf;
+  const float vc = e > 0.0f ? vo + clip_vf : vo - clip_vf;
+  const float dv = vl - rt, dc = vc - rt;
+  const bool use_c = use && out && fabsf(dc) > fabsf(dv);
+  const double D = (double)dv, C = (double)dc;
+  s_c2 = s_c2 + (use ? (use_c ? C * C : D * D) : 0.0);
+  n_out += use && out ? 1u : 0u;
+  return use_c ? 0.0f : gv;
+}
+
 // (amdgpu_waves_per_eu(4, 4) and kPpoMaxGrid go together: 1024 blocks of four waves are 16 waves per CU on 256 CUs, four per SIMD, so the
-//  whole grid is resident at once whatever the instantiation; the float4 one needs the cap for its registers, the generic ones just obey it)
-template <int W, bool VEC>
-__global__ __launch_bounds__(kPpoBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) void ppo_main_kernel(PpoK a, size_t rows, const double* __restrict__ fin, double* __restrict__ partials) {
+//  whole grid is resident at once for every instantiation without options; the float4 one needs the cap for its registers, the generic
+//  ones just obey it)
+// (with the options the float4 instantiation and the eight-wide one hold three more sums and a fourth per-row stream: at 128 registers
+//  they spill, so these two alone run at three waves per SIMD, 768 of the 1024 blocks resident and the rest behind them, and keep their
+//  scratch at 0; nothing waits on the whole grid, so residency is a matter of speed only)
+// KT: PpoK, or PpoOptMainK (pf_ppo_loss_opt: one more [M] stream, three more sums)
+template <int W, bool VEC, class KT>
+__global__ __launch_bounds__(kPpoBlock) __attribute__((amdgpu_waves_per_eu(KT::kOpt && (VEC || W == 8) ? 3 : 4, 4))) void ppo_main_kernel(KT a, size_t rows, const double* __restrict__ fin, double* __restrict__ partials) {
   static_assert(!VEC || W == 4, "the float4 path is four wide");
-  constexpr int U = VEC ? kPpoRowsVec : kPpoRowsGen;
-  __shared__ double sh[kPpoWaves][kPpoQ];
+  constexpr bool OPT = KT::kOpt;
+  constexpr int U = VEC ? kPpoRowsVec : kPpoRowsGen, QN = OPT ? kPpoStride : kPpoQ;
+  __shared__ double sh[kPpoWaves][QN];
   float ls[W], inv[W];
 #pragma unroll
   for (int c = 0; c < W; ++c) {
@@ -228,8 +281,12 @@ __global__ __launch_bounds__(kPpoBlock) __attribute__((amdgpu_waves_per_eu(4, 4)
 #pragma unroll
   for (int c = 0; c < W; ++c) gls[c] = 0.0;
   float r_lo = INFINITY, r_hi = -INFINITY;
+  double s_c2 = 0.0, s_b = 0.0;  // (the options' sums: dead code without them)
+  uint32_t n_out = 0;
+  float kb = 0.0f;
+  if constexpr (OPT) kb = (2.0f * a.o.bounds_coef) * w32;
   for (size_t r0 = (size_t)blockIdx.x * kPpoBlock + threadIdx.x; r0 < rows; r0 += (size_t)U * stride) {
-    float m[U][W], x[U][W], lpo[U], ad[U], rt[U], vl[U];
+    float m[U][W], x[U][W], lpo[U], ad[U], rt[U], vl[U], vo[OPT ? U : 1];
     uint32_t b[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {  // every load of the U rows (nothing here waits); the rows past M read row M - 1 again
@@ -252,6 +309,7 @@ __global__ __launch_bounds__(kPpoBlock) __attribute__((amdgpu_waves_per_eu(4, 4)
       rt[u] = a.returns[i];
       vl[u] = a.value[i];
       b[u] = a.vbytes[i];
+      if constexpr (OPT) vo[u] = a.o.values_old[i];
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -263,7 +321,11 @@ __global__ __launch_bounds__(kPpoBlock) __attribute__((amdgpu_waves_per_eu(4, 4)
 #pragma unroll
       for (int c = 0; c < W; ++c) gls[c] = gls[c] + (double)gt[c];
       ppo_actor_terms(live, surr, r, d, a.clip, sum[0], sum[2], n_clip, r_lo, r_hi);
-      const float gv = ppo_critic_row(vl[u], rt[u], kv, live, sum[1], sum[4], sum[5], sum[6]);
+      float gv = ppo_critic_row(vl[u], rt[u], kv, live, sum[1], sum[4], sum[5], sum[6]);
+      if constexpr (OPT) {
+        s_b = s_b + (double)ppo_bounds_row<W>(m[u], W, live && a.o.bnd != 0, kb, a.o.lo, a.o.hi, gm);
+        gv = ppo_vclip_row(gv, vl[u], rt[u], vo[u], a.o.clip_vf, live && a.o.vclip != 0, s_c2, n_out);
+      }
       if (in) {
         if constexpr (VEC) {
           ppo_f4 o;
@@ -278,22 +340,27 @@ __global__ __launch_bounds__(kPpoBlock) __attribute__((amdgpu_waves_per_eu(4, 4)
     }
   }
   sum[3] = (double)n_clip;
-  double q[kPpoQ];
+  double q[QN];
 #pragma unroll
   for (int j = 0; j < kPpoSums; ++j) q[j] = ts_wave_sum(sum[j]);
   q[kPpoSums] = ts_wave_min((double)r_lo);
   q[kPpoSums + 1] = ts_wave_max((double)r_hi);
 #pragma unroll
   for (int c = 0; c < kPpoMaxA; ++c) q[kPpoSums + 2 + c] = c < W ? ts_wave_sum(gls[c < W ? c : 0]) : 0.0;
+  if constexpr (OPT) {
+    q[kPpoColVc] = ts_wave_sum(s_c2);
+    q[kPpoColOut] = ts_wave_sum((double)n_out);
+    q[kPpoColBnd] = ts_wave_sum(s_b);
+  }
   const int wave = (int)threadIdx.x / 64, lane = (int)threadIdx.x % 64;
-  if (lane < kPpoQ) {  // (every lane holds all of them: lane t writes the t-th)
+  if (lane < QN) {  // (every lane holds all of them: lane t writes the t-th)
     double v = q[0];
 #pragma unroll
-    for (int j = 1; j < kPpoQ; ++j) v = lane == j ? q[j] : v;
+    for (int j = 1; j < QN; ++j) v = lane == j ? q[j] : v;
     sh[wave][lane] = v;
   }
   __syncthreads();
-  if (threadIdx.x < kPpoQ) {  // the block's four waves in ascending order
+  if (threadIdx.x < QN) {  // the block's four waves in ascending order
     const int j = (int)threadIdx.x;
     double v = sh[0][j];
 #pragma unroll
@@ -304,13 +371,16 @@ __global__ __launch_bounds__(kPpoBlock) __attribute__((amdgpu_waves_per_eu(4, 4)
 
 constexpr double kPpoEntropyConst = 1.41893853320467274178;  // 1/2 (1 + log 2 pi)
 
-// One block. partials: n_blocks rows of kPpoStride; fin: ppo_adv_finish_kernel's
-__global__ __launch_bounds__(kPpoBlock) void ppo_finish_kernel(const double* __restrict__ partials, int n_blocks, const double* __restrict__ fin,
-                                                                const float* __restrict__ log_std, int width, float vf_coef, float ent_coef,
-                                                                double* __restrict__ stats, float* __restrict__ grad_log_std) {
-  __shared__ double seg[kPpoQ * kPpoSeg];
+// One block. partials: n_blocks rows of kPpoStride; fin: ppo_adv_finish_kernel's. OPT: the options' three columns are summed too, and
+// vclip / bnd say which of them are live (a column of an option that is off holds a sum nobody asked for, and is not used)
+template <bool OPT>
+PF_DEV void ppo_finish(const double* __restrict__ partials, const int n_blocks, const double* __restrict__ fin, const float* __restrict__ log_std,
+                       const int width, const float vf_coef, const float ent_coef, double* __restrict__ stats, float* __restrict__ grad_log_std,
+                       const bool vclip, const bool bnd, const float bounds_coef) {
+  constexpr int QN = OPT ? kPpoStride : kPpoQ;
+  __shared__ double seg[QN * kPpoSeg];
   const int t = (int)threadIdx.x;
-  if (t < kPpoQ * kPpoSeg) {
+  if (t < QN * kPpoSeg) {
     const int q = t / kPpoSeg, sg = t % kPpoSeg, chunk = (n_blocks + kPpoSeg - 1) / kPpoSeg;
     const int b1 = (sg + 1) * chunk < n_blocks ? (sg + 1) * chunk : n_blocks;
     double v = q == kPpoSums ? (double)INFINITY : q == kPpoSums + 1 ? -(double)INFINITY : 0.0;
@@ -336,11 +406,19 @@ __global__ __launch_bounds__(kPpoBlock) void ppo_finish_kernel(const double* __r
     double H = 0.0;
     for (int k = 0; k < width; ++k) H = H + ((double)log_std[k] + kPpoEntropyConst);
     const double policy_loss = -(w * total(0));
-    const double value_loss = 0.5 * (w * total(1));
+    double value_loss = 0.5 * (w * total(1));
+    if constexpr (OPT) value_loss = vclip ? 0.5 * (w * total(kPpoColVc)) : value_loss;
     const double mean_r = w * total(4), mean_d = w * total(6);
     const double var_r = w * total(5) - mean_r * mean_r, var_d = w * total(1) - mean_d * mean_d;
+    double loss = (policy_loss + (double)vf_coef * value_loss) - (double)ent_coef * H;
+    double clipped = 0.0, bounds_loss = 0.0;
+    if constexpr (OPT) {
+      clipped = vclip ? w * total(kPpoColOut) : 0.0;
+      bounds_loss = bnd ? w * total(kPpoColBnd) : 0.0;
+      loss = bnd ? loss + (double)bounds_coef * bounds_loss : loss;
+    }
     stats[0] = c;
-    stats[1] = (policy_loss + (double)vf_coef * value_loss) - (double)ent_coef * H;
+    stats[1] = loss;
     stats[2] = policy_loss;
     stats[3] = value_loss;
     stats[4] = H;
@@ -351,11 +429,22 @@ __global__ __launch_bounds__(kPpoBlock) void ppo_finish_kernel(const double* __r
     stats[9] = 1.0 - var_d / var_r;
     stats[10] = total(kPpoSums);
     stats[11] = total(kPpoSums + 1);
-    stats[12] = 0.0;
-    stats[13] = 0.0;
+    stats[12] = clipped;
+    stats[13] = bounds_loss;
     stats[14] = 0.0;
     stats[15] = 0.0;
   }
+}
+__global__ __launch_bounds__(kPpoBlock) void ppo_finish_kernel(const double* __restrict__ partials, int n_blocks, const double* __restrict__ fin,
+                                                                const float* __restrict__ log_std, int width, float vf_coef, float ent_coef,
+                                                                double* __restrict__ stats, float* __restrict__ grad_log_std) {
+  ppo_finish<false>(partials, n_blocks, fin, log_std, width, vf_coef, ent_coef, stats, grad_log_std, false, false, 0.0f);
+}
+__global__ __launch_bounds__(kPpoBlock) void ppo_finish_opt_kernel(const double* __restrict__ partials, int n_blocks, const double* __restrict__ fin,
+                                                                    const float* __restrict__ log_std, int width, float vf_coef, float ent_coef,
+                                                                    double* __restrict__ stats, float* __restrict__ grad_log_std, int vclip, int bnd,
+                                                                    float bounds_coef) {
+  ppo_finish<true>(partials, n_blocks, fin, log_std, width, vf_coef, ent_coef, stats, grad_log_std, vclip != 0, bnd != 0, bounds_coef);
 }
 
 }  // namespace pf

@@ -10,6 +10,7 @@ import torch
 from . import _lib as L
 
 STATE_SLOTS = ("step", "grad_norm", "clip_coef", "lr", "skipped")
+KL_LR_KEYS = ("factor", "low", "high", "min", "max")
 
 
 def _f32(x):
@@ -27,9 +28,17 @@ class Adam:
 
     The hyperparameters reach the kernel as float32 and are held here as those values: `betas` reads (0.8999999762, 0.9990000129)
     after betas=(0.9, 0.999). There is ONE step counter for all parameters (state[0]): a parameter that sat out steps because its
-    .grad was None is bias-corrected with the common counter, where torch counts per parameter."""
+    .grad was None is bias-corrected with the common counter, where torch counts per parameter.
 
-    def __init__(self, env_or_engine, params, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None, skip_nonfinite=False):
+    target_kl (None: off, and nothing below applies) puts the KL decisions of a PPO recipe on the device: step(stats=...) is then
+    pf_kl_control followed by pf_adam_step_gated, and the step is taken only where stats' approx_kl <= kl_stop * target_kl (kl_stop
+    >= 1; inf: never stop). Once a step has pushed the KL over that limit the later epochs on the same batch measure the same KL and
+    are skipped too: early stopping without a host read. kl_lr = dict(factor=, low=, high=, min=, max=) adapts the learning rate
+    in the same launch (lr / factor where kl > high * target_kl, lr * factor where kl < low * target_kl, within [min, max]); it needs
+    `lr` to be a device tensor. kl_dict() reads what was decided."""
+
+    def __init__(self, env_or_engine, params, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None, skip_nonfinite=False,
+                 target_kl=None, kl_stop=1.5, kl_lr=None):
         engine = getattr(env_or_engine, "engine", env_or_engine)
         if not hasattr(engine, "adam_step"):
             raise ValueError(f"the first argument must be a vector env or a BatchEngine, got {type(env_or_engine).__name__}")
@@ -57,6 +66,29 @@ class Adam:
         self.skip_nonfinite = bool(skip_nonfinite)
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
+        self.target_kl, self.kl_stop, self.kl_lr = None, float("inf"), None
+        if target_kl is None:
+            if kl_lr is not None:
+                raise ValueError("kl_lr comes with target_kl (the KL its thresholds are multiples of)")
+            return
+        num = (int, float)
+        if isinstance(target_kl, bool) or not isinstance(target_kl, num) or not 0.0 < float(target_kl) < float("inf"):
+            raise ValueError(f"target_kl must be None or a finite Python number > 0, got {target_kl!r}")
+        if isinstance(kl_stop, bool) or not isinstance(kl_stop, num) or not float(kl_stop) >= 1.0:
+            raise ValueError(f"kl_stop must be a Python number >= 1 (inf: never stop), got {kl_stop!r}")
+        if kl_lr is not None:
+            if not isinstance(kl_lr, dict) or sorted(kl_lr) != sorted(KL_LR_KEYS):
+                raise ValueError(f"kl_lr must be a dict with the keys {KL_LR_KEYS}, got {kl_lr!r}")
+            if any(isinstance(v, bool) or not isinstance(v, num) or not 0.0 < float(v) < float("inf") for v in kl_lr.values()):
+                raise ValueError(f"kl_lr: every value must be a finite Python number > 0, got {kl_lr!r}")
+            if not (kl_lr["factor"] > 1.0 and kl_lr["low"] < kl_lr["high"] and kl_lr["min"] <= kl_lr["max"]):
+                raise ValueError(f"kl_lr needs factor > 1, low < high and min <= max, got {kl_lr!r}")
+            if not torch.is_tensor(self._lr):
+                raise ValueError("kl_lr changes the learning rate on the device: lr must be a one-element float32 device tensor")
+            self.kl_lr = {k: _f32(kl_lr[k]) for k in KL_LR_KEYS}
+        self.target_kl, self.kl_stop = _f32(target_kl), _f32(kl_stop)
+        self.gate = torch.ones(1, dtype=torch.int32, device=engine.device)
+        self.kl_state = torch.zeros(4, dtype=torch.float64, device=engine.device)
 
     # ------------------------------------------------------------------ hyperparameters, as the float32 values the kernel applies
     @property
@@ -109,10 +141,18 @@ class Adam:
         self._weight_decay = _f32(value)
 
     # ------------------------------------------------------------------ the step
-    def step(self, grads=None):
+    def step(self, grads=None, stats=None, adapt_lr=True):
         """One step. Without `grads`, every parameter's .grad; parameters whose .grad is None take no part, neither in the norm nor in
         the update (none at all: nothing happens). With `grads`, a list of one gradient tensor per parameter, e.g.
-        engine.mlp_backward's own tensors. Returns nothing and synchronises nothing."""
+        engine.mlp_backward's own tensors. With target_kl, `stats` (the [16] block of the ppo_loss / ppo_grad call that made the
+        gradients) is required: its approx_kl decides on the device whether the step is taken, and with kl_lr and adapt_lr the new
+        learning rate (adapt_lr=False: not in this call -- a recipe adapts once per batch, on its last epoch). Returns nothing and
+        synchronises nothing."""
+        if self.target_kl is None:
+            if stats is not None:
+                raise ValueError("stats is read only with target_kl (this optimiser has none)")
+        elif stats is None:
+            raise ValueError("stats (the [16] block of ppo_loss / ppo_grad) is required with target_kl")
         if grads is None:
             live = [i for i, p in enumerate(self.params) if p.grad is not None]
             if not live:
@@ -127,8 +167,14 @@ class Adam:
             if len(grads) != len(self.params):
                 raise ValueError(f"grads must hold one tensor per parameter ({len(self.params)}), got {len(grads)}")
             params, m, v = self.params, self.exp_avg, self.exp_avg_sq
+        gate = None
+        if self.target_kl is not None:
+            adapt = bool(adapt_lr) and self.kl_lr is not None
+            lr_args = dict(factor=self.kl_lr["factor"], low=self.kl_lr["low"], high=self.kl_lr["high"], lr_min=self.kl_lr["min"], lr_max=self.kl_lr["max"]) if adapt else {}
+            gate = self.gate
+            self.engine.kl_control(stats, gate, self.kl_state, self.target_kl, self.kl_stop, lr=self._lr if torch.is_tensor(self._lr) else None, adapt=adapt, **lr_args)
         self.engine.adam_step(params, grads, m, v, self.state, lr=self._lr, betas=self._betas, eps=self._eps, weight_decay=self._weight_decay,
-                              max_grad_norm=self.max_grad_norm, skip_nonfinite=self.skip_nonfinite)
+                              max_grad_norm=self.max_grad_norm, skip_nonfinite=self.skip_nonfinite, gate=gate)
 
     def zero_grad(self, set_to_none: bool = True):
         for p in self.params:
@@ -145,6 +191,14 @@ class Adam:
         """{step, grad_norm (before clipping), clip_coef, lr, skipped} of the last step, as Python numbers: the one host synchronisation."""
         s = self.state.tolist()
         return dict(zip(STATE_SLOTS, [int(s[0]), s[1], s[2], s[3], int(s[4])]))
+
+    def kl_dict(self):
+        """{approx_kl, lr, gate, gated_calls (gates the control closed), gated_steps (steps the optimiser skipped for a closed gate)}
+        of the last step with target_kl, as Python numbers. Synchronises."""
+        if self.target_kl is None:
+            raise ValueError("kl_dict() needs an optimiser made with target_kl")
+        k, gated = self.kl_state.tolist(), float(self.state[5])
+        return dict(approx_kl=k[0], lr=k[1], gate=int(k[2]), gated_calls=int(k[3]), gated_steps=int(gated))
 
     # ------------------------------------------------------------------ checkpoints in torch.optim.Adam's layout
     def _torch_group(self):
@@ -163,7 +217,10 @@ class Adam:
         if step > 0:
             for i in range(len(self.params)):
                 state[i] = dict(step=torch.tensor(step, dtype=torch.float32), exp_avg=self.exp_avg[i].clone(), exp_avg_sq=self.exp_avg_sq[i].clone())
-        return dict(state=state, param_groups=[self._torch_group()])
+        sd = dict(state=state, param_groups=[self._torch_group()])
+        if self.target_kl is not None:  # (a key torch's optimisers ignore)
+            sd["kl_control"] = dict(state=self.kl_state.tolist(), gate=int(self.gate), gated_steps=float(self.state[5]))
+        return sd
 
     def load_state_dict(self, sd):
         """Takes this class's state_dict() or torch.optim.Adam's / AdamW's over the same parameters in the same order."""
@@ -201,3 +258,8 @@ class Adam:
                 self.exp_avg_sq[i].zero_()
         self.state.zero_()
         self.state[0] = steps.pop() if steps else 0.0
+        kl = sd.get("kl_control")
+        if self.target_kl is not None:
+            self.kl_state.copy_(torch.tensor(kl["state"] if kl else [0.0] * 4, dtype=torch.float64))
+            self.gate.fill_(kl["gate"] if kl else 1)
+            self.state[5] = kl["gated_steps"] if kl else 0.0

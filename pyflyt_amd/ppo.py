@@ -7,6 +7,7 @@ from torch.autograd.function import once_differentiable
 
 STAT_NAMES = ("valid_rows", "loss", "policy_loss", "value_loss", "entropy", "approx_kl", "clip_fraction", "advantage_mean", "advantage_std",
               "explained_variance", "ratio_min", "ratio_max")
+OPTION_STAT_NAMES = ("value_clip_fraction", "bounds_loss")  # slots 12 and 13, written by the calls with options
 
 
 class _PpoLoss(torch.autograd.Function):
@@ -34,6 +35,22 @@ class _PpoLoss(torch.autograd.Function):
                 gv.view(ctx.shapes[1]) * grad_loss if need[2] else None, None, None, None, None, None, None, None)
 
 
+def _options(batch, clip_vf, action_bounds, bounds_coef, values_old):
+    """The options of ppo_loss and ppo_grad as the engine's keywords; none at all with the defaults, so that such a call is the one
+    it always was. values_old: the batch dict's values, or the explicit tensor."""
+    if clip_vf is None and action_bounds is None and values_old is None and isinstance(bounds_coef, (int, float)) and bounds_coef == 0:
+        return {}
+    if len(batch) == 1 and isinstance(batch[0], dict):
+        if values_old is not None:
+            raise ValueError("values_old comes from the batch dict (its values); give it only with explicit tensors")
+        if clip_vf is not None:
+            values_old = batch[0].get("values")
+            if values_old is None:
+                raise ValueError("the batch lacks ['values'], which clip_vf clips the new values around")
+            values_old = values_old.reshape(-1)
+    return dict(clip_vf=clip_vf, action_bounds=action_bounds, bounds_coef=bounds_coef, values_old=values_old)
+
+
 def _batch_tensors(batch, valid):
     """(actions, logp_old, advantages, returns, valid, from_dict) of ppo_loss's and ppo_grad's `*batch`: the dict env.collect
     returned, or the four tensors."""
@@ -51,7 +68,7 @@ def _batch_tensors(batch, valid):
 
 
 def ppo_loss(env_or_engine, mean, log_std, value, *batch, valid=None, clip: float = 0.2, vf_coef: float = 0.5, ent_coef: float = 0.0,
-             normalize_advantage: bool = True):
+             normalize_advantage: bool = True, clip_vf=None, action_bounds=None, bounds_coef: float = 0.0, values_old=None):
     """loss, stats = ppo_loss(env, actor(obs), log_std, critic(obs), batch) with `batch` the dict env.collect returned (its actions,
     logp, advantages, returns and valid, flattened and used whole), or ppo_loss(env, mean, log_std, value, actions, logp_old,
     advantages, returns, valid=...) with explicit tensors such as a gathered minibatch. `loss` is a float32 scalar on the device
@@ -60,19 +77,26 @@ def ppo_loss(env_or_engine, mean, log_std, value, *batch, valid=None, clip: floa
     the host. A deliberate trade: the gradients wait in buffers the engine owns and are NOT copied for backward (a copy would move
     another 40 bytes per row next to a pass of 74), so backward() must come before the next ppo_loss on the same env or engine; a
     later one raises RuntimeError, whatever that next call's shape was, and never uses overwritten gradients. Two losses from one
-    engine that are both to be backpropagated need .backward() after each, or an engine each."""
+    engine that are both to be backpropagated need .backward() after each, or an engine each.
+
+    The options (pf_ppo_loss_opt): clip_vf clips the value loss around the batch's values (the dict's, or values_old= with explicit
+    tensors); action_bounds=(low, high) with bounds_coef > 0 penalises means outside the box, e.g. env.action_space.low / .high.
+    Their gradients come out of the same backward(); ppo_stats_dict(stats, options=True) names their two statistics."""
     engine = getattr(env_or_engine, "engine", env_or_engine)
     if not hasattr(engine, "ppo_loss"):
         raise ValueError(f"the first argument must be a vector env or a BatchEngine, got {type(env_or_engine).__name__}")
     actions, logp_old, advantages, returns, valid, from_dict = _batch_tensors(batch, valid)
     if from_dict:
         mean, value = mean.reshape(actions.shape), value.reshape(advantages.shape)  # ([k n, A] and [k n, 1] from the networks)
-    coefficients = dict(clip=clip, vf_coef=vf_coef, ent_coef=ent_coef, normalize_advantage=normalize_advantage)
+    coefficients = dict(clip=clip, vf_coef=vf_coef, ent_coef=ent_coef, normalize_advantage=normalize_advantage,
+                        **_options(batch, clip_vf, action_bounds, bounds_coef, values_old))
+    if from_dict and coefficients.get("values_old") is not None:
+        coefficients["values_old"] = coefficients["values_old"].reshape(advantages.shape)
     return _PpoLoss.apply(mean, log_std, value, engine, actions, logp_old, advantages, returns, valid, coefficients)
 
 
 def ppo_grad(env_or_engine, x, actor, critic, log_std, *batch, valid=None, clip: float = 0.2, vf_coef: float = 0.5, ent_coef: float = 0.0,
-             normalize_advantage: bool = True, activation=None):
+             normalize_advantage: bool = True, activation=None, clip_vf=None, action_bounds=None, bounds_coef: float = 0.0, values_old=None):
     """stats = ppo_grad(env, x, actor, critic, log_std, batch): one epoch's gradients in one call (pf_ppo_grad). What
     `ppo_loss(env, mlp(env, x, actor), log_std, mlp(env, x, critic), batch)[0].backward()` leaves in .grad, the network gradients bit
     for bit, without the mean, value and their gradient tensors and without the two forward passes: the tile kernel of the backward
@@ -84,7 +108,8 @@ def ppo_grad(env_or_engine, x, actor, critic, log_std, *batch, valid=None, clip:
     The gradients are ADDED into .grad of every parameter of the two networks and of log_std (assigned, as copies of the engine's
     tensors, where .grad is None), as loss.backward() does; parameters with requires_grad False are left alone. There is no autograd
     graph and no loss tensor: `stats` is the [16] float64 device tensor of pf_ppo_loss (a copy; ppo_stats_dict names it, slot 1 is
-    the loss). x gets no gradient and an x with requires_grad raises ValueError. Nothing synchronises with the host."""
+    the loss). x gets no gradient and an x with requires_grad raises ValueError. Nothing synchronises with the host.
+    clip_vf, action_bounds, bounds_coef and values_old are ppo_loss's options (pf_ppo_grad_opt)."""
     from .nets import parse_net
 
     engine = getattr(env_or_engine, "engine", env_or_engine)
@@ -100,6 +125,7 @@ def ppo_grad(env_or_engine, x, actor, critic, log_std, *batch, valid=None, clip:
     if not torch.is_tensor(log_std):
         raise ValueError(f"log_std must be a float32 tensor of shape (A,), got {type(log_std).__name__}")
     actions, logp_old, advantages, returns, valid, from_dict = _batch_tensors(batch, valid)
+    options = _options(batch, clip_vf, action_bounds, bounds_coef, values_old)
     if from_dict:  # ([k, n, ...] from collect: the rows of x in the same order)
         A = actions.shape[-1]
         actions, logp_old, advantages, returns = actions.reshape(-1, A), logp_old.reshape(-1), advantages.reshape(-1), returns.reshape(-1)
@@ -108,7 +134,7 @@ def ppo_grad(env_or_engine, x, actor, critic, log_std, *batch, valid=None, clip:
     detached = [[(w.detach(), b.detach()) for w, b in layers] for layers in (a_layers, c_layers)]
     ga, gc, gls, stats = engine.ppo_grad(x, detached[0], detached[1], log_std.detach(), actions, logp_old, advantages, returns, valid=valid, clip=clip,
                                          vf_coef=vf_coef, ent_coef=ent_coef, normalize_advantage=normalize_advantage, actor_activation=a_act,
-                                         critic_activation=c_act)
+                                         critic_activation=c_act, **options)
     pairs = [(p, g) for layers, grads in ((a_layers, ga), (c_layers, gc)) for lp, lg in zip(layers, grads) for p, g in zip(lp, lg)] + [(log_std, gls)]
     for p, g in pairs:  # (the engine owns its tensors and overwrites them at the next call: .grad gets copies, a few KB)
         if not p.requires_grad:
@@ -120,9 +146,10 @@ def ppo_grad(env_or_engine, x, actor, critic, log_std, *batch, valid=None, clip:
     return stats.clone()
 
 
-def ppo_stats_dict(stats):
-    """The [16] stats tensor of ppo_loss as Python numbers by name (THE place that synchronises with the device)."""
+def ppo_stats_dict(stats, options: bool = False):
+    """The [16] stats tensor of ppo_loss as Python numbers by name (THE place that synchronises with the device); options=True adds
+    value_clip_fraction and bounds_loss, the two slots the calls with options write."""
     values = stats.tolist()
-    out = dict(zip(STAT_NAMES, values))
+    out = dict(zip(STAT_NAMES + OPTION_STAT_NAMES if options else STAT_NAMES, values))
     out["valid_rows"] = int(out["valid_rows"])
     return out

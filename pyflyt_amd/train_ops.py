@@ -282,14 +282,54 @@ class TrainOps:
         K.non_negative(vf_coef, "vf_coef")
         K.non_negative(ent_coef, "ent_coef")
 
+    def _ppo_options(self, A, rows, clip_vf, values_old, action_bounds, bounds_coef):
+        """What ppo_loss and ppo_grad ask of the options, before anything is launched: the filled pf_ppo_options block, or None where
+        both options are off (the call is then the one without options). `rows`: the shapes admitted for values_old."""
+        if clip_vf is None:
+            if values_old is not None:
+                raise ValueError("values_old comes with clip_vf (the range the new values are clipped to around it)")
+        else:
+            K.number(clip_vf, "clip_vf")
+            K.positive(clip_vf, "clip_vf")
+            K.tensor(self.device, values_old, "values_old", rows, required="{name} is required with clip_vf: a tensor of shape {shape}")
+        K.number(bounds_coef, "bounds_coef")
+        K.non_negative(bounds_coef, "bounds_coef")
+        lo = hi = None
+        if action_bounds is not None:
+            try:
+                lo, hi = ([float(v) for v in side] for side in action_bounds)
+            except (TypeError, ValueError):
+                raise ValueError(f"action_bounds must be a pair (low, high) of sequences of {A} numbers, got {action_bounds!r}") from None
+            if len(lo) != A or len(hi) != A:
+                raise ValueError(f"action_bounds must be a pair (low, high) of sequences of {A} numbers (the action width), got {len(lo)} and {len(hi)}")
+            if any(l != l or h != h for l, h in zip(lo, hi)):
+                raise ValueError("action_bounds must not hold a NaN (-inf / +inf: open on that side)")
+            if any(l > h for l, h in zip(lo, hi)):
+                raise ValueError(f"action_bounds: low must be <= high in every column, got {lo} and {hi}")
+        elif float(bounds_coef) > 0.0:
+            raise ValueError("action_bounds is required with bounds_coef > 0 (the box the means are kept in)")
+        bounded = float(bounds_coef) > 0.0
+        if clip_vf is None and not bounded:
+            return None
+        o = L.PfPpoOptions()
+        o.clip_vf, o.values_old = (0.0 if clip_vf is None else float(clip_vf)), _ptr(values_old)
+        o.bounds_coef = float(bounds_coef)
+        for c in range(8):
+            o.bounds_lo[c], o.bounds_hi[c] = (lo[c], hi[c]) if bounded and c < A else (float("-inf"), float("inf"))
+        return o
+
     def ppo_loss(self, mean, log_std, value, actions, logp_old, advantages, returns, valid=None, clip: float = 0.2, vf_coef: float = 0.5,
-                 ent_coef: float = 0.0, normalize_advantage: bool = True):
+                 ent_coef: float = 0.0, normalize_advantage: bool = True, clip_vf=None, action_bounds=None, bounds_coef: float = 0.0, values_old=None):
         """pf_ppo_loss: the clipped PPO objective of a diagonal-Gaussian policy, its statistics and its gradients with respect to
         mean, value and log_std (include/pyflyt_amd.h has the semantics). mean, actions [..., A] of one shape, A in 1..8; value,
         logp_old, advantages, returns [...] (a trailing axis of 1 is accepted: a critic's output); valid [...] bool / uint8 or None
         (every row valid); all flattened to M = the product of the leading axes, which need not be k n: a gathered minibatch is a
         valid input. Returns (grad_mean [M, A], grad_value [M], grad_log_std [A], stats [16] float64): tensors the engine owns,
-        overwritten by the next call with the same M and A (stats and grad_log_std by every call)."""
+        overwritten by the next call with the same M and A (stats and grad_log_std by every call).
+        The options (pf_ppo_loss_opt; with the defaults the call is pf_ppo_loss): clip_vf = the range the value loss clips the new
+        values to around values_old [...] (the batch's values; required with it); action_bounds = (low, high), two sequences of A
+        numbers (an env's action_space.low / .high; -inf / +inf = open), and bounds_coef > 0: the penalty on means outside that box.
+        stats[12] is then the fraction of rows outside the value clip range and stats[13] the bounds loss."""
         K.ranked(mean, "mean", "{name} must be a float32 tensor of shape (..., A)")
         A = int(mean.shape[-1])
         if not 1 <= A <= 8:
@@ -304,6 +344,7 @@ class TrainOps:
             if name != "valid" or x is not None:
                 K.tensor(self.device, x, name, shapes, dtypes, required="{name} is required: a tensor of shape {shape}")
         self._ppo_coefficients(clip, vf_coef, ent_coef, normalize_advantage)
+        options = self._ppo_options(A, rows, clip_vf, values_old, action_bounds, bounds_coef)
         o = self._lazy("_ppo_out", lambda: dict(M=0, A=0, stats=torch.zeros(16, dtype=torch.float64, device=self.device), calls=0))
         if o["M"] != M or o["A"] != A:
             kw = dict(dtype=torch.float32, device=self.device)
@@ -314,7 +355,10 @@ class TrainOps:
         a.mean, a.log_std, a.actions, a.logp_old = _ptr(mean), _ptr(log_std), _ptr(actions), _ptr(logp_old)
         a.advantages, a.returns, a.value, a.valid = _ptr(advantages), _ptr(returns), _ptr(value), _ptr(valid)
         a.grad_mean, a.grad_value, a.grad_log_std, a.stats = _ptr(o["grad_mean"]), _ptr(o["grad_value"]), _ptr(o["grad_log_std"]), _ptr(o["stats"])
-        self._launch(self.lib.pf_ppo_loss, C.byref(a), M, A)
+        if options is None:
+            self._launch(self.lib.pf_ppo_loss, C.byref(a), M, A)
+        else:
+            self._launch(self.lib.pf_ppo_loss_opt, C.byref(a), C.byref(options), M, A)
         return o["grad_mean"], o["grad_value"], o["grad_log_std"], o["stats"]
 
     # ------------------------------------------------------------------ the networks
@@ -398,13 +442,16 @@ class TrainOps:
         return o["grads"]
 
     def ppo_grad(self, x, actor, critic, log_std, actions, logp_old, advantages, returns, valid=None, clip: float = 0.2, vf_coef: float = 0.5,
-                 ent_coef: float = 0.0, normalize_advantage: bool = True, actor_activation="tanh", critic_activation="tanh"):
+                 ent_coef: float = 0.0, normalize_advantage: bool = True, actor_activation="tanh", critic_activation="tanh", clip_vf=None,
+                 action_bounds=None, bounds_coef: float = 0.0, values_old=None):
         """pf_ppo_grad: what mlp_forward(actor), mlp_forward(critic), ppo_loss, mlp_backward(actor), mlp_backward(critic) give on the
         rows of x [..., in_dim], without the mean, value, grad_mean and grad_value tensors between them (include/pyflyt_amd.h has the
         semantics). actor, critic: [(weight, bias), ...] as for mlp_forward, the critic one wide and on the same in_dim; actions
         [..., A]; logp_old, advantages, returns [...] (a trailing axis of 1 is accepted); valid [...] bool / uint8 or None. Returns
         (actor_grads, critic_grads, grad_log_std [A], stats [16] float64), the first two [(grad_weight, grad_bias), ...]: tensors the
-        engine owns, overwritten by the next call with the same rows and layer shapes (stats by every call); so is the workspace."""
+        engine owns, overwritten by the next call with the same rows and layer shapes (stats by every call); so is the workspace.
+        clip_vf with values_old [...], action_bounds with bounds_coef: ppo_loss's options (pf_ppo_grad_opt; with the defaults the call
+        is pf_ppo_grad)."""
         qa, rows, dims_a = self._mlp_block(x, actor, actor_activation)
         qc, _, dims_c = self._mlp_block(x, critic, critic_activation)
         A = dims_a[-1][0]
@@ -418,6 +465,7 @@ class TrainOps:
             if name != "valid" or t is not None:
                 K.tensor(self.device, t, name, shapes, dtypes, required="{name} is required: a tensor of shape {shape}")
         self._ppo_coefficients(clip, vf_coef, ent_coef, normalize_advantage)
+        options = self._ppo_options(A, per_row, clip_vf, values_old, action_bounds, bounds_coef)
         cache = self._lazy("_ppo_grad", lambda: dict(stats=torch.zeros(16, dtype=torch.float64, device=self.device)))
         key = (rows, tuple(dims_a), tuple(dims_c))
         o = cache.get(key)
@@ -439,18 +487,23 @@ class TrainOps:
         a.actor, a.critic = C.addressof(qa), C.addressof(qc)
         a.x, a.log_std, a.actions, a.logp_old = _ptr(x), _ptr(log_std), _ptr(actions), _ptr(logp_old)
         a.advantages, a.returns, a.valid = _ptr(advantages), _ptr(returns), _ptr(valid)
-        self._launch(self.lib.pf_ppo_grad, C.byref(a), rows, _ptr(o["workspace"]), o["bytes"])
+        if options is None:
+            self._launch(self.lib.pf_ppo_grad, C.byref(a), rows, _ptr(o["workspace"]), o["bytes"])
+        else:
+            self._launch(self.lib.pf_ppo_grad_opt, C.byref(a), C.byref(options), rows, _ptr(o["workspace"]), o["bytes"])
         return o["grads"][0], o["grads"][1], o["grad_log_std"], cache["stats"]
 
     # ------------------------------------------------------------------ the optimiser
     def adam_step(self, params, grads, exp_avg, exp_avg_sq, state, *, lr=3e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
-                  max_grad_norm=None, skip_nonfinite: bool = False):
+                  max_grad_norm=None, skip_nonfinite: bool = False, gate=None):
         """pf_adam_step: one Adam / AdamW step with global gradient-norm clipping over the tensors `params` (1..32 of them), in
         place, in two launches (include/pyflyt_amd.h has the semantics). grads, exp_avg and exp_avg_sq are lists of tensors shaped
         like the parameters; state is the [8] float64 block (steps, norm, clip coefficient, learning rate, skipped calls), read
         and overwritten. lr is a Python number or a one-element float32 device tensor, read by the kernel at every call.
         max_grad_norm None = no clipping. The hyperparameters reach the kernel as float32. The workspace (one per total size) and
-        the filled argument block (one per set of addresses) are the engine's. Returns `state`; nothing synchronises."""
+        the filled argument block (one per set of addresses) are the engine's. gate: a one-element int32 / uint32 device tensor
+        (kl_control's): the call is then pf_adam_step_gated, and a zero there skips the step on the device (state[5] counts those).
+        Returns `state`; nothing synchronises."""
         lists = dict(params=params, grads=grads, exp_avg=exp_avg, exp_avg_sq=exp_avg_sq)
         for name, ts in lists.items():
             if not isinstance(ts, (list, tuple)):
@@ -517,9 +570,51 @@ class TrainOps:
         if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
             raise ValueError(f"max_grad_norm must be > 0 or None (no clipping), got {max_grad_norm}")
         K.boolean(skip_nonfinite, "skip_nonfinite")
+        K.tensor(self.device, gate, "gate", (1,), K.GATE)
         a = o["args"]
         a.lr, a.beta1, a.beta2, a.eps, a.weight_decay = (0.0 if lr_dev is not None else float(lr)), b1, b2, float(eps), float(weight_decay)
         a.max_grad_norm, a.skip_nonfinite = (float("inf") if max_grad_norm is None else float(max_grad_norm)), int(skip_nonfinite)
         with torch.cuda.device(self.device):  # (its own launch code: the raw stream handle, for the host cost of a step)
-            L.check(self.lib.pf_adam_step(self._ctx, o["ref"], o["workspace"], o["bytes"], C.c_void_p(_raw_stream(self._index))), self._ctx)
+            if gate is None:
+                L.check(self.lib.pf_adam_step(self._ctx, o["ref"], o["workspace"], o["bytes"], C.c_void_p(_raw_stream(self._index))), self._ctx)
+            else:
+                L.check(self.lib.pf_adam_step_gated(self._ctx, o["ref"], _ptr(gate), o["workspace"], o["bytes"], C.c_void_p(_raw_stream(self._index))), self._ctx)
+        return state
+
+    def kl_control(self, stats, gate, state, target_kl, stop_factor: float = 1.5, lr=None, adapt: bool = False, factor: float = 1.5, low: float = 0.5,
+                   high: float = 2.0, lr_min: float = 1e-6, lr_max: float = 1e-2):
+        """pf_kl_control: the decisions a PPO recipe takes from the measured KL, in one launch of one thread (include/pyflyt_amd.h has
+        the semantics). stats: a [16] float64 block of ppo_loss / ppo_grad (slot 5 is read); gate: [1] int32 / uint32, written 1 where
+        kl <= stop_factor * target_kl (what adam_step(gate=) reads); state: [4] float64 (kl, lr, gate, closed gates so far). With
+        adapt, lr (a one-element float32 device tensor) is divided by `factor` where kl > high * target_kl and multiplied where
+        kl < low * target_kl, within [lr_min, lr_max]. Returns `state`; nothing synchronises."""
+        need = "{name} is required: a tensor of shape {shape}"
+        K.tensor(self.device, stats, "stats", (16,), torch.float64, required=need)
+        K.tensor(self.device, gate, "gate", (1,), K.GATE, required=need)
+        K.tensor(self.device, state, "state", (4,), torch.float64, required=need)
+        K.number(target_kl, "target_kl")
+        K.positive(target_kl, "target_kl")
+        K.number(stop_factor, "stop_factor")
+        if not float(stop_factor) >= 1.0:
+            raise ValueError(f"stop_factor must be >= 1 (inf: the gate never closes on a number), got {stop_factor}")
+        K.boolean(adapt, "adapt")
+        if lr is not None:
+            K.tensor(self.device, lr, "lr", tuple(lr.shape) if torch.is_tensor(lr) and lr.numel() == 1 else (1,), required="{name} must be a one-element float32 device tensor")
+        if adapt:
+            if lr is None:
+                raise ValueError("lr (a one-element float32 device tensor) is required with adapt")
+            for name, x in (("factor", factor), ("low", low), ("high", high), ("lr_min", lr_min), ("lr_max", lr_max)):
+                K.number(x, name)
+                K.positive(x, name)
+            if not float(factor) > 1.0:
+                raise ValueError(f"factor must be > 1, got {factor}")
+            if not float(low) < float(high):
+                raise ValueError(f"low must be < high, got {low} and {high}")
+            if not float(lr_min) <= float(lr_max):
+                raise ValueError(f"lr_min must be <= lr_max, got {lr_min} and {lr_max}")
+        a = L.PfKlControl()
+        a.stats, a.gate, a.state, a.lr_dev = _ptr(stats), _ptr(gate), _ptr(state), _ptr(lr)
+        a.target_kl, a.stop_factor, a.adapt = float(target_kl), float(stop_factor), int(adapt)
+        a.lr_factor, a.lr_low, a.lr_high, a.lr_min, a.lr_max = float(factor), float(low), float(high), float(lr_min), float(lr_max)
+        self._launch(self.lib.pf_kl_control, C.byref(a))
         return state

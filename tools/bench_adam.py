@@ -106,6 +106,33 @@ def epoch_legs(eng, rows):
     return out
 
 
+def kl_epoch_legs(eng, rows):
+    """An epoch of examples/13 (ppo_grad and the step, on the engine's own tensors) with pf_adam_step, and with pf_kl_control +
+    pf_adam_step_gated under a target no epoch reaches (the gate stays open: the same update), each eager and replayed from a
+    captured graph: what the KL decisions cost when they are on the device (tools/bench_ppo_grad.py --options records it)."""
+    out, keep = {}, []
+    for name, kl in (("adam_step", {}), ("kl_control_and_gated_step", dict(target_kl=1e6, kl_stop=1.5))):
+        actor, critic, log_std, params = parameters()
+        o, (actions, logp, adv, ret), valid = batch(rows, actor, log_std)
+        la = [(actor[i].weight.detach(), actor[i].bias.detach()) for i in (0, 2, 4)]
+        lc = [(critic[i].weight.detach(), critic[i].bias.detach()) for i in (0, 2)]
+        opt = pyflyt_amd.Adam(eng, [p.detach() for p in params], lr=LR, max_grad_norm=MAX_NORM, **kl)
+
+        def epoch(o=o, la=la, lc=lc, ls=log_std.detach(), actions=actions, logp=logp, adv=adv, ret=ret, valid=valid, opt=opt, gated=bool(kl)):
+            ga, gc, gls, stats = eng.ppo_grad(o, la, lc, ls, actions, logp, adv, ret, valid=valid, clip=0.2, vf_coef=1.0, ent_coef=0.0, normalize_advantage=True)
+            grads = [t for pair in ga for t in pair] + [t for pair in gc for t in pair] + [gls]
+            opt.step(grads=grads, stats=stats) if gated else opt.step(grads=grads)
+        for _ in range(3):
+            epoch()
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            epoch()
+        out[name], out[name + "_graph"] = epoch, graph.replay
+        keep.append((graph, opt, params))
+    return out, keep
+
+
 def time_leg(fn, inner, min_seconds=0.3):
     """ms per call: device events around `inner` calls, repeated until min_seconds of them have been timed."""
     for _ in range(inner):

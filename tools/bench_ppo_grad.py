@@ -9,6 +9,10 @@ each eager and replayed from a captured graph (Fg, Cg); and the composed path's 
 two tile launches have to be set against). One process, device events, every leg warmed up, at least 0.3 s per sample,
 the legs alternated, the median of --repeats with min and max. Also checks that both paths give the same network gradients bit for
 bit, and records the intermediate tensors the composed path allocates. Prints one JSON line and writes profiles/ppo_grad/bench.json.
+
+--options measures what PPO's options cost instead, and writes profiles/ppo_options/bench.json: pf_ppo_grad_opt with value clipping and
+the bounds loss both on against pf_ppo_grad on the same rows (eager and replayed), and, through tools/bench_adam.py, an epoch with
+pf_kl_control + pf_adam_step_gated against the same epoch with pf_adam_step.
 """
 import argparse
 import json
@@ -65,12 +69,75 @@ def legs(eng, rows):
     return {"F": fused, "C": composed, "Fg": graphs["Fg"].replay, "Cg": graphs["Cg"].replay}, agree, intermediates, parts
 
 
+def option_legs(eng, rows):
+    """pf_ppo_grad and pf_ppo_grad_opt (clip_vf = 0.2 around values_old = the critic's values shifted by 0.3 on every third row; the
+    box [-1, 1] with bounds_coef = 1e-4) on the same rows, eager and replayed."""
+    actor, critic, log_std = networks()
+    o, (actions, logp, adv, ret), valid = batch(rows, actor, log_std)
+    la = [(actor[i].weight.detach(), actor[i].bias.detach()) for i in (0, 2, 4)]
+    lc = [(critic[i].weight.detach(), critic[i].bias.detach()) for i in (0, 2)]
+    ls = log_std.detach()
+    values_old = eng.mlp_forward(o, lc, "tanh").reshape(-1).clone()
+    values_old[::3] += 0.3
+    opts = dict(clip_vf=0.2, values_old=values_old, action_bounds=([-1.0] * A, [1.0] * A), bounds_coef=1e-4)
+    fns = {"plain": lambda: eng.ppo_grad(o, la, lc, ls, actions, logp, adv, ret, valid=valid, **COEF),
+           "options": lambda: eng.ppo_grad(o, la, lc, ls, actions, logp, adv, ret, valid=valid, **COEF, **opts)}
+    stats = fns["options"]()[3].clone()
+    graphs = {}
+    for name in ("plain", "options"):
+        fns[name]()
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            fns[name]()
+        graphs[name] = g
+    fns.update({name + "_graph": g.replay for name, g in graphs.items()})
+    return fns, graphs, {"value_clip_fraction": float(stats[12]), "bounds_loss": float(stats[13])}
+
+
+def options_main(args):
+    from bench_adam import kl_epoch_legs, measure as measure_inner
+
+    eng = BatchEngine(build_params("quadx", "none"), 64, device=DEV)
+    rows = args.epoch_rows
+    res = {"workload": f"D = {D}, actor 64-64-{A} tanh, critic 64-1 tanh", "device": torch.cuda.get_device_name(0), "rows": rows}
+    fns, graphs, seen = option_legs(eng, rows)
+    t = measure(fns, args.repeats)
+    g = {"unit": "ms per epoch of gradients", "options_on": "clip_vf 0.2, bounds_coef 1e-4 on [-1, 1]^4", **seen, **t}
+    for a, b in (("options", "plain"), ("options_graph", "plain_graph")):
+        g[f"{a}_against_{b}"] = {"difference_ms": t[a]["median"] - t[b]["median"], "ratio": t[a]["median"] / t[b]["median"],
+                                 "combined_spread_ms": (t[a]["max"] - t[a]["min"]) + (t[b]["max"] - t[b]["min"])}
+    res["ppo_grad_opt"] = g
+    del fns, graphs
+    res["kl_gate"] = {"unit": "ms per epoch (ppo_grad and the optimiser's step)"}
+    for r in (65536, rows):
+        legs, keep = kl_epoch_legs(eng, r)
+        m = measure_inner(legs, args.repeats, 4 if r > (1 << 20) else 20)
+        for a, b in (("kl_control_and_gated_step", "adam_step"), ("kl_control_and_gated_step_graph", "adam_step_graph")):
+            m[f"{a}_minus_{b}_us"] = 1e3 * (m[a]["median"] - m[b]["median"])
+        res["kl_gate"][str(r)] = m
+        del legs, keep
+        torch.cuda.empty_cache()
+    eng.close()
+    line = json.dumps(res)
+    print(line)
+    out = args.out if args.out_given else os.path.join(ROOT, "profiles", "ppo_options", "bench.json")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    open(out, "w").write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--epoch-rows", type=int, default=65536 * 64)
     ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ppo_grad", "bench.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--options", action="store_true", help="time pf_ppo_grad_opt and the KL-gated step instead (profiles/ppo_options/bench.json)")
     args = ap.parse_args()
+    args.out_given = args.out is not None
+    if args.options:
+        return options_main(args)
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "ppo_grad", "bench.json")
     eng = BatchEngine(build_params("quadx", "none"), 64, device=DEV)
     res = {"workload": f"D = {D}, actor 64-64-{A} tanh, critic 64-1 tanh", "device": torch.cuda.get_device_name(0), "rows": args.epoch_rows,
            "unit": "ms per epoch of gradients", "launches": {"F": 7, "C": 10}}

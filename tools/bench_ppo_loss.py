@@ -4,6 +4,8 @@ and their output-gradients.
   a  engine.ppo_loss(...)                      pf_ppo_loss alone: the advantage pass, the main kernel and the two finish kernels
   b  the same loss in eager torch float32 with backward() down to the gradients of mean, value and log_std: what a user writes today
   c  pyflyt_amd.ppo_loss(...) and backward()   (a) through the autograd wrapper, the grad_output multiply included
+  o  engine.ppo_loss(..., clip_vf=, action_bounds=, bounds_coef=)   pf_ppo_loss_opt with both options on (only with --legs ao: what the
+     options cost the pass; profiles/ppo_options/bench.json quotes it)
 
 M = 65 536 x 64 and 524 288 x 64 rows, A = 4, a quarter of the rows invalid. One process, device events around batches of calls (at
 least 0.3 s per sample), every leg warmed up, the legs alternated and repeated three times; median and spread. (a) and (b) are checked
@@ -71,6 +73,12 @@ def make_legs(eng, m, dev):
     def leg_b():
         return torch.autograd.grad(torch_loss(mean, log_std, value, *rest, valid), [mean, value, log_std])
 
+    values_old = value.detach() + 0.3 * (torch.arange(m, device=dev) % 3 == 0)  # (a third of the rows outside the clip range)
+    opts = dict(clip_vf=0.2, values_old=values_old, action_bounds=([-1.0] * A, [1.0] * A), bounds_coef=1e-4)
+
+    def leg_o():
+        return eng.ppo_loss(mean.detach(), log_std.detach(), value.detach(), *rest, valid=valid, **kw, **opts)
+
     def leg_c():
         loss, _ = pyflyt_amd.ppo_loss(eng, mean, log_std, value, *rest, valid=valid, **kw)
         return torch.autograd.grad(loss, [mean, value, log_std])
@@ -80,7 +88,7 @@ def make_legs(eng, m, dev):
     for o, t in zip(ours[:3], theirs):
         assert (o - t).abs().max().item() <= 1e-4 * max(t.abs().max().item(), 1e-12), ((o - t).abs().max().item(), t.abs().max().item())
     del ours, theirs
-    return {"a": leg_a, "b": leg_b, "c": leg_c}
+    return {"a": leg_a, "b": leg_b, "c": leg_c, "o": leg_o}
 
 
 def time_leg(fn, min_seconds=0.3):
@@ -128,6 +136,8 @@ def main():
             case["hbm_fraction_of_peak"] = by / (case["a"]["us"] * 1e-6) / HBM_PEAK
             if "b" in case:
                 case["torch_over_pf_ppo_loss"] = case["b"]["us"] / case["a"]["us"]
+            if "o" in case:
+                case["options_over_pf_ppo_loss"] = case["o"]["us"] / case["a"]["us"]
         res["cases"][str(n)] = case
         del legs
         torch.cuda.empty_cache()
