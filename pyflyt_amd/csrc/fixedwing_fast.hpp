@@ -276,6 +276,9 @@ struct FwHot {
   // LIFT_Y: the vertical tail (lift unit +y, torque unit -z); otherwise lift +z, torque +y.
   // `a`: this surface's actuation after the first-order lag. Accumulates into F, tau (base frame,
   // torque about the base origin).
+  // (The ticks call surface<true> only. surface<false> is the readable form surface_pair is written
+  //  after and checked against: its one user is tests/device_probes/aero_probe.hip, where
+  //  tests/test_gpu_aero.py holds the pair to it bit for bit.)
   template <bool LIFT_Y>
   PF_DEV void surface(const FwSurf S, const float a, v3& F, v3& tau) const {
     const float vx = fmaf(wb.y, S.rz, fmaf(-wb.z, S.ry, vb.x));
@@ -344,7 +347,9 @@ struct FwHot {
       tau.z = fmaf(-S.ry, fp, tau.z);
     }
   }
-  // Two lift-+z surfaces at once: surface<false> element by element (same operations on each element),
+  // Two lift-+z surfaces at once: surface<false> element by element (same operations on each element:
+  // the updated actuation is surface<false>'s to the bit, and so are fp, fn and tau.y once added to a
+  // zeroed total as surface<false> adds them, on every point of tests/test_gpu_aero.py's sweep),
   // the multiply-add chains in packed fp32. The statement ORDER is the schedule (the build runs with the
   // machine scheduler off): a packed result read by the very next VALU instruction costs a wait state
   // (s_nop) and a compare needs two instructions before the select that reads its mask (gfx940 hazards),

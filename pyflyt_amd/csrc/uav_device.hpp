@@ -172,7 +172,9 @@ PF_DEV void half_angle(float c, float s, float& ch, float& sh) {
   sh = pos ? b : __builtin_copysignf(a, s);
 }
 
-// sin/cos of a small angle (|x| <= 1: error < 2e-8) by Taylor polynomials, no range reduction
+// sin/cos of a small angle by Taylor polynomials, no range reduction. |x| <= 1: the polynomials are within
+// 2e-8 of the functions (3e-9 on [-0.8, 0.8]); the float32 result, with the roundings of its last steps,
+// within 1e-7 (under 8e-8 on [-0.8, 0.8]: tests/test_cpu_aero_ref.py)
 PF_DEV void sincos_small(float x, float& sn, float& cs) {
   const float t = x * x;
   sn = x * fmaf(t, fmaf(t, fmaf(t, fmaf(t, fmaf(t, -2.5052108e-8f, 2.7557319e-6f), -1.9841270e-4f), 8.3333333e-3f), -1.6666667e-1f), 1.0f);
