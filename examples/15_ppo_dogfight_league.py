@@ -1,6 +1,7 @@
 """Example 14's self-play loop against a small league: team 1 is flown by TWO earlier snapshots of the actor at once, and the loop prints
-the win rate against each. `env.collect(..., opponent=[older, newer], outcomes=True)` cuts the copies into two contiguous segments, flies
-segment p's team 1 with snapshot p (one pf_policy_act over all rows and one merge per snapshot), and adds pf_episode_outcomes to every
+the win rate against each. `env.collect(..., opponent=[older, newer], outcomes=True, pooled=True)` cuts the copies into two contiguous
+segments, flies segment p's team 1 with snapshot p (the actor and both snapshots in ONE pf_policy_act_pool per step, every lane evaluated
+once by the policy that flies it; without pooled=True, one pf_policy_act over all rows and one merge per snapshot, for the same bits), and adds pf_episode_outcomes to every
 step: `outcome_counts` [2, 16] holds, per snapshot, how team 0's episodes ended (collision, out of bounds, team_win, dead, or the time
 limit) and how the copies that finished in this batch went -- team 0 wins, team 1 wins, draws. `env.episode_outcomes_dict()` reads the
 block back by name: the one host synchronisation the win rate costs.
@@ -49,7 +50,7 @@ for it in range(iterations):
         overwrite(nets[0], stds[0], nets[1], stds[1])
         overwrite(nets[1], stds[1], actor, log_std)
     with torch.no_grad():
-        b = env.collect(policy, lambda o: mlp(env, o, critic), K, gamma=0.99, lam=0.95, opponent=league, outcomes=True)
+        b = env.collect(policy, lambda o: mlp(env, o, critic), K, gamma=0.99, lam=0.95, opponent=league, outcomes=True, pooled=True)
     o = b["obs"].reshape(-1, D)
     for _ in range(EPOCHS):
         loss, stats = ppo_loss(env, mlp(env, o, actor), log_std, mlp(env, o, critic), b, clip=CLIP, vf_coef=1.0, ent_coef=0.0, normalize_advantage=True)

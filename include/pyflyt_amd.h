@@ -999,6 +999,43 @@ typedef struct pf_outcome_args {
 size_t pf_sizeof_outcome(void);
 int pf_episode_outcomes(pf_ctx* ctx, const pf_outcome_args* a, int k_steps, int agents_per_world, void* stream);
 
+/* pf_policy_act for a POOL of policies in one launch: every row is evaluated once, by the policy that row_policy names for it -- a
+ * learner and a league's past snapshots on their own lanes of one dogfight batch, or G checkpoints side by side in one batch of a
+ * single-agent env. (Added without a new PF_ABI_VERSION: three new functions; pf_policy and every other struct are as they were.)
+ *   - row_policy: device, [n] int32, n = pf_n_lanes(ctx): the policy of every row, 0 .. n_policies - 1. Any other value (-1 by
+ *     convention) means "no policy": that row of actions_out and of mean_out is not written, not one byte.
+ *   - THE PLAN. pf_policy_pool_plan turns row_policy into the caller's `plan` buffer (device, opaque, plan_bytes =
+ *     pf_policy_pool_plan_bytes(n, n_policies)): per policy the list of its rows, padded to whole tiles of 64 rows, and the policy
+ *     every tile runs. ceil(n / 64) + n_policies tiles always suffice, so the size is a function of (n, n_policies) alone and
+ *     nothing reads a count back. pf_policy_pool_plan_bytes is a pure host function; it returns 0 for what the calls refuse (n < 1,
+ *     n_policies outside 1..PF_POLICY_POOL_MAX). The plan is built once per assignment of rows to policies, not once per step: one
+ *     workgroup sorts the rows, so it is not fast (about 0.2 ms at 65 536 rows and 17 policies). A policy without rows is fine. The
+ *     plan's bytes are a function of row_policy alone (a policy's rows stand in ascending order); and no bit that
+ *     pf_policy_act_pool writes depends on the order in which a plan lists a policy's rows.
+ *   - pf_policy_act_pool: `policies` is a HOST array of n_policies pf_policy blocks, passed to the kernel as arguments.
+ *     policies[0].obs0 is the call's [n][D] input and policies[0].mean_out its [n][A] mean output or NULL; those two fields of the
+ *     other entries are ignored. The entries may differ in n_layers, widths, activation and in whether log_std is NULL; D and A are
+ *     the context's (pf_policy_act: ARGUMENTS).
+ *   - THE RESULT. For every row i with p = row_policy[i] in range, actions_out[i] and mean_out[i] hold the bits that
+ *     pf_policy_act(ctx, &policies[p], ..., step_index) writes for row i on the same observation: the same bias-first ascending fmaf
+ *     chain on the float32-input matrix instruction, the same float32 tanh, the same expf(log_std), the same Philox call keyed by
+ *     (seed, global lane, step_index, 0) on stream constant 4 -- wherever the row lands in a tile.
+ *   - A STALE PLAN (one made for another row_policy, n or n_policies, or bytes that no pf_policy_pool_plan wrote) may give wrong
+ *     actions but never an access outside the caller's tensors: the kernel checks every row index and every policy index it reads
+ *     from the plan before it addresses anything with them.
+ *   - ERRORS: PF_ERR_ARG, the argument named, before any launch, for a NULL ctx / row_policy / policies / plan / actions_out /
+ *     policies[0].obs0 or a layer's w / b, n_policies outside 1..PF_POLICY_POOL_MAX, plan_bytes different from
+ *     pf_policy_pool_plan_bytes(n, n_policies), and per entry pf_policy_act's checks with "policies[p]: " in front; PF_ERR_UNSUPPORTED
+ *     for a context without an env task or a hidden width over PF_POLICY_MAX_HIDDEN.
+ *   - Both calls are enqueued on `stream`: no host synchronisation, no allocation, no copy -- capturable in a HIP graph;
+ *     pf_policy_act_pool is ONE launch. The weights are read at every call; neither call keeps anything in the context. obs0 and
+ *     the outputs must not overlap; the plan must not be rewritten while a pf_policy_act_pool that reads it is in flight. */
+#define PF_POLICY_POOL_MAX 17   /* a learner and PF_OUTCOME_MAX_GROUPS opponents */
+size_t pf_policy_pool_plan_bytes(int n_rows, int n_policies);
+int pf_policy_pool_plan(pf_ctx* ctx, const int32_t* row_policy, int n_policies, void* plan, size_t plan_bytes, void* stream);
+int pf_policy_act_pool(pf_ctx* ctx, const pf_policy* policies, int n_policies, const void* plan, size_t plan_bytes,
+                       float* actions_out, uint32_t step_index, void* stream);
+
 /* The reference's LOWER boundary for one drone: applyExternalForce / applyExternalTorque on the base link in
  * LINK_FRAME followed by stepSimulation (core/drones/quadx.py:502-510, core/aviary.py:516), n_ticks times with
  * the wrench b->wrench held: the free-body tick alone (collision detection, gyroscopic term, +-max_coord_vel

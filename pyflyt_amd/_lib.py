@@ -84,6 +84,7 @@ PfTrajStatsMasked = _STRUCTS["pf_traj_stats_masked_args"]
 PfPpoGradArgs = _STRUCTS["pf_ppo_grad_args"]
 PfPpoOptions, PfKlControl = _STRUCTS["pf_ppo_options"], _STRUCTS["pf_kl_control_args"]
 PfOutcome, PF_OUTCOME_SLOTS, PF_OUTCOME_MAX_GROUPS = _STRUCTS["pf_outcome_args"], _DEFINES["PF_OUTCOME_SLOTS"], _DEFINES["PF_OUTCOME_MAX_GROUPS"]
+PF_POLICY_POOL_MAX = _DEFINES["PF_POLICY_POOL_MAX"]
 # pf_episode_outcomes' slots by name (include/pyflyt_amd.h): 0-9 per agent, 10-13 per world
 OUTCOME_SLOT_NAMES = ("episodes", "terminated", "truncated", "collision", "out_of_bounds", "complete", "dead", "nonfinite", "second_word_sum", "clean",
                       "worlds", "team0_wins", "team1_wins", "draws")
@@ -144,6 +145,10 @@ def lib():
     L.pf_rollout_policy.argtypes = [C.c_void_p, C.POINTER(PfBuffers), C.POINTER(PfPolicy), C.c_int, C.c_uint32, C.c_void_p]
     L.pf_sizeof_policy.restype = C.c_size_t
     L.pf_policy_act.argtypes = [C.c_void_p, C.POINTER(PfPolicy), C.c_void_p, C.c_uint32, C.c_void_p]
+    L.pf_policy_pool_plan_bytes.argtypes = [C.c_int, C.c_int]
+    L.pf_policy_pool_plan_bytes.restype = C.c_size_t
+    L.pf_policy_pool_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.pf_policy_act_pool.argtypes = [C.c_void_p, C.POINTER(PfPolicy), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p]
     L.pf_gae.argtypes = [C.c_void_p, C.POINTER(PfGae), C.c_int, C.c_void_p]
     L.pf_sizeof_gae.restype = C.c_size_t
     L.pf_traj_stats.argtypes = [C.c_void_p, C.POINTER(PfTrajStats), C.c_int, C.c_void_p]

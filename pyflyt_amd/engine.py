@@ -333,6 +333,66 @@ class BatchEngine(TrainOps):
         self._launch(self.lib.pf_policy_act, C.byref(q), _ptr(out), int(step_index) & 0xFFFFFFFF)
         return out if mean_out is None else (out, mean_out)
 
+    # ------------------------------------------------------------------ a pool of policies in one launch
+    def _pool_blocks(self, policies, name="policies", most=L.PF_POLICY_POOL_MAX):
+        """The pf_policy blocks of a pool (a list of 1..`most` MLPPolicy) as one ctypes array, each filled and checked for this engine."""
+        if not isinstance(policies, (list, tuple)) or not 1 <= len(policies) <= most:
+            raise ValueError(f"{name}: a pool holds 1..{most} policies, got {len(policies) if isinstance(policies, (list, tuple)) else type(policies).__name__}")
+        arr = (L.PfPolicy * len(policies))()
+        for p, policy in enumerate(policies):
+            self._check_policy(policy)
+            policy.fill(arr[p], self)
+        return arr
+
+    def _pool_plan_bytes(self, n_policies):
+        """pf_policy_pool_plan_bytes for this engine's rows (a pure host function: asked of the library itself, no context)."""
+        if isinstance(n_policies, bool) or not isinstance(n_policies, int) or not 1 <= n_policies <= L.PF_POLICY_POOL_MAX:
+            raise ValueError(f"n_policies must be an int in 1..{L.PF_POLICY_POOL_MAX}, got {n_policies!r}")
+        return int(L.lib().pf_policy_pool_plan_bytes(self.n, n_policies))
+
+    def policy_pool_plan(self, row_policy, n_policies):
+        """pf_policy_pool_plan: the plan of a pool launch, a new uint8 tensor (opaque). row_policy [n] int32: the policy of every
+        row, 0 .. n_policies - 1; any other value (-1) = no policy, and policy_act_pool leaves that row's outputs alone. Made once
+        per assignment of rows to policies; one launch, nothing synchronises."""
+        nbytes = self._pool_plan_bytes(n_policies)
+        K.tensor(self.device, row_policy, "row_policy", (self.n,), torch.int32, required="{name} is required: an int32 tensor of shape {shape}")
+        plan = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self._launch(self.lib.pf_policy_pool_plan, _ptr(row_policy), n_policies, _ptr(plan), nbytes)
+        return plan
+
+    def policy_act_pool(self, policies, plan, step_index: int = 0, obs=None, out=None, mean_out=None):
+        """pf_policy_act_pool: policy_act for a list of 1..17 MLPPolicy in ONE launch, every row evaluated once by the policy that the
+        plan's row_policy names for it (policy_pool_plan). Arguments and return value as policy_act's. Row i of the outputs holds the
+        bits of policy_act(policies[row_policy[i]], ...); a row without a policy is not written."""
+        arr = self._pool_blocks(policies)
+        K.tensor(self.device, plan, "plan", (self._pool_plan_bytes(len(arr)),), torch.uint8,
+                 required="{name} is required: policy_pool_plan's uint8 tensor of shape {shape}")
+        obs = self._cur_obs if obs is None else K.tensor(self.device, obs, "obs", (self.n, self.obs_dim))
+        if out is None:
+            out = torch.empty(self.n, self.action_dim, dtype=torch.float32, device=self.device)
+        K.tensor(self.device, out, "out", (self.n, self.action_dim))
+        K.tensor(self.device, mean_out, "mean_out", (self.n, self.action_dim))
+        head = arr[0]  # (a view of the array's first block: its address is the array's)
+        head.obs0 = obs.data_ptr()
+        head.mean_out = _ptr(mean_out)
+        self._launch(self.lib.pf_policy_act_pool, C.byref(head), len(arr), _ptr(plan), plan.numel(), _ptr(out), int(step_index) & 0xFFFFFFFF)
+        return out if mean_out is None else (out, mean_out)
+
+    def _closed_loop_pool(self, policies, k_steps, group, n_groups):
+        """What rollout_policy_steps asks of a LIST of policies before it touches a tensor; returns ((the pf_policy blocks, row_policy), k):
+        row_policy is `group`, or None = every row flies the list's only entry."""
+        pool = list(policies)
+        if not 1 <= len(pool) <= L.PF_OUTCOME_MAX_GROUPS:
+            raise ValueError(f"policy: a pool holds 1..{L.PF_OUTCOME_MAX_GROUPS} policies, got {len(pool)}")
+        k = int(k_steps)
+        if k < 1:
+            raise ValueError(f"k_steps must be >= 1, got {k_steps}")
+        self._check_stepwise()
+        if n_groups != len(pool) or (group is None and len(pool) > 1):
+            raise ValueError(f"policy: a pool of {len(pool)} needs group (which policy flies a lane) and n_groups = {len(pool)}, got n_groups = {n_groups!r}")
+        K.tensor(self.device, group, "group", (self.n,), torch.int32)
+        return (self._pool_blocks(pool, "policy", L.PF_OUTCOME_MAX_GROUPS), group), k
+
     def rollout_policy_steps(self, policy, k_steps: int, step_index0: int = 0, store_mean: bool = False, outcomes: bool = False, group=None, n_groups: int = 1):
         """rollout_policy, step by step: k x (pf_policy_act, pf_env_step) into the same trajectory tensors, the same return value.
         Two launches per step instead of one for the whole rollout, on every single-agent env: QuadX, Fixedwing-Waypoints and
@@ -343,8 +403,15 @@ class BatchEngine(TrainOps):
         rollout_policy_worlds (whole worlds reset on the device), or policy_act and env_step with the culling by hand.
         outcomes=True: every step enqueues pf_episode_outcomes behind pf_env_step (three launches per step), on the step's flag rows
         and on its final_info row under SAME_STEP, on the live state otherwise; (outcome [k, n] uint8, outcome_counts [n_groups, 16]
-        int64, zeroed when the call begins) are appended to what is returned. group [n] int32 in 0..n_groups-1: the row a lane counts in."""
+        int64, zeroed when the call begins) are appended to what is returned. group [n] int32 in 0..n_groups-1: the row a lane counts in.
+        `policy` may be a list of 1..16 MLPPolicy with n_groups = its length (and `group`, required for more than one): lane i is
+        flown by entry group[i] -- G checkpoints side by side in one batch. One pf_policy_pool_plan before the loop, then per step
+        ONE pf_policy_act_pool instead of pf_policy_act; each row has the bits its policy's own pf_policy_act would give it."""
         K.boolean(outcomes, "outcomes")
+        if isinstance(policy, (list, tuple)):
+            pool, k = self._closed_loop_pool(policy, k_steps, group, n_groups)
+            return self._rollout_with(lambda q, t, k, s0, mean, oc=None: self._launch_steps(q, t, k, s0, mean, oc=oc, pool=pool), pool[0][0], k, step_index0,
+                                      store_mean, outcomes, group, n_groups)
         q, k, _ = self._closed_loop(policy, k_steps, False)
         return self._rollout_with(self._launch_steps, q, k, step_index0, store_mean, outcomes, group, n_groups)
 
@@ -398,7 +465,7 @@ class BatchEngine(TrainOps):
             return self.params.vehicle == L.QUADX and self.params.task in (L.TASK_HOVER, L.TASK_WAYPOINTS)
         return fused
 
-    def _launch_steps(self, q, t, k, step_index0, mean, A=None, qo=None, opp_lanes=None, oc=None):
+    def _launch_steps(self, q, t, k, step_index0, mean, A=None, qo=None, opp_lanes=None, oc=None, pool=None):
         """THE stepwise closed loop: k x (pf_policy_act, pf_env_step) into the trajectory tensors `t`, acting first on the engine's
         current observation -- the act of step s reads the row the env wrote at step s - 1, the env's buffer block (a private copy:
         nothing else sees the row cursor) points at the rows of step s, final_obs / final_info rows included where `t` has them.
@@ -409,7 +476,10 @@ class BatchEngine(TrainOps):
         every step ends with pf_episode_outcomes on its flag rows into t["outcome"][s] -- behind pf_env_step, and for worlds behind
         pf_world_sync (it reads valid[s] and the reset mask) and in front of the masked pf_env_reset (it reads the live state); the
         words are the step's final_info row where `t` has one. One device selection and one stream
-        handle for all the calls; no allocation inside the loop, nothing synchronises."""
+        handle for all the calls; no allocation inside the loop, nothing synchronises.
+        With `pool` (a ctypes array of pf_policy blocks, and row_policy [n] int32 or None = every row flies entry 0) the act of every
+        step is ONE pf_policy_act_pool straight into actions[s] (and mean[s]): the plan is made here, once, before the loop, and there
+        is no second act, no opponent buffer and no merge (`q` is not used and `qo` is None)."""
         b = self._block(self._buffers())
         lib, ctx, check, qref, bref = self.lib, self._ctx, L.check, C.byref(q), C.byref(b)
         act, step = lib.pf_policy_act, lib.pf_env_step
@@ -434,15 +504,27 @@ class BatchEngine(TrainOps):
             outcome, ocref, p_out = lib.pf_episode_outcomes, C.byref(oc), t["outcome"].data_ptr()
             if A is not None:
                 oc.world_reset, oc.world_latch = t["reset"].data_ptr(), self.world_outcome.data_ptr()
+        if pool is not None:
+            arr, row_policy = pool
+            if row_policy is None:
+                row_policy = torch.zeros(n, dtype=torch.int32, device=self.device)
+            plan = self.policy_pool_plan(row_policy, len(arr))
+            act_pool, n_pool, p_plan, plan_bytes, head = lib.pf_policy_act_pool, len(arr), C.c_void_p(plan.data_ptr()), plan.numel(), arr[0]
+            aref = C.byref(head)  # (entry 0 is a view of the array's first block: its address is the array's)
         cur = self._cur_obs.data_ptr()
         with torch.cuda.device(self.device):
             stream = self._stream()
             for s in range(k):
                 step_index = (int(step_index0) + s) & 0xFFFFFFFF
-                q.obs0 = cur
-                q.mean_out = p_mean + 4 * n * W * s if p_mean is not None else None
                 a = p_act + 4 * n * W * s
-                rc = act(ctx, qref, a, step_index, stream)
+                if pool is not None:
+                    head.obs0 = cur
+                    head.mean_out = p_mean + 4 * n * W * s if p_mean is not None else None
+                    rc = act_pool(ctx, aref, n_pool, p_plan, plan_bytes, a, step_index, stream)
+                else:
+                    q.obs0 = cur
+                    q.mean_out = p_mean + 4 * n * W * s if p_mean is not None else None
+                    rc = act(ctx, qref, a, step_index, stream)
                 if rc:
                     check(rc, ctx)
                 if opp is not None:
@@ -565,10 +647,15 @@ class BatchEngine(TrainOps):
         self._launch(self.lib.pf_world_sync, C.byref(a), A)
         return valid_out, reset_out
 
-    def _closed_loop_worlds(self, policy, k_steps, agents_per_world, opponent, opponent_lanes, outcomes=False, group=None, n_groups=1):
+    def _closed_loop_worlds(self, policy, k_steps, agents_per_world, opponent, opponent_lanes, outcomes=False, group=None, n_groups=1, pooled=False):
         """What rollout_policy_worlds and collect_rollout_worlds refuse before they touch a tensor; returns (the policy's pf_policy
-        block, the opponents' [(pf_policy block, the [n, 1] bool lanes it flies)] or None, k, A). `opponent`: one MLPPolicy, which flies
-        opponent_lanes, or a list of 1..16 (a pool): entry p flies the opponent_lanes whose group is p (a list of one: all of them)."""
+        block, the opponents' [(pf_policy block, the [n, 1] bool lanes it flies)] or None, k, A, pool). `opponent`: one MLPPolicy, which flies
+        opponent_lanes, or a list of 1..16 (a pool): entry p flies the opponent_lanes whose group is p (a list of one: all of them).
+        `pooled`: `pool` is _launch_steps' -- the blocks of [policy] + the opponents, and row_policy = 1 + group on the opponents'
+        lanes, 0 on the others -- and the list of opponents is None; otherwise `pool` is None."""
+        K.boolean(pooled, "pooled")
+        if pooled and opponent is None:
+            raise ValueError("pooled=True needs an opponent (one policy or a list): the pool launch flies the learner and its opponents in one act, and without an opponent there is nothing to pool")
         if self.params.task == L.TASK_NONE:
             raise ValueError("the world rollout needs an engine with an env task")
         if self.params.autoreset != L.AUTORESET_OFF:
@@ -597,11 +684,15 @@ class BatchEngine(TrainOps):
             K.tensor(self.device, opponent_lanes, "opponent_lanes", (self.n,), K.FLAGS, required="{name} must be a bool / uint8 tensor of shape {shape}")
             K.tensor(self.device, group, "group", (self.n,), torch.int32)
             lanes = opponent_lanes.bool()
+            if pooled:
+                one = torch.ones((), dtype=torch.int32, device=self.device)
+                row_policy = torch.where(lanes, one if len(blocks) == 1 else 1 + group, one - 1).contiguous()
+                return q, None, k, A, ((L.PfPolicy * (1 + len(blocks)))(q, *blocks), row_policy)
             qo = [(b, (lanes if len(blocks) == 1 else lanes & (group == p)).view(self.n, 1)) for p, b in enumerate(blocks)]
-        return q, qo, k, A
+        return q, qo, k, A, None
 
     def rollout_policy_worlds(self, policy, k_steps: int, agents_per_world: int, step_index0: int = 0, opponent=None, opponent_lanes=None,
-                              store_mean: bool = False, outcomes: bool = False, group=None, n_groups: int = 1):
+                              store_mean: bool = False, outcomes: bool = False, group=None, n_groups: int = 1, pooled: bool = False):
         """The closed loop of the multi-agent envs (dogfight, multi-agent hover: auto-reset OFF), with worlds of `agents_per_world`
         adjacent lanes reset on the device once every agent of them has finished. Step s enqueues pf_policy_act(policy,
         step_index0 + s) on the current observation into actions[s] (and mean[s]); pf_env_step into row s; pf_world_sync on row s,
@@ -614,29 +705,34 @@ class BatchEngine(TrainOps):
         reward, terminated, truncated [k, n], actions [k, n, action width], valid [k, n] bool) and, with store_mean, the policy's
         means as a seventh: tensors the engine owns, overwritten by the next call with the same k. The latch is world_done.
         `opponent` may be a list of 1..16 policies (a pool): entry p flies the opponent_lanes whose `group` ([n] int32) is p, at the
-        price of one pf_policy_act over ALL rows and one merge per entry -- P full launches, not P partial ones. outcomes=True: every
+        price of one pf_policy_act over ALL rows and one merge per entry -- P full launches, not P partial ones -- unless pooled=True:
+        then the plan of row_policy = where(opponent_lanes, 1 + group, 0) is made once before the loop (pf_policy_pool_plan) and every
+        step's act is ONE pf_policy_act_pool over [policy] + the opponents straight into actions[s] (and mean[s]), each row evaluated
+        once: four launches per step whatever the pool's size, no second act, no merge. Every returned tensor, the state and the
+        counts have the bits of pooled=False, but for `mean` on an opponent's lanes (which are never valid): pooled, it holds that
+        opponent's own mean; not pooled, the learner's. pooled=True without an opponent is a ValueError. outcomes=True: every
         step enqueues pf_episode_outcomes between pf_world_sync and the reset (one launch more per step) and (outcome [k, n] uint8,
         outcome_counts [n_groups, 16] int64, zeroed when the call begins, row = group) are appended to what is returned; the world
         latch is world_outcome."""
-        q, qo, k, A = self._closed_loop_worlds(policy, k_steps, agents_per_world, opponent, opponent_lanes, outcomes, group, n_groups)
+        q, qo, k, A, pool = self._closed_loop_worlds(policy, k_steps, agents_per_world, opponent, opponent_lanes, outcomes, group, n_groups, pooled)
         t = self._lazy("_wtraj", lambda: self._new_world_traj(k, k), keep=lambda t: t["k"] == k)
         mean = self._traj_mean(t) if store_mean else None
-        self._launch_steps(q, t, k, step_index0, mean, A, qo, opponent_lanes, self._outcome_block(t, k, group, n_groups) if outcomes else None)
+        self._launch_steps(q, t, k, step_index0, mean, A, qo, opponent_lanes, self._outcome_block(t, k, group, n_groups) if outcomes else None, pool)
         out = (t["obs"], t["reward"], t["terminated"], t["truncated"], t["actions"], t["valid"])
         out = out + (mean,) if store_mean else out
         return out + (t["outcome"], t["outcome_counts"]) if outcomes else out
 
     def collect_rollout_worlds(self, policy, k_steps: int, agents_per_world: int, step_index0: int = 0, opponent=None, opponent_lanes=None,
-                               outcomes: bool = False, group=None, n_groups: int = 1):
+                               outcomes: bool = False, group=None, n_groups: int = 1, pooled: bool = False):
         """rollout_policy_worlds for a learner, as collect_rollout is rollout_policy_steps': the same loop into trajectory tensors of
         its own whose observations live in ONE buffer obs_all [k + 1, n, D] -- row 0 a copy of the engine's current observation,
         rows 1 .. k written by the env steps (and, on reset steps, by the resets). Returns collect_rollout's dict (obs_all, obs =
         obs_all[1:], reward, terminated, truncated, actions, mean) plus valid [k, n] bool, and with outcomes=True outcome and
-        outcome_counts (opponent pools, group and n_groups as in rollout_policy_worlds)."""
-        q, qo, k, A = self._closed_loop_worlds(policy, k_steps, agents_per_world, opponent, opponent_lanes, outcomes, group, n_groups)
+        outcome_counts (opponent pools, group, n_groups and pooled as in rollout_policy_worlds)."""
+        q, qo, k, A, pool = self._closed_loop_worlds(policy, k_steps, agents_per_world, opponent, opponent_lanes, outcomes, group, n_groups, pooled)
         t = self._lazy("_wctraj", lambda: self._new_world_traj(k, k + 1), keep=lambda t: t["k"] == k)
         oc = self._outcome_block(t, k, group, n_groups) if outcomes else None
-        return self._collect_into(t, lambda t: self._launch_steps(q, t, k, step_index0, self._traj_mean(t), A, qo, opponent_lanes, oc))
+        return self._collect_into(t, lambda t: self._launch_steps(q, t, k, step_index0, self._traj_mean(t), A, qo, opponent_lanes, oc, pool))
 
     def _new_world_traj(self, k, obs_rows):
         t = self._new_traj(k, obs_rows, mean=False)

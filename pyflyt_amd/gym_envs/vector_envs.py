@@ -192,7 +192,28 @@ class _VecEnvBase(ClosedLoopEnv):
             return self._obs(self.engine.obs), r[1], r[2], r[3], r[4]
         return self._ret
 
-    def rollout(self, policy, k_steps: int, store_mean: bool = False, fused=None, outcomes: bool = False):
+    _pool_groups = None  # {G: [num_envs] int32}: the default segment index of every env for a list of G policies
+
+    def _pool_args(self, policies, fused, group):
+        """rollout()'s refusals for a list of policies, before anything is launched; returns the engine's group / n_groups."""
+        G = len(policies)
+        if not 1 <= G <= L.PF_OUTCOME_MAX_GROUPS or G > self.num_envs:
+            raise ValueError(f"policy: a pool holds 1..{L.PF_OUTCOME_MAX_GROUPS} policies and at most one per env ({self.num_envs}), got {G}")
+        if fused is not None and not isinstance(fused, bool):
+            raise ValueError(f"fused must be None, True or False, got {fused!r}")
+        if fused:
+            raise ValueError("fused=True with a list of policies: the fused launch evaluates one policy; fused=None or False runs the stepwise loop with the pool launch")
+        if group is None:
+            groups = self._pool_groups = self._pool_groups or {}
+            if G not in groups:
+                from ..dist import strong_shard
+
+                sizes = torch.tensor([strong_shard(self.num_envs, g, G).lanes for g in range(G)])
+                groups[G] = torch.repeat_interleave(torch.arange(G, dtype=torch.int32), sizes).to(self.device)
+            group = groups[G]
+        return dict(group=group, n_groups=G)
+
+    def rollout(self, policy, k_steps: int, store_mean: bool = False, fused=None, outcomes: bool = False, group=None):
         """`k_steps` closed-loop env steps, every action computed on the device by `policy` (a pyflyt_amd.MLPPolicy) from the
         observation the env has just returned. Returns the trajectories (obs [k, n, D] -- the engine's flat observation rows, what
         the policy reads --, reward, terminated, truncated, actions [k, n, action width]) and the infos of the LAST step (with
@@ -207,10 +228,23 @@ class _VecEnvBase(ClosedLoopEnv):
         ended) and outcome_counts [1, 16] int64 on the device (episode_outcomes_dict() reads it back) come in front of the infos. One
         pf_episode_outcomes launch per step on the stepwise path; behind the fused launch, one on the final_info rows under
         SAME_STEP. Under NEXT_STEP the fused launch has nothing left to read (collect() says why): fused=None then takes the stepwise
-        path, and fused=True is a ValueError."""
+        path, and fused=True is a ValueError.
+        `policy` may be a list of 1 to 16 MLPPolicy -- checkpoints flown side by side in one batch: env i is flown by entry group[i]
+        (`group`: a [num_envs] int32 tensor; default: contiguous, near-equal segments by dist.strong_shard's rule, as the dogfight's
+        opponent pool uses). Only the stepwise path serves a list (fused=None takes it, fused=True is a ValueError): one
+        pf_policy_pool_plan per call, then per step ONE pf_policy_act_pool, every env evaluated once by its own policy with the bits
+        that policy alone would give it. outcomes=True then returns outcome_counts [G, 16], one row per policy. `group` without a
+        list is a ValueError."""
         if self._needs_reset:
             raise RuntimeError("call reset() before rollout()")
         k = int(k_steps)
+        if isinstance(policy, (list, tuple)):
+            out = self.engine.rollout_policy_steps(list(policy), k, step_index0=self._policy_step, store_mean=store_mean, outcomes=outcomes,
+                                                   **self._pool_args(policy, fused, group))
+            self._after_policy_steps(k)
+            return out + (self._infos_obj,)
+        if group is not None:
+            raise ValueError("group comes with a list of policies (which entry flies an env)")
         if self.engine._fused_policy(fused, outcomes):
             out = self.engine.rollout_policy(policy, k, step_index0=self._policy_step, store_mean=store_mean, outcomes=outcomes)
         else:
@@ -253,7 +287,10 @@ class _VecEnvBase(ClosedLoopEnv):
         stepwise path each step enqueues one pf_episode_outcomes launch behind pf_env_step. The fused launch keeps the flags in
         registers and resets lanes inside the launch: under SAME_STEP its final_info rows hold every ended episode's words and one
         call behind the launch reads them; under NEXT_STEP nothing holds them, so fused=None runs the stepwise loop (the same bits,
-        at the stepwise loop's price) and fused=True with outcomes=True is a ValueError."""
+        at the stepwise loop's price) and fused=True with outcomes=True is a ValueError.
+        A list of policies is refused (ValueError): a batch has one behaviour policy; rollout() flies a list."""
+        if isinstance(policy, (list, tuple)):
+            raise ValueError("collect() takes one policy, not a list: a batch has one behaviour policy (rollout() flies a list of policies side by side)")
         stats = self._collect_args(policy, value_fn, gamma, lam, stats, normalize_reward, outcomes)
         eng, k = self.engine, int(k_steps)
         if not eng._fused_policy(fused, outcomes):  # (refused before the flags are read or anything is launched)

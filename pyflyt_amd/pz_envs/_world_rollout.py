@@ -74,22 +74,23 @@ class WorldRollout(ClosedLoopEnv):
         self.step_count += k
         self.agents = self.possible_agents[:]  # (as after reset_envs: finished copies restart on the device, no agent is culled for good)
 
-    def _world_rollout(self, policy, k_steps, opponent, store_mean, outcomes=False):
+    def _world_rollout(self, policy, k_steps, opponent, store_mean, outcomes=False, pooled=False):
         if self._needs_reset:
             raise RuntimeError("call reset() before rollout()")
         k = int(k_steps)
         opponent, lanes, group, n_groups = self._world_args(opponent)
         out = self.engine.rollout_policy_worlds(policy, k, self.num_possible_agents, step_index0=self._policy_step, opponent=opponent,
-                                                opponent_lanes=lanes, store_mean=bool(store_mean), outcomes=outcomes, group=group, n_groups=n_groups)
+                                                opponent_lanes=lanes, store_mean=bool(store_mean), outcomes=outcomes, group=group, n_groups=n_groups,
+                                                pooled=pooled)
         self._after_worlds(k)
         return out
 
-    def _world_collect(self, policy, value_fn, k_steps, gamma, lam, opponent, stats=False, normalize_reward=False, outcomes=False):
+    def _world_collect(self, policy, value_fn, k_steps, gamma, lam, opponent, stats=False, normalize_reward=False, outcomes=False, pooled=False):
         stats = self._collect_args(policy, value_fn, gamma, lam, stats, normalize_reward, outcomes)
         k = int(k_steps)
         opponent, lanes, group, n_groups = self._world_args(opponent)
         t = self.engine.collect_rollout_worlds(policy, k, self.num_possible_agents, step_index0=self._policy_step, opponent=opponent,
-                                               opponent_lanes=lanes, outcomes=outcomes, group=group, n_groups=n_groups)
+                                               opponent_lanes=lanes, outcomes=outcomes, group=group, n_groups=n_groups, pooled=pooled)
         self._after_worlds(k)
         return self._collect_batch(t, policy, value_fn, gamma, lam, stats, normalize_reward, LazyInfos(self._flat_infos()), valid=t["valid"],
                                    outcomes=outcomes)

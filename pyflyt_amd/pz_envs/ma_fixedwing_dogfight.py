@@ -172,7 +172,7 @@ class MAFixedwingDogfightEnv(WorldRollout):
                 "collision": lambda: (bits() & _DF_COLLISION) != 0, "out_of_bounds": lambda: (bits() & _DF_OOB) != 0,
                 "team_win": lambda: (bits() & _DF_TEAM_WIN) != 0}
 
-    def rollout(self, policy, k_steps: int, opponent=None, store_mean: bool = False, outcomes: bool = False):
+    def rollout(self, policy, k_steps: int, opponent=None, store_mean: bool = False, outcomes: bool = False, pooled: bool = False):
         """`k_steps` closed-loop env steps of every copy, every action computed on the device by `policy` (a pyflyt_amd.MLPPolicy over
         the flattened observation) -- the loop of policy_act, step(), culling and reset_envs() without the host: a copy whose
         aircraft have ALL finished is reset on the device in the next step, which is no transition for any of them
@@ -188,8 +188,13 @@ class MAFixedwingDogfightEnv(WorldRollout):
         the latch as the last step left it, `agents` the full list (as after reset_envs), and step() / reset_envs() go on from there.
         `opponent` may also be a list of 1 to 16 MLPPolicy, a pool (a league's past snapshots): the copies are cut into contiguous,
         near-equal segments of whole copies (dist.strong_shard's rule), segment p's team 1 is flown by entry p, and p is the lanes'
-        group in outcome_counts. Every entry costs one pf_policy_act over ALL rows and one merge onto its segment: P full launches
-        and P merges per step, not P partial ones. opponent=[p] is opponent=p, bit for bit.
+        group in outcome_counts. By default every entry costs one pf_policy_act over ALL rows and one merge onto its segment: P full
+        launches and P merges per step, not P partial ones. opponent=[p] is opponent=p, bit for bit.
+        pooled=True (with an opponent, one or a list; a ValueError without) takes the pool launch instead: the lanes are sorted by who
+        flies them once per call (pf_policy_pool_plan) and every step's act is ONE pf_policy_act_pool for the learner and all its
+        opponents, each row evaluated once by its own policy -- four launches per step whatever the pool's size. Every returned
+        tensor, the final state and outcome_counts have the bits of pooled=False, with one difference: on an opponent's lanes, which
+        are never valid, `mean` holds that opponent's own mean instead of the learner's.
         outcomes=True appends outcome [k, n] uint8 (pf_outcome_bit of every episode that ended: collision, out of bounds, team_win
         as PF_OC_COMPLETE, dead; team 1's lanes included) and outcome_counts [G, 16] int64 on the device, G = 1 or the pool's size:
         per group this call's episodes of the VALID lanes by cause (slots 0-9; slot 8 sums received_hits) and the copies that
@@ -197,10 +202,10 @@ class MAFixedwingDogfightEnv(WorldRollout):
         team_win and none of the other team's did -- an opponent's lanes decide this although they are never valid). A copy is
         tallied in the step that resets it, so one that finishes in the call's last steps is counted by the next call; copies reset
         by reset() / reset_envs() are not tallied. One launch more per step. episode_outcomes_dict() reads a block back by name."""
-        return self._world_rollout(policy, k_steps, opponent, store_mean, outcomes)
+        return self._world_rollout(policy, k_steps, opponent, store_mean, outcomes, pooled)
 
     def collect(self, policy, value_fn, k_steps: int, gamma: float = 0.99, lam: float = 0.95, opponent=None, stats: bool = False,
-                normalize_reward: bool = False, outcomes: bool = False):
+                normalize_reward: bool = False, outcomes: bool = False, pooled: bool = False):
         """One PPO batch from rollout()'s loop, as the vector envs' collect(): `value_fn` (a float32 [M, D] tensor -> [M] or [M, 1])
         runs under torch.no_grad() on all k + 1 observation rows, pf_gae (BatchEngine.gae) supplies advantages, returns and logp.
         Returns a dict with the vector envs' keys: obs [k, n, D] the policy's inputs, actions, mean, logp (None without a log_std),
@@ -222,8 +227,9 @@ class MAFixedwingDogfightEnv(WorldRollout):
         collect() without stats in between advances the env behind its back, and the first episode_return / episode_length after
         it would lack those steps -- reset() the env before switching. reset() and reset_envs() zero the carries of the lanes they
         reset; reset(seed=other) keeps the running moments.
-        `opponent` may be a pool and outcomes=True adds outcome and outcome_counts to the batch, both as rollout() describes them."""
-        return self._world_collect(policy, value_fn, k_steps, gamma, lam, opponent, stats, normalize_reward, outcomes)
+        `opponent` may be a pool, pooled=True flies it in the pool launch, and outcomes=True adds outcome and outcome_counts to the
+        batch, all as rollout() describes them."""
+        return self._world_collect(policy, value_fn, k_steps, gamma, lam, opponent, stats, normalize_reward, outcomes, pooled)
 
     # ------------------------------------------------------------------ ma_fixedwing_base_env.py:272-334
     def step(self, actions: dict):
