@@ -850,6 +850,29 @@ int pf_ppo_loss_opt(pf_ctx* ctx, const pf_ppo_loss_args* a, const pf_ppo_options
 int pf_ppo_grad_opt(pf_ctx* ctx, const pf_ppo_grad_args* a, const pf_ppo_options* options, int64_t rows, void* workspace, size_t workspace_bytes,
                     void* stream);
 
+/* A minibatch of a PPO epoch without a gathered copy: pf_ppo_grad_opt on the m rows of a batch of rows_total rows that an index list
+ * names. By definition the call is pf_ppo_grad_opt(ctx, a', options', m, ...) with t'[j] = t[row_index[j]] for every per-row tensor t:
+ * x, actions, logp_old, advantages, returns, valid and options->values_old. No row is moved: the kernels read their rows through the
+ * index. Every clause of pf_ppo_grad / pf_ppo_grad_opt holds (options == NULL or off: pf_ppo_grad's kernels' arithmetic); what
+ * differs is stated here. (Added without a new PF_ABI_VERSION: a new function, every existing struct as it was.)
+ *   - BIT IDENTITY. Every sum order of pf_ppo_grad is a function of (rows, the two shapes) alone, so every output -- all weight and
+ *     bias gradients, grad_log_std and all sixteen stats slots -- has the bits of pf_ppo_grad_opt on contiguous gathered copies.
+ *   - PER MINIBATCH. c, w = 1 / c, mu and sigma are taken over the m indexed rows: the advantages are normalised per minibatch.
+ *   - THE INDEX. row_index: device, [m], int32. Duplicates are allowed (rows are only read). A row of the batch that no index names
+ *     is never read (but for row 0 under OUT OF RANGE, where nothing of it is chosen): it may hold NaN, in x too.
+ *   - OUT OF RANGE. An index outside [0, rows_total) is never dereferenced. Its slot is an invalid row by selection: zero gradient,
+ *     in no sum, not counted in c. In its place row 0 of every per-row tensor is loaded and not chosen; the slot's x is zeros (row 0
+ *     of x need not be finite). stats[14] = the number of such slots, 0 where there are none (pf_ppo_grad_opt always writes 0).
+ *   - LAUNCHES AND WORKSPACE. The same seven launches, with the row numbers taken through the index; no atomics, no allocation, no
+ *     copy, no host synchronisation -- capturable. The workspace is pf_ppo_grad's, of pf_ppo_grad_workspace_bytes(actor, critic, m).
+ *   - ERRORS, beyond those of pf_ppo_grad_opt (whose `rows` is m here). PF_ERR_ARG, pf_last_error naming the argument: m < 1 or
+ *     m >= 2^31 - 64; rows_total < 1 or rows_total >= 2^31 - 64; row_index NULL (these three first, in this order, before the context
+ *     is looked at); row_index overlapping an output or the workspace. The overlap checks on the inputs use their extents of
+ *     rows_total rows, not m. */
+int pf_ppo_grad_rows(pf_ctx* ctx, const pf_ppo_grad_args* a, const pf_ppo_options* options /* may be NULL */,
+                     const int32_t* row_index /* device, [m] */, int64_t m, int64_t rows_total,
+                     void* workspace, size_t workspace_bytes, void* stream);
+
 /* What a PPO recipe decides from the measured KL, on the device: one launch of one thread behind the loss, no host synchronisation,
  * capturable. Any context. (Added without a new PF_ABI_VERSION: a new function and a new block.)
  *   - kl = stats[5] (approx_kl of pf_ppo_loss / pf_ppo_grad and their _opt forms).

@@ -9,9 +9,9 @@ from ._lib import PyFlytAmdError
 from .params import build_params
 from .moments import RunningMoments
 from .policy import MLPPolicy
-from .ppo import ppo_grad, ppo_loss, ppo_stats_dict
+from .ppo import minibatches, ppo_grad, ppo_loss, ppo_stats_dict
 from .nets import mlp
 from .optim import Adam
 
-__all__ = ["_lib", "PyFlytAmdError", "build_params", "MLPPolicy", "RunningMoments", "ppo_loss", "ppo_grad", "ppo_stats_dict", "mlp", "Adam"]
+__all__ = ["_lib", "PyFlytAmdError", "build_params", "MLPPolicy", "RunningMoments", "ppo_loss", "ppo_grad", "ppo_stats_dict", "minibatches", "mlp", "Adam"]
 __version__ = "0.1.0"

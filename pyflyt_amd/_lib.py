@@ -174,6 +174,8 @@ def lib():
     L.pf_sizeof_ppo_options.restype = C.c_size_t
     L.pf_ppo_loss_opt.argtypes = [C.c_void_p, C.POINTER(PfPpoLoss), C.POINTER(PfPpoOptions), C.c_size_t, C.c_int, C.c_void_p]
     L.pf_ppo_grad_opt.argtypes = [C.c_void_p, C.POINTER(PfPpoGradArgs), C.POINTER(PfPpoOptions), C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.pf_ppo_grad_rows.argtypes = [C.c_void_p, C.POINTER(PfPpoGradArgs), C.POINTER(PfPpoOptions), C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t,
+                                   C.c_void_p]
     L.pf_sizeof_kl_control.restype = C.c_size_t
     L.pf_kl_control.argtypes = [C.c_void_p, C.POINTER(PfKlControl), C.c_void_p]
     L.pf_adam_step_gated.argtypes = [C.c_void_p, C.POINTER(PfAdam), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]

@@ -1,4 +1,4 @@
-// abi_train.hpp -- the C ABI's training side: pf_policy_act, pf_gae, pf_traj_stats / pf_traj_stats_masked, pf_ppo_loss, pf_mlp_forward / pf_mlp_backward, pf_ppo_grad,
+// abi_train.hpp -- the C ABI's training side: pf_policy_act, pf_gae, pf_traj_stats / pf_traj_stats_masked, pf_ppo_loss, pf_mlp_forward / pf_mlp_backward, pf_ppo_grad (and pf_ppo_grad_rows),
 // pf_adam_step, pf_world_sync and pf_episode_outcomes, each behind the checks and launches it shares with another. Host code.
 #pragma once
 #include <cmath>
@@ -41,6 +41,16 @@ static KT ppo_grad_head(const pf_ppo_grad_args* a, const pf_mlp* net, float* par
   K.log_std = a->log_std, K.actions = a->actions, K.logp_old = a->logp_old, K.advantages = a->advantages, K.returns = a->returns;
   K.vbytes = adv.vbytes, K.vmask = adv.vmask, K.fin = adv.fin, K.stat_part = stat_part;
   return K;
+}
+// pf_ppo_grad_rows' tile launch of one network: the head above with the index list
+template <int HEAD, bool OPT>
+static void launch_ppo_grad_rows_head(const pf_ppo_grad_args* a, const pf_mlp* net, float* part, int64_t m, const ppo_adv& adv, double* stat_part,
+                                      const pf::PpoOptK& KO, const int32_t* row_index, int64_t rows_total, int grid, hipStream_t s) {
+  typedef pf::PpoGradRowsK<HEAD, OPT> KT;
+  KT K = ppo_grad_head<KT>(a, net, part, m, adv, stat_part);
+  if constexpr (OPT) K.o = KO;
+  K.row_index = row_index, K.rows_total = (uint32_t)rows_total;
+  hipLaunchKernelGGL(pf::mlp_backward_kernel<KT>, dim3(grid), dim3(256), 0, s, K);
 }
 
 extern "C" {
@@ -161,12 +171,17 @@ static int ppo_coef_check(pf_ctx* ctx, const char* who, float clip, float vf_coe
   if (normalize_advantage != 0 && normalize_advantage != 1) return arg_fail(ctx, who, "normalize_advantage must be 0 or 1");
   return PF_OK;
 }
-static ppo_adv launch_ppo_adv(pf_ctx* ctx, const float* advantages, const uint8_t* valid, size_t rows, hipStream_t s) {
+// row_index: null, or the index list of pf_ppo_grad_rows: `rows` slots into a batch of rows_total rows
+static ppo_adv launch_ppo_adv(pf_ctx* ctx, const float* advantages, const uint8_t* valid, size_t rows, hipStream_t s, const int32_t* row_index = nullptr,
+                              int64_t rows_total = 0) {
   double* adv_part = ctx->ppo_scratch + pf::kPpoAdvOffset;
   // (no valid: the byte loads read the advantages' first M bytes and the mask drops them)
   const ppo_adv r{valid ? valid : reinterpret_cast<const uint8_t*>(advantages), valid ? 0xFFu : 0u, ctx->ppo_scratch + pf::kPpoFinOffset};
   const unsigned grid = pf::ppo_grid(rows);
-  hipLaunchKernelGGL(pf::ppo_adv_kernel, dim3(grid), dim3(pf::kPpoBlock), 0, s, advantages, r.vbytes, r.vmask, rows, adv_part);
+  if (row_index)
+    hipLaunchKernelGGL(pf::ppo_adv_rows_kernel, dim3(grid), dim3(pf::kPpoBlock), 0, s, advantages, r.vbytes, r.vmask, row_index, rows, (uint32_t)rows_total, adv_part);
+  else
+    hipLaunchKernelGGL(pf::ppo_adv_kernel, dim3(grid), dim3(pf::kPpoBlock), 0, s, advantages, r.vbytes, r.vmask, rows, adv_part);
   hipLaunchKernelGGL(pf::ppo_adv_finish_kernel, dim3(1), dim3(pf::kPpoBlock), 0, s, adv_part, (int)grid, r.fin);
   return r;
 }
@@ -372,9 +387,9 @@ size_t pf_ppo_grad_workspace_bytes(const pf_mlp* actor, const pf_mlp* critic, in
   const int grid = pf::mlp_grid(rows);
   return pf::ppo_grad_stat_bytes(grid) + sizeof(float) * (size_t)grid * ((size_t)pf::mlp_param_count(*actor, nullptr) + (size_t)pf::mlp_param_count(*critic, nullptr));
 }
-// pf_ppo_grad (o = NULL) and pf_ppo_grad_opt
+// pf_ppo_grad (o = NULL), pf_ppo_grad_opt and pf_ppo_grad_rows (indexed: rows = m slots of row_index into a batch of rows_total rows)
 static int ppo_grad_call(pf_ctx* ctx, const char* who, const pf_ppo_grad_args* a, const pf_ppo_options* o, int64_t rows, void* workspace, size_t workspace_bytes,
-                         void* stream) {
+                         void* stream, bool indexed = false, const int32_t* row_index = nullptr, int64_t rows_total = 0) {
   if (!ctx) return arg_fail(ctx, who, "ctx is required");
   if (!a) return arg_fail(ctx, who, "the argument block is required");
   if (!a->actor) return arg_fail(ctx, who, "actor is required");
@@ -384,7 +399,7 @@ static int ppo_grad_call(pf_ctx* ctx, const char* who, const pf_ppo_grad_args* a
   const pf_mlp* nets[2] = {a->actor, a->critic};
   if (!mlp_has_params(a->actor)) return arg_fail(ctx, who, "actor: w / b: every layer needs w and b");
   if (!mlp_has_params(a->critic)) return arg_fail(ctx, who, "critic: w / b: every layer needs w and b");
-  if (int rc = rows_check(ctx, who, rows)) return rc;
+  if (int rc = rows_check(ctx, who, rows)) return rc;  // (pf_ppo_grad_rows has refused a bad m in its own words)
   const arg_ptr required[] = {{"x", a->x}, {"log_std", a->log_std}, {"actions", a->actions}, {"logp_old", a->logp_old}, {"advantages", a->advantages},
                               {"returns", a->returns}, {"grad_log_std", a->grad_log_std}, {"stats", a->stats}, {"workspace", workspace}, {nullptr, nullptr}};
   if (int rc = require_args(ctx, who, required)) return rc;
@@ -401,12 +416,14 @@ static int ppo_grad_call(pf_ctx* ctx, const char* who, const pf_ppo_grad_args* a
   const size_t need = pf_ppo_grad_workspace_bytes(a->actor, a->critic, rows);
   if (workspace_bytes < need) return arg_fail(ctx, who, "workspace_bytes is below pf_ppo_grad_workspace_bytes(actor, critic, rows)");
   if (((uintptr_t)workspace & 7) != 0) return arg_fail(ctx, who, "workspace must be 8-byte aligned (it holds rows of double partial sums)");
-  const size_t M = (size_t)rows, A = (size_t)a->actor->out_dim;
+  // M: the rows the inputs hold (an indexed call reads anywhere in the batch); the kernels work on `rows` of them
+  const size_t M = (size_t)(indexed ? rows_total : rows), A = (size_t)a->actor->out_dim;
   pf::PpoOptK KO;
   bool opt = false;
   if (int rc = ppo_options_check(ctx, who, o, (int)A, a->returns, &KO, &opt)) return rc;
-  arg_span spans[8 + 15];
+  arg_span spans[9 + 15];
   int ns = 0;
+  if (indexed) spans[ns++] = {"row_index", row_index, sizeof(int32_t) * (size_t)rows};
   spans[ns++] = {"x", a->x, sizeof(float) * M * a->actor->in_dim};
   spans[ns++] = {"log_std", a->log_std, sizeof(float) * A};
   spans[ns++] = {"actions", a->actions, sizeof(float) * M * A};
@@ -423,11 +440,26 @@ static int ppo_grad_call(pf_ctx* ctx, const char* who, const pf_ppo_grad_args* a
   if (const char* e = spans_overlap(spans, ns, buf, sizeof(buf), n_read)) return arg_fail(ctx, who, e);
   if (int rc = ensure_device(ctx)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  const ppo_adv adv = launch_ppo_adv(ctx, a->advantages, a->valid, M, s);
   const int grid = pf::mlp_grid(rows);
   double* stat_part = (double*)workspace;
   float* const part0 = (float*)((char*)workspace + pf::ppo_grad_stat_bytes(grid));
   float* const part[2] = {part0, part0 + (size_t)grid * (size_t)pf::mlp_param_count(*a->actor, nullptr)};
+  if (indexed) {  // the same seven launches through the index list; with the options off, the heads without them
+    const ppo_adv adv = launch_ppo_adv(ctx, a->advantages, a->valid, (size_t)rows, s, row_index, rows_total);
+    if (opt) {
+      launch_ppo_grad_rows_head<pf::kGradActor, true>(a, a->actor, part[0], rows, adv, stat_part, KO, row_index, rows_total, grid, s);
+      launch_ppo_grad_rows_head<pf::kGradCritic, true>(a, a->critic, part[1], rows, adv, stat_part, KO, row_index, rows_total, grid, s);
+    } else {
+      launch_ppo_grad_rows_head<pf::kGradActor, false>(a, a->actor, part[0], rows, adv, stat_part, KO, row_index, rows_total, grid, s);
+      launch_ppo_grad_rows_head<pf::kGradCritic, false>(a, a->critic, part[1], rows, adv, stat_part, KO, row_index, rows_total, grid, s);
+    }
+    for (int k = 0; k < 2; ++k) launch_mlp_reduce(nets[k], gw[k], gb[k], part[k], grid, s);
+    hipLaunchKernelGGL(opt ? pf::ppo_finish_rows_kernel<true> : pf::ppo_finish_rows_kernel<false>, dim3(1), dim3(pf::kPpoBlock), 0, s, (const double*)stat_part, grid,
+                       (const double*)adv.fin, a->log_std, (int)A, a->vf_coef, a->ent_coef, a->stats, a->grad_log_std, opt ? KO.vclip : 0, opt ? KO.bnd : 0,
+                       opt ? KO.bounds_coef : 0.0f, (const double*)(ctx->ppo_scratch + pf::kPpoAdvOffset), (int)pf::ppo_grid((size_t)rows));
+    return launched(ctx);
+  }
+  const ppo_adv adv = launch_ppo_adv(ctx, a->advantages, a->valid, M, s);
   if (opt) {  // the heads with the options, the same seven launches
     auto KA = ppo_grad_head<pf::PpoGradOptK<pf::kGradActor>>(a, a->actor, part[0], rows, adv, stat_part);
     auto KC = ppo_grad_head<pf::PpoGradOptK<pf::kGradCritic>>(a, a->critic, part[1], rows, adv, stat_part);
@@ -453,6 +485,17 @@ int pf_ppo_grad(pf_ctx* ctx, const pf_ppo_grad_args* a, int64_t rows, void* work
 }
 int pf_ppo_grad_opt(pf_ctx* ctx, const pf_ppo_grad_args* a, const pf_ppo_options* options, int64_t rows, void* workspace, size_t workspace_bytes, void* stream) {
   return ppo_grad_call(ctx, "pf_ppo_grad_opt", a, options, rows, workspace, workspace_bytes, stream);
+}
+int pf_ppo_grad_rows(pf_ctx* ctx, const pf_ppo_grad_args* a, const pf_ppo_options* options, const int32_t* row_index, int64_t m, int64_t rows_total, void* workspace,
+                     size_t workspace_bytes, void* stream) {
+  static const char* who = "pf_ppo_grad_rows";
+  // (what the call adds comes first and needs nothing else: m and rows_total decide every extent below)
+  if (m < 1) return arg_fail(ctx, who, "m must be >= 1");
+  if (m > (int64_t)INT32_MAX - pf::kActRows) return arg_fail(ctx, who, "m must be below 2^31 - 64 (the kernels index slots with 32 bits)");
+  if (rows_total < 1) return arg_fail(ctx, who, "rows_total must be >= 1");
+  if (rows_total > (int64_t)INT32_MAX - pf::kActRows) return arg_fail(ctx, who, "rows_total must be below 2^31 - 64 (row_index holds 32-bit row numbers)");
+  if (!row_index) return arg_fail(ctx, who, "row_index is required");
+  return ppo_grad_call(ctx, who, a, options, m, workspace, workspace_bytes, stream, true, row_index, rows_total);
 }
 size_t pf_adam_workspace_bytes(int64_t total_numel) {
   if (total_numel < 1 || total_numel > (int64_t)INT32_MAX) return 0;

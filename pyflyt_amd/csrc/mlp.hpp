@@ -28,6 +28,10 @@
 // it was as a plain function (profiles/ppo_grad/nothing_moved.txt). With a block derived from MlpK that has a head (ppo_grad.hpp:
 // PpoGradK), step 2 is replaced: the head loads its own row data a tile ahead, and once h_last stands in LDS it computes the output
 // layer and from it the tile's rows of G. Steps 1 and 3 - 6, the running sums and the block of partials are this one text either way.
+// A head with kIndexed (ppo_grad.hpp: PpoGradRowsK) names its rows by an index list: slot j of the n is row row_index[j] of x. Every
+// wave holds a tile's 64 indices, lane = slot, in ONE register, loaded TWO tiles ahead: when the loads of the next tile's rows are
+// issued at the top of a tile, their addresses come from a register that was filled a whole tile earlier, so no dependent load
+// stands on a tile's path. A row number of load_x is uniform over the wave: v_readlane of that register.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -51,6 +55,7 @@ struct MlpK {
   typedef MlpNone Rows;
   typedef MlpNone Sums;
   static constexpr int kHead = 0;  // the rows of G are the caller's grad_out (ppo_grad.hpp: the heads that compute them in the tile)
+  static constexpr bool kIndexed = false;  // a tile's rows are the rows tile * 64 ... of x (ppo_grad.hpp: the heads that take them through an index list)
   pf_mlp Q;
   const float* x;
   const float* grad_out;
@@ -157,6 +162,17 @@ __global__ void __launch_bounds__(256) mlp_backward_kernel(const KT K) {
       x[rr] = (ch < nchunks && c < D) ? K.x[(size_t)g * D + c] : 0.0f;
     }
   };
+  // the same through the index list: `s` = this wave's copy of the tile's 64 row numbers, lane = slot (slots past n repeat slot n - 1's),
+  // -1 where the list's number lay outside the batch: row 0 is loaded in its place and zeros are chosen
+  auto load_x_rows = [&](const int s, const int ch, float (&x)[16]) {
+    const int c = ch * kPolH + lane, wu = __builtin_amdgcn_readfirstlane(wv);
+#pragma unroll
+    for (int rr = 0; rr < 16; ++rr) {
+      const int g = __builtin_amdgcn_readlane(s, wu * 16 + rr);
+      const float v = (ch < nchunks && c < D) ? K.x[(size_t)max(g, 0) * D + c] : 0.0f;
+      x[rr] = g < 0 ? 0.0f : v;
+    }
+  };
   // the tile's rows of grad_out: two elements per thread; rows past n and columns past A are exact zeros, never read
   auto load_g = [&](const int tile, float (&g)[2]) {
 #pragma unroll
@@ -194,9 +210,18 @@ __global__ void __launch_bounds__(256) mlp_backward_kernel(const KT K) {
   float xc[2][16], gq[2];  // the next tile's rows, loaded a tile ahead of their use
   typename KT::Rows hq;    // (a head's rows likewise; its sums for `stats`)
   typename KT::Sums hsum;
-  load_x((int)blockIdx.x, 0, xc[0]);
-  load_x((int)blockIdx.x, 1, xc[1]);
-  if constexpr (HEAD == 0) load_g((int)blockIdx.x, gq); else K.load_rows((int)blockIdx.x, t, hq);
+  int nraw = 0;            // an indexed head: the index list's 64 numbers of the next tile, lane = slot, as loaded
+  if constexpr (KT::kIndexed) {
+    const int s = K.row_of(K.load_index((int)blockIdx.x, lane));  // (the one dependent load of the launch)
+    if ((int)blockIdx.x + (int)gridDim.x < ntiles) nraw = K.load_index((int)blockIdx.x + (int)gridDim.x, lane);
+    load_x_rows(s, 0, xc[0]);
+    load_x_rows(s, 1, xc[1]);
+    K.load_rows((int)blockIdx.x, t, s, hq);
+  } else {
+    load_x((int)blockIdx.x, 0, xc[0]);
+    load_x((int)blockIdx.x, 1, xc[1]);
+    if constexpr (HEAD == 0) load_g((int)blockIdx.x, gq); else K.load_rows((int)blockIdx.x, t, hq);
+  }
   __syncthreads();  // the staged weights
   for (int tile = (int)blockIdx.x; tile < ntiles; tile += (int)gridDim.x) {
     act_barrier();  // the previous tile's readers of TX, TH0 and G are done
@@ -215,7 +240,15 @@ __global__ void __launch_bounds__(256) mlp_backward_kernel(const KT K) {
     } else {
       K.stage_rows(t, hq, HS);
     }
-    if (tile + (int)gridDim.x < ntiles) {
+    if constexpr (KT::kIndexed) {
+      if (tile + (int)gridDim.x < ntiles) {
+        const int s = K.row_of(nraw);  // (arrived during the previous tile)
+        if (tile + 2 * (int)gridDim.x < ntiles) nraw = K.load_index(tile + 2 * (int)gridDim.x, lane);
+        load_x_rows(s, 0, xc[0]);
+        load_x_rows(s, 1, xc[1]);
+        K.load_rows(tile + (int)gridDim.x, t, s, hq);
+      }
+    } else if (tile + (int)gridDim.x < ntiles) {
       load_x(tile + (int)gridDim.x, 0, xc[0]);
       load_x(tile + (int)gridDim.x, 1, xc[1]);
       if constexpr (HEAD == 0) load_g(tile + (int)gridDim.x, gq); else K.load_rows(tile + (int)gridDim.x, t, hq);

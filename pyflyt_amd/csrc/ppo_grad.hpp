@@ -16,6 +16,11 @@
 //   mlp_reduce_kernel x 2                   mlp.hpp's, one per network.
 //   ppo_finish_kernel                       ppo_loss.hpp's, over the mlp_grid(rows) rows of partials.
 //
+// pf_ppo_grad_rows is the same seven launches on the m rows an index list names: ppo_adv_rows_kernel, ppo_adv_finish_kernel as it is,
+// mlp_backward_kernel<PpoGradRowsK<head, options>> (mlp.hpp: how the indices travel a tile ahead of the rows), the two reductions and
+// ppo_finish_rows_kernel. A slot is the same lane of the same tile of the same workgroup as the row of a contiguous call, so every sum
+// has that call's bits.
+//
 // So the order of the double sums behind stats and grad_log_std differs from pf_ppo_loss's (a lane's rows are 64 apart in a tile and the
 // workgroup's tiles gridDim apart; at most 256 rows of partials instead of 1024) and nothing else does. LDS: the backward's 120 576 bytes
 // plus 3 200 for the head, under gfx950's 160 KB with one network staged: a launch per network. No atomics; the grid is mlp_grid(rows).
@@ -65,10 +70,22 @@ struct PpoGradOpt<true> {
   PpoOptK o;
 };
 
-// OPT: the heads of pf_ppo_grad_opt, instantiations of their own (PpoGradOptK below); PpoGradK is the head without
-template <int HEAD, bool OPT>
-struct PpoGradHead : MlpK, PpoGradOpt<OPT> {
+// what a head of pf_ppo_grad_rows adds: the index list [n] and the rows of the batch it points into
+template <bool IDX>
+struct PpoGradIdx {};
+template <>
+struct PpoGradIdx<true> {
+  const int32_t* row_index;
+  uint32_t rows_total;
+};
+constexpr uint32_t kGradBadSlot = 0x100u;  // set in a slot's validity word (a byte otherwise) where its index lay outside the batch
+
+// OPT: the heads of pf_ppo_grad_opt, instantiations of their own (PpoGradOptK below); PpoGradK is the head without.
+// IDX: the heads of pf_ppo_grad_rows (PpoGradRowsK below): slot j of the n is row row_index[j] of every per-row tensor
+template <int HEAD, bool OPT, bool IDX = false>
+struct PpoGradHead : MlpK, PpoGradOpt<OPT>, PpoGradIdx<IDX> {
   static constexpr int kHead = HEAD;
+  static constexpr bool kIndexed = IDX;
   static constexpr int kLdsFloats = kGradLdsFloats;
   typedef PpoGradRows Rows;
   typedef std::conditional_t<OPT, PpoGradOptSums, PpoGradSums> Sums;
@@ -125,6 +142,34 @@ struct PpoGradHead : MlpK, PpoGradOpt<OPT> {
       r.b = vbytes[g];
     }
   }
+  // the index list's number of slot `lane` of a tile as it stands in memory (slots past n: slot n - 1's), and what the kernel makes of
+  // it once it has arrived: the row, or -1 for a number outside [0, rows_total)
+  PF_DEV int load_index(const int tile, const int lane) const { return this->row_index[min(tile * kActRows + lane, n - 1)]; }
+  PF_DEV int row_of(const int raw) const { return (uint32_t)raw < this->rows_total ? raw : -1; }
+  // load_rows through the index: `s` = row_of() of the tile's 64 slots, lane = slot, in every wave. A slot outside the batch loads row 0
+  // and carries kGradBadSlot in its validity word: nothing of it is chosen (make_g)
+  PF_DEV void load_rows(const int tile, const int t, const int s, Rows& r) const {
+    const int A = Q.out_dim;
+    if constexpr (HEAD == kGradActor) {
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const int idx = t + 256 * u, row = idx / kActMaxA, c = idx % kActMaxA;
+        const int g = __shfl(s, row);
+        r.a[u] = (tile * kActRows + row < n && g >= 0 && c < A) ? actions[(size_t)g * A + c] : 0.0f;
+      }
+    }
+    if (t < kActRows) {
+      const size_t g = (size_t)max(s, 0);
+      if constexpr (HEAD == kGradActor) {
+        r.p = logp_old[g];
+        r.q = advantages[g];
+      } else {
+        r.p = returns[g];
+        if constexpr (OPT) r.q = this->o.values_old[g];
+      }
+      r.b = (uint32_t)vbytes[g] | (s < 0 ? kGradBadSlot : 0u);
+    }
+  }
   PF_DEV void stage_rows(const int t, const Rows& r, float* HS) const {
     if constexpr (HEAD == kGradActor) {
 #pragma unroll
@@ -152,7 +197,8 @@ struct PpoGradHead : MlpK, PpoGradOpt<OPT> {
     if (wv == 0) {
       const float w32 = HS[kGradLdsFin];
       const uint32_t all = vmask == 0u ? 1u : 0u;
-      const bool live = tile * kActRows + lane < n && ((__float_as_uint(HS[kGradLdsRow + 2 * kActRows + lane]) & vmask) | all) != 0u;
+      bool live = tile * kActRows + lane < n && ((__float_as_uint(HS[kGradLdsRow + 2 * kActRows + lane]) & vmask) | all) != 0u;
+      if constexpr (IDX) live = live && (__float_as_uint(HS[kGradLdsRow + 2 * kActRows + lane]) & kGradBadSlot) == 0u;
       float* g = G + lane * kMlpGS;
       if constexpr (HEAD == kGradActor) {
         const float cf[5] = {1.0f - clip, 1.0f + clip, w32, HS[kGradLdsFin + 1], HS[kGradLdsFin + 2]};
@@ -231,6 +277,8 @@ template <int HEAD>
 struct PpoGradK : PpoGradHead<HEAD, false> {};
 template <int HEAD>
 struct PpoGradOptK : PpoGradHead<HEAD, true> {};
+template <int HEAD, bool OPT>
+struct PpoGradRowsK : PpoGradHead<HEAD, OPT, true> {};
 
 // the workspace, in this order: the rows of double partials, the actor's blocks of float partials, the critic's
 inline size_t ppo_grad_stat_bytes(int grid) { return sizeof(double) * (size_t)grid * kPpoStride; }

@@ -23,6 +23,8 @@
 // The grid of the two strided kernels is min(ceil(M / 256), 1024): a function of M alone, so (M, A) fix the order of every sum. No
 // atomics. Selections are selects: every input of an invalid row is loaded and then NOT chosen, so a NaN there reaches nothing.
 // A missing `valid` is served without a second instantiation: the byte is read from memory that is readable anyway and masked off.
+// pf_ppo_grad_rows (ppo_grad.hpp) has two siblings here, ppo_adv_rows_kernel and ppo_finish_rows_kernel: the first and the last kernel of
+// a call on the rows an index list names.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -133,6 +135,58 @@ __global__ __launch_bounds__(kPpoBlock) void ppo_adv_kernel(const float* __restr
     partials[(size_t)blockIdx.x * kPpoAdvStride + threadIdx.x] = v;
   }
 }
+
+// ppo_adv_kernel through an index list (pf_ppo_grad_rows): slot j of the m takes the advantage and the validity byte of row row_index[j],
+// the slots to the same threads in the same order, so the three sums have the bits of ppo_adv_kernel on the gathered copies. An index
+// outside [0, rows_total) is not dereferenced: row 0 is loaded in its place and not chosen, and the slot is counted in the partials'
+// fourth column (a whole number: its order of summation is free)
+__global__ __launch_bounds__(kPpoBlock) void ppo_adv_rows_kernel(const float* __restrict__ adv, const uint8_t* __restrict__ vbytes, uint32_t vmask,
+                                                                  const int32_t* __restrict__ row_index, size_t rows, uint32_t rows_total,
+                                                                  double* __restrict__ partials) {
+  __shared__ double sh[kPpoWaves][kPpoAdvStride];
+  const size_t stride = (size_t)gridDim.x * kPpoBlock;
+  const uint32_t all = vmask == 0u ? 1u : 0u;
+  uint32_t n = 0, n_bad = 0;
+  double s1 = 0.0, s2 = 0.0;
+  for (size_t r0 = (size_t)blockIdx.x * kPpoBlock + threadIdx.x; r0 < rows; r0 += (size_t)kPpoAdvUnroll * stride) {
+    uint32_t g[kPpoAdvUnroll];
+    float x[kPpoAdvUnroll];
+    uint32_t b[kPpoAdvUnroll];
+#pragma unroll
+    for (int u = 0; u < kPpoAdvUnroll; ++u) {  // the eight indices, then the eight rows behind them
+      const size_t rw = r0 + (size_t)u * stride;
+      g[u] = (uint32_t)row_index[rw < rows ? rw : rows - 1];
+    }
+#pragma unroll
+    for (int u = 0; u < kPpoAdvUnroll; ++u) {
+      const size_t i = g[u] < rows_total ? g[u] : 0u;  // (a negative index is a large unsigned one)
+      x[u] = adv[i];
+      b[u] = vbytes[i];
+    }
+#pragma unroll
+    for (int u = 0; u < kPpoAdvUnroll; ++u) {
+      const bool in = r0 + (size_t)u * stride < rows, good = g[u] < rows_total;
+      const bool ok = in && good && ((b[u] & vmask) | all) != 0u;
+      const double d = (double)x[u];
+      n += ok ? 1u : 0u;
+      n_bad += in && !good ? 1u : 0u;
+      s1 = s1 + (ok ? d : 0.0);
+      s2 = s2 + (ok ? d * d : 0.0);
+    }
+  }
+  const double q0 = ts_wave_sum((double)n), q1 = ts_wave_sum(s1), q2 = ts_wave_sum(s2), q3 = ts_wave_sum((double)n_bad);
+  const int wave = (int)threadIdx.x / 64, lane = (int)threadIdx.x % 64;
+  if (lane < kPpoAdvStride) sh[wave][lane] = lane == 0 ? q0 : lane == 1 ? q1 : lane == 2 ? q2 : q3;
+  __syncthreads();
+  if (threadIdx.x < kPpoAdvStride) {
+    double v = sh[0][threadIdx.x];
+#pragma unroll
+    for (int w = 1; w < kPpoWaves; ++w) v = v + sh[w][threadIdx.x];
+    partials[(size_t)blockIdx.x * kPpoAdvStride + threadIdx.x] = v;
+  }
+}
+// (ppo_adv_finish_kernel below, as it is, makes c, mu and sigma of these partials; the fourth column waits for the call's last kernel,
+//  ppo_finish_rows_kernel, which adds it up into stats[14])
 
 // One block. fin: c, mu, sigma, then the float32 roundings of mu and of 1 / max(sigma, 1e-8)
 __global__ __launch_bounds__(kPpoBlock) void ppo_adv_finish_kernel(const double* __restrict__ partials, int n_blocks, double* __restrict__ fin) {
@@ -372,11 +426,12 @@ __global__ __launch_bounds__(kPpoBlock) __attribute__((amdgpu_waves_per_eu(KT::k
 constexpr double kPpoEntropyConst = 1.41893853320467274178;  // 1/2 (1 + log 2 pi)
 
 // One block. partials: n_blocks rows of kPpoStride; fin: ppo_adv_finish_kernel's. OPT: the options' three columns are summed too, and
-// vclip / bnd say which of them are live (a column of an option that is off holds a sum nobody asked for, and is not used)
+// vclip / bnd say which of them are live (a column of an option that is off holds a sum nobody asked for, and is not used).
+// bad: null, or a word of LDS written before the call that holds stats[14] (ppo_finish_rows_kernel)
 template <bool OPT>
 PF_DEV void ppo_finish(const double* __restrict__ partials, const int n_blocks, const double* __restrict__ fin, const float* __restrict__ log_std,
                        const int width, const float vf_coef, const float ent_coef, double* __restrict__ stats, float* __restrict__ grad_log_std,
-                       const bool vclip, const bool bnd, const float bounds_coef) {
+                       const bool vclip, const bool bnd, const float bounds_coef, const double* bad = nullptr) {
   constexpr int QN = OPT ? kPpoStride : kPpoQ;
   __shared__ double seg[QN * kPpoSeg];
   const int t = (int)threadIdx.x;
@@ -431,7 +486,7 @@ PF_DEV void ppo_finish(const double* __restrict__ partials, const int n_blocks, 
     stats[11] = total(kPpoSums + 1);
     stats[12] = clipped;
     stats[13] = bounds_loss;
-    stats[14] = 0.0;
+    stats[14] = bad ? *bad : 0.0;
     stats[15] = 0.0;
   }
 }
@@ -445,6 +500,23 @@ __global__ __launch_bounds__(kPpoBlock) void ppo_finish_opt_kernel(const double*
                                                                     double* __restrict__ stats, float* __restrict__ grad_log_std, int vclip, int bnd,
                                                                     float bounds_coef) {
   ppo_finish<true>(partials, n_blocks, fin, log_std, width, vf_coef, ent_coef, stats, grad_log_std, vclip != 0, bnd != 0, bounds_coef);
+}
+// pf_ppo_grad_rows' last kernel: ppo_finish_kernel (OPT = false) or ppo_finish_opt_kernel, with stats[14] = the slots whose index
+// lay outside the batch: the fourth column of ppo_adv_rows_kernel's adv_blocks rows of partials, whole numbers added up by wave 2
+template <bool OPT>
+__global__ __launch_bounds__(kPpoBlock) void ppo_finish_rows_kernel(const double* __restrict__ partials, int n_blocks, const double* __restrict__ fin,
+                                                                     const float* __restrict__ log_std, int width, float vf_coef, float ent_coef,
+                                                                     double* __restrict__ stats, float* __restrict__ grad_log_std, int vclip, int bnd,
+                                                                     float bounds_coef, const double* __restrict__ adv_part, int adv_blocks) {
+  __shared__ double bad;
+  const int wave = (int)threadIdx.x / 64, lane = (int)threadIdx.x % 64;
+  if (wave == 2) {
+    double v = 0.0;
+    for (int b = lane; b < adv_blocks; b += 64) v = v + adv_part[(size_t)b * kPpoAdvStride + kPpoAdvQ];
+    v = ts_wave_sum(v);
+    if (lane == 0) bad = v;
+  }
+  ppo_finish<OPT>(partials, n_blocks, fin, log_std, width, vf_coef, ent_coef, stats, grad_log_std, vclip != 0, bnd != 0, bounds_coef, &bad);  // (its barrier orders the word)
 }
 
 }  // namespace pf

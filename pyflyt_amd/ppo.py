@@ -8,6 +8,7 @@ from torch.autograd.function import once_differentiable
 STAT_NAMES = ("valid_rows", "loss", "policy_loss", "value_loss", "entropy", "approx_kl", "clip_fraction", "advantage_mean", "advantage_std",
               "explained_variance", "ratio_min", "ratio_max")
 OPTION_STAT_NAMES = ("value_clip_fraction", "bounds_loss")  # slots 12 and 13, written by the calls with options
+ROWS_STAT_NAME = "index_out_of_range"  # slot 14, written by ppo_grad(rows=)
 
 
 class _PpoLoss(torch.autograd.Function):
@@ -96,7 +97,7 @@ def ppo_loss(env_or_engine, mean, log_std, value, *batch, valid=None, clip: floa
 
 
 def ppo_grad(env_or_engine, x, actor, critic, log_std, *batch, valid=None, clip: float = 0.2, vf_coef: float = 0.5, ent_coef: float = 0.0,
-             normalize_advantage: bool = True, activation=None, clip_vf=None, action_bounds=None, bounds_coef: float = 0.0, values_old=None):
+             normalize_advantage: bool = True, activation=None, clip_vf=None, action_bounds=None, bounds_coef: float = 0.0, values_old=None, rows=None):
     """stats = ppo_grad(env, x, actor, critic, log_std, batch): one epoch's gradients in one call (pf_ppo_grad). What
     `ppo_loss(env, mlp(env, x, actor), log_std, mlp(env, x, critic), batch)[0].backward()` leaves in .grad, the network gradients bit
     for bit, without the mean, value and their gradient tensors and without the two forward passes: the tile kernel of the backward
@@ -109,7 +110,10 @@ def ppo_grad(env_or_engine, x, actor, critic, log_std, *batch, valid=None, clip:
     tensors, where .grad is None), as loss.backward() does; parameters with requires_grad False are left alone. There is no autograd
     graph and no loss tensor: `stats` is the [16] float64 device tensor of pf_ppo_loss (a copy; ppo_stats_dict names it, slot 1 is
     the loss). x gets no gradient and an x with requires_grad raises ValueError. Nothing synchronises with the host.
-    clip_vf, action_bounds, bounds_coef and values_old are ppo_loss's options (pf_ppo_grad_opt)."""
+    clip_vf, action_bounds, bounds_coef and values_old are ppo_loss's options (pf_ppo_grad_opt).
+    rows=idx, a 1-D contiguous int32 device tensor such as one of minibatches(): the call works on the rows of the flattened batch that
+    idx names (pf_ppo_grad_rows) and gives what it gives on gathered copies of them, bit for bit, without making the copies; the
+    advantages are normalised over those rows. int64 is refused, not converted."""
     from .nets import parse_net
 
     engine = getattr(env_or_engine, "engine", env_or_engine)
@@ -134,7 +138,7 @@ def ppo_grad(env_or_engine, x, actor, critic, log_std, *batch, valid=None, clip:
     detached = [[(w.detach(), b.detach()) for w, b in layers] for layers in (a_layers, c_layers)]
     ga, gc, gls, stats = engine.ppo_grad(x, detached[0], detached[1], log_std.detach(), actions, logp_old, advantages, returns, valid=valid, clip=clip,
                                          vf_coef=vf_coef, ent_coef=ent_coef, normalize_advantage=normalize_advantage, actor_activation=a_act,
-                                         critic_activation=c_act, **options)
+                                         critic_activation=c_act, rows=rows, **options)
     pairs = [(p, g) for layers, grads in ((a_layers, ga), (c_layers, gc)) for lp, lg in zip(layers, grads) for p, g in zip(lp, lg)] + [(log_std, gls)]
     for p, g in pairs:  # (the engine owns its tensors and overwrites them at the next call: .grad gets copies, a few KB)
         if not p.requires_grad:
@@ -146,10 +150,30 @@ def ppo_grad(env_or_engine, x, actor, critic, log_std, *batch, valid=None, clip:
     return stats.clone()
 
 
-def ppo_stats_dict(stats, options: bool = False):
+def minibatches(total_rows, n_minibatches, *, device, generator=None):
+    """The shuffled minibatches of one epoch over a batch of total_rows rows, as ppo_grad(rows=) takes them: ONE
+    torch.randperm(total_rows, dtype=torch.int32) on `device`, cut into n_minibatches contiguous views whose sizes differ by at most
+    one (torch.tensor_split). No kernel of this library and no host synchronisation; `generator` (on `device`) makes it repeatable.
+    Invalid rows are NOT compacted away: a minibatch names its share of them, the kernels drop them by selection, and w = 1 / c is
+    taken per minibatch over its valid rows -- so the minibatches of an epoch weigh the same only as far as their valid counts agree."""
+    for name, v in (("total_rows", total_rows), ("n_minibatches", n_minibatches)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise ValueError(f"{name} must be an int >= 1, got {v!r}")
+    if n_minibatches > total_rows:
+        raise ValueError(f"n_minibatches must be at most total_rows ({total_rows}: a minibatch names a row or more), got {n_minibatches}")
+    if total_rows >= 2 ** 31 - 64:
+        raise ValueError(f"total_rows must be below 2^31 - 64 (the row numbers are int32), got {total_rows}")
+    perm = torch.randperm(total_rows, dtype=torch.int32, device=device, generator=generator)
+    return list(torch.tensor_split(perm, n_minibatches))
+
+
+def ppo_stats_dict(stats, options: bool = False, rows: bool = False):
     """The [16] stats tensor of ppo_loss as Python numbers by name (THE place that synchronises with the device); options=True adds
-    value_clip_fraction and bounds_loss, the two slots the calls with options write."""
+    value_clip_fraction and bounds_loss, the two slots the calls with options write; rows=True adds index_out_of_range, the number
+    of slots of a ppo_grad(rows=) call whose row number lay outside the batch (slot 14; 0 after every other call)."""
     values = stats.tolist()
     out = dict(zip(STAT_NAMES + OPTION_STAT_NAMES if options else STAT_NAMES, values))
     out["valid_rows"] = int(out["valid_rows"])
+    if rows:
+        out[ROWS_STAT_NAME] = int(values[14])
     return out

@@ -443,7 +443,7 @@ class TrainOps:
 
     def ppo_grad(self, x, actor, critic, log_std, actions, logp_old, advantages, returns, valid=None, clip: float = 0.2, vf_coef: float = 0.5,
                  ent_coef: float = 0.0, normalize_advantage: bool = True, actor_activation="tanh", critic_activation="tanh", clip_vf=None,
-                 action_bounds=None, bounds_coef: float = 0.0, values_old=None):
+                 action_bounds=None, bounds_coef: float = 0.0, values_old=None, rows=None):
         """pf_ppo_grad: what mlp_forward(actor), mlp_forward(critic), ppo_loss, mlp_backward(actor), mlp_backward(critic) give on the
         rows of x [..., in_dim], without the mean, value, grad_mean and grad_value tensors between them (include/pyflyt_amd.h has the
         semantics). actor, critic: [(weight, bias), ...] as for mlp_forward, the critic one wide and on the same in_dim; actions
@@ -451,7 +451,12 @@ class TrainOps:
         (actor_grads, critic_grads, grad_log_std [A], stats [16] float64), the first two [(grad_weight, grad_bias), ...]: tensors the
         engine owns, overwritten by the next call with the same rows and layer shapes (stats by every call); so is the workspace.
         clip_vf with values_old [...], action_bounds with bounds_coef: ppo_loss's options (pf_ppo_grad_opt; with the defaults the call
-        is pf_ppo_grad)."""
+        is pf_ppo_grad).
+        rows: None, or a minibatch as a 1-D contiguous int32 tensor [m] of row numbers into the flattened batch (pf_ppo_grad_rows): the
+        call is then the one on the m gathered rows, bit for bit, without a gathered copy; the advantages are normalised over those m
+        rows; duplicates are allowed; a number outside the batch makes its slot an invalid row and is counted in stats[14]. int64 is
+        refused, not converted. The engine's tensors are then those of m rows."""
+        index = rows
         qa, rows, dims_a = self._mlp_block(x, actor, actor_activation)
         qc, _, dims_c = self._mlp_block(x, critic, critic_activation)
         A = dims_a[-1][0]
@@ -466,6 +471,13 @@ class TrainOps:
                 K.tensor(self.device, t, name, shapes, dtypes, required="{name} is required: a tensor of shape {shape}")
         self._ppo_coefficients(clip, vf_coef, ent_coef, normalize_advantage)
         options = self._ppo_options(A, per_row, clip_vf, values_old, action_bounds, bounds_coef)
+        total = rows
+        if index is not None:  # (the workspace and the cache are those of the m rows the call works on)
+            K.ranked(index, "rows", "{name} must be a 1-D int32 tensor of row numbers", 1)
+            rows = int(index.shape[0])
+            if rows < 1:
+                raise ValueError("rows must name at least one row, got an empty tensor")
+            K.tensor(self.device, index, "rows", (rows,), torch.int32)
         cache = self._lazy("_ppo_grad", lambda: dict(stats=torch.zeros(16, dtype=torch.float64, device=self.device)))
         key = (rows, tuple(dims_a), tuple(dims_c))
         o = cache.get(key)
@@ -487,7 +499,10 @@ class TrainOps:
         a.actor, a.critic = C.addressof(qa), C.addressof(qc)
         a.x, a.log_std, a.actions, a.logp_old = _ptr(x), _ptr(log_std), _ptr(actions), _ptr(logp_old)
         a.advantages, a.returns, a.valid = _ptr(advantages), _ptr(returns), _ptr(valid)
-        if options is None:
+        if index is not None:
+            self._launch(self.lib.pf_ppo_grad_rows, C.byref(a), None if options is None else C.byref(options), _ptr(index), rows, total, _ptr(o["workspace"]),
+                         o["bytes"])
+        elif options is None:
             self._launch(self.lib.pf_ppo_grad, C.byref(a), rows, _ptr(o["workspace"]), o["bytes"])
         else:
             self._launch(self.lib.pf_ppo_grad_opt, C.byref(a), C.byref(options), rows, _ptr(o["workspace"]), o["bytes"])

@@ -7,13 +7,15 @@ symbol name normalised, so that a kernel whose mangled name gained a template ar
     python tools/compare_kernel_asm.py /tmp/parent.s /tmp/this.s [regex of the kernels to compare]
 
 Prints one line per kernel (verdict, lines compared, sha256 prefix of either text, name) and the first lines of a difference; exits 1
-if a kernel differs or is missing. profiles/ppo_options/nothing_moved.txt is its output."""
+if a kernel differs or is missing. profiles/ppo_grad_rows/nothing_moved.txt is its output."""
 import difflib
 import hashlib
 import re
 import sys
 
-TRAINING = r"ppo_main_kernel|ppo_finish_kernel|ppo_adv|PpoGradK|adam_update_kernel|adam_norm_kernel|mlp_backward_kernelINS_4MlpK|mlp_reduce|policy_act_kernel"
+TRAINING = (r"ppo_main_kernel|ppo_finish_kernel|ppo_finish_opt_kernel|ppo_adv|PpoGradK|PpoGradOptK|adam_update_kernel|adam_norm_kernel|kl_control|"
+            r"mlp_backward_kernelINS_4MlpK|mlp_reduce|policy_act_kernel")
+NEW = r"PpoGradRowsK|_rows_kernel"  # the kernels of the commit under comparison: on one side only, listed and not compared
 
 
 def functions(path):
@@ -53,13 +55,13 @@ def normalised(lines, name):
 
 def key(name):
     """What a kernel is called on both sides; None for the kernels this comparison is not about (the new instantiations)."""
-    if re.search(r"PpoOptMainK|PpoGradOptK|AdamGatedK|_opt_kernel|kl_control", name):
+    if re.search(NEW, name):
         return None
     m = re.search(r"ppo_main_kernelILi(\d)ELb(\d)E", name)
     if m:
-        return "ppo_main_kernel<%s, %s>" % (m.group(1), "float4" if m.group(2) == "1" else "generic")
+        return "ppo_main_kernel<%s, %s%s>" % (m.group(1), "float4" if m.group(2) == "1" else "generic", ", options" if "PpoOptMainK" in name else "")
     if "adam_update_kernel" in name:
-        return "adam_update_kernel"
+        return "adam_update_kernel<gated>" if "AdamGatedK" in name else "adam_update_kernel"
     return name
 
 
