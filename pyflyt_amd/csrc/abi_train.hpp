@@ -2,6 +2,7 @@
 // pf_adam_step, pf_world_sync and pf_episode_outcomes, each behind the checks and launches it shares with another. Host code.
 #pragma once
 #include <cmath>
+#include <type_traits>
 
 #include "abi_ctx.hpp"  // (with the HIP runtime)
 #include "rocket_landing.hpp"  // kRlActionDim
@@ -32,25 +33,101 @@ struct ppo_adv {
   uint32_t vmask;
   double* fin;
 };
-// a head's block: MlpK, what pf_ppo_grad_args gives both heads, and the call's advantage block and rows of partials
+// pf_ppo_grad_rows' index list: the slots' row numbers into a batch of rows_total rows; index null = a contiguous call, every row its own slot
+struct ppo_rows {
+  const int32_t* index;
+  int64_t rows_total;
+};
+constexpr ppo_rows kNoIndex{nullptr, 0};
+// the moments over `rows` rows, or over the `rows` slots of the index list ix
+static ppo_adv launch_ppo_adv(pf_ctx* ctx, const float* advantages, const uint8_t* valid, size_t rows, const ppo_rows& ix, hipStream_t s) {
+  double* adv_part = ctx->ppo_scratch + pf::kPpoAdvOffset;
+  // (no valid: the byte loads read the advantages' first M bytes and the mask drops them)
+  const ppo_adv r{valid ? valid : reinterpret_cast<const uint8_t*>(advantages), valid ? 0xFFu : 0u, ctx->ppo_scratch + pf::kPpoFinOffset};
+  const unsigned grid = pf::ppo_grid(rows);
+  if (ix.index)
+    hipLaunchKernelGGL(pf::ppo_adv_rows_kernel, dim3(grid), dim3(pf::kPpoBlock), 0, s, advantages, r.vbytes, r.vmask, ix.index, rows, (uint32_t)ix.rows_total, adv_part);
+  else
+    hipLaunchKernelGGL(pf::ppo_adv_kernel, dim3(grid), dim3(pf::kPpoBlock), 0, s, advantages, r.vbytes, r.vmask, rows, adv_part);
+  hipLaunchKernelGGL(pf::ppo_adv_finish_kernel, dim3(1), dim3(pf::kPpoBlock), 0, s, adv_part, (int)grid, r.fin);
+  return r;
+}
+// What pf_ppo_loss and pf_ppo_grad launch last: `kernel`, one of the finish kernels, over n_blocks rows of partials. `a`: either call's
+// argument block; `more`: what ppo_finish_opt_kernel and ppo_finish_rows_kernel take behind the arguments all of them have.
+template <class KERNEL, class ARGS, class... MORE>
+static void launch_ppo_finish(KERNEL kernel, hipStream_t s, const double* partials, int n_blocks, const ppo_adv& adv, const ARGS* a, int width, MORE... more) {
+  hipLaunchKernelGGL(kernel, dim3(1), dim3(pf::kPpoBlock), 0, s, partials, n_blocks, (const double*)adv.fin, a->log_std, width, a->vf_coef, a->ent_coef, a->stats,
+                     a->grad_log_std, more...);
+}
+// ppo_main_kernel's instantiation for a row width and a path; KT: PpoK, or PpoOptMainK for the call with the options
 template <class KT>
-static KT ppo_grad_head(const pf_ppo_grad_args* a, const pf_mlp* net, float* part, int64_t rows, const ppo_adv& adv, double* stat_part) {
+static auto ppo_main_pick(int width, bool vec) -> void (*)(KT, size_t, const double*, double*) {
+  using pf::ppo_main_kernel;
+  void (*const by_width[pf::kPpoMaxA])(KT, size_t, const double*, double*) = {
+      ppo_main_kernel<1, false, KT>, ppo_main_kernel<2, false, KT>, ppo_main_kernel<3, false, KT>, ppo_main_kernel<4, false, KT>,
+      ppo_main_kernel<5, false, KT>, ppo_main_kernel<6, false, KT>, ppo_main_kernel<7, false, KT>, ppo_main_kernel<8, false, KT>};
+  return vec ? ppo_main_kernel<4, true, KT> : by_width[width - 1];
+}
+// pf_ppo_loss' launches behind the advantage pass: the main kernel of K's type and the finish kernel that goes with it
+template <class KT>
+static void launch_ppo_loss(pf_ctx* ctx, const KT& K, const pf_ppo_loss_args* a, size_t rows, int width, const ppo_adv& adv, hipStream_t s) {
+  double* main_part = ctx->ppo_scratch + pf::kPpoMainOffset;
+  const unsigned grid = pf::ppo_grid(rows);
+  // (one float4 per row where the rows are four wide and the caller's pointers allow it; the same arithmetic either way)
+  const bool vec = width == 4 && (((uintptr_t)a->actions | (uintptr_t)a->mean | (uintptr_t)a->grad_mean) & 15) == 0;
+  hipLaunchKernelGGL(ppo_main_pick<KT>(width, vec), dim3(grid), dim3(pf::kPpoBlock), 0, s, K, rows, (const double*)adv.fin, main_part);
+  if constexpr (KT::kOpt)
+    launch_ppo_finish(pf::ppo_finish_opt_kernel, s, main_part, (int)grid, adv, a, width, K.o.vclip, K.o.bnd, K.o.bounds_coef);
+  else
+    launch_ppo_finish(pf::ppo_finish_kernel, s, main_part, (int)grid, adv, a, width);
+}
+// A head's tile launch on one network. Its block is MlpK, what pf_ppo_grad_args gives both heads, the call's advantage block and rows of
+// partials; OPT adds the options KO, IDX the index list. The block's type is the one each call has always named.
+template <int HEAD, bool OPT, bool IDX>
+static void launch_ppo_grad_head(const pf_ppo_grad_args* a, const pf_mlp* net, float* part, int64_t rows, const ppo_adv& adv, double* stat_part,
+                                 const pf::PpoOptK& KO, const ppo_rows& ix, int grid, hipStream_t s) {
+  typedef std::conditional_t<IDX, pf::PpoGradRowsK<HEAD, OPT>, std::conditional_t<OPT, pf::PpoGradOptK<HEAD>, pf::PpoGradK<HEAD>>> KT;
   KT K;
   static_cast<pf::MlpK&>(K) = pf::MlpK{*net, a->x, nullptr, part, (int)rows};
   K.clip = a->clip, K.vf_coef = a->vf_coef, K.normalize = a->normalize_advantage;
   K.log_std = a->log_std, K.actions = a->actions, K.logp_old = a->logp_old, K.advantages = a->advantages, K.returns = a->returns;
   K.vbytes = adv.vbytes, K.vmask = adv.vmask, K.fin = adv.fin, K.stat_part = stat_part;
-  return K;
-}
-// pf_ppo_grad_rows' tile launch of one network: the head above with the index list
-template <int HEAD, bool OPT>
-static void launch_ppo_grad_rows_head(const pf_ppo_grad_args* a, const pf_mlp* net, float* part, int64_t m, const ppo_adv& adv, double* stat_part,
-                                      const pf::PpoOptK& KO, const int32_t* row_index, int64_t rows_total, int grid, hipStream_t s) {
-  typedef pf::PpoGradRowsK<HEAD, OPT> KT;
-  KT K = ppo_grad_head<KT>(a, net, part, m, adv, stat_part);
   if constexpr (OPT) K.o = KO;
-  K.row_index = row_index, K.rows_total = (uint32_t)rows_total;
+  if constexpr (IDX) K.row_index = ix.index, K.rows_total = (uint32_t)ix.rows_total;
   hipLaunchKernelGGL(pf::mlp_backward_kernel<KT>, dim3(grid), dim3(256), 0, s, K);
+}
+// the workgroups' partial gradients (`part`, one row of the network's parameters per workgroup of the backward launch) summed into gw / gb
+static void launch_mlp_reduce(const pf_mlp* q, float* const* gw, float* const* gb, const float* part, int grid, hipStream_t s) {
+  pf::MlpOutK O;
+  const int P = pf::mlp_param_count(*q, O.end);
+  for (int l = 0; l < 3; ++l) {
+    O.p[2 * l] = l < q->n_layers ? gw[l] : nullptr;
+    O.p[2 * l + 1] = l < q->n_layers ? gb[l] : nullptr;
+  }
+  hipLaunchKernelGGL(pf::mlp_reduce_kernel, dim3((P + 255) / 256), dim3(256), 0, s, part, grid, P, O);
+}
+// The seven launches of a gradient call on `rows` rows, or slots of ix: the advantage pass and its finish, the actor's head and the critic's,
+// a reduction for each, the finish. OPT: the heads and the finish with the options KO; IDX: all of them through the index list (DESIGN.md
+// section 31 has the table). gw / gb: either network's gradient outputs.
+template <bool OPT, bool IDX>
+static void launch_ppo_grad(pf_ctx* ctx, const pf_ppo_grad_args* a, float* const* const (&gw)[2], float* const* const (&gb)[2], const pf::PpoOptK& KO,
+                            const ppo_rows& ix, int64_t rows, void* workspace, hipStream_t s) {
+  const pf_mlp* nets[2] = {a->actor, a->critic};
+  const int grid = pf::mlp_grid(rows), A = a->actor->out_dim;
+  double* stat_part = (double*)workspace;
+  float* const part0 = (float*)((char*)workspace + pf::ppo_grad_stat_bytes(grid));
+  float* const part[2] = {part0, part0 + (size_t)grid * (size_t)pf::mlp_param_count(*a->actor, nullptr)};
+  const ppo_adv adv = launch_ppo_adv(ctx, a->advantages, a->valid, (size_t)rows, ix, s);
+  launch_ppo_grad_head<pf::kGradActor, OPT, IDX>(a, nets[0], part[0], rows, adv, stat_part, KO, ix, grid, s);
+  launch_ppo_grad_head<pf::kGradCritic, OPT, IDX>(a, nets[1], part[1], rows, adv, stat_part, KO, ix, grid, s);
+  for (int k = 0; k < 2; ++k) launch_mlp_reduce(nets[k], gw[k], gb[k], part[k], grid, s);
+  if constexpr (IDX)  // (with the options off, the finish without them: nothing of KO is read)
+    launch_ppo_finish(pf::ppo_finish_rows_kernel<OPT>, s, stat_part, grid, adv, a, A, OPT ? KO.vclip : 0, OPT ? KO.bnd : 0, OPT ? KO.bounds_coef : 0.0f,
+                      (const double*)(ctx->ppo_scratch + pf::kPpoAdvOffset), (int)pf::ppo_grid((size_t)rows));
+  else if constexpr (OPT)
+    launch_ppo_finish(pf::ppo_finish_opt_kernel, s, stat_part, grid, adv, a, A, KO.vclip, KO.bnd, KO.bounds_coef);
+  else
+    launch_ppo_finish(pf::ppo_finish_kernel, s, stat_part, grid, adv, a, A);
 }
 
 extern "C" {
@@ -171,20 +248,6 @@ static int ppo_coef_check(pf_ctx* ctx, const char* who, float clip, float vf_coe
   if (normalize_advantage != 0 && normalize_advantage != 1) return arg_fail(ctx, who, "normalize_advantage must be 0 or 1");
   return PF_OK;
 }
-// row_index: null, or the index list of pf_ppo_grad_rows: `rows` slots into a batch of rows_total rows
-static ppo_adv launch_ppo_adv(pf_ctx* ctx, const float* advantages, const uint8_t* valid, size_t rows, hipStream_t s, const int32_t* row_index = nullptr,
-                              int64_t rows_total = 0) {
-  double* adv_part = ctx->ppo_scratch + pf::kPpoAdvOffset;
-  // (no valid: the byte loads read the advantages' first M bytes and the mask drops them)
-  const ppo_adv r{valid ? valid : reinterpret_cast<const uint8_t*>(advantages), valid ? 0xFFu : 0u, ctx->ppo_scratch + pf::kPpoFinOffset};
-  const unsigned grid = pf::ppo_grid(rows);
-  if (row_index)
-    hipLaunchKernelGGL(pf::ppo_adv_rows_kernel, dim3(grid), dim3(pf::kPpoBlock), 0, s, advantages, r.vbytes, r.vmask, row_index, rows, (uint32_t)rows_total, adv_part);
-  else
-    hipLaunchKernelGGL(pf::ppo_adv_kernel, dim3(grid), dim3(pf::kPpoBlock), 0, s, advantages, r.vbytes, r.vmask, rows, adv_part);
-  hipLaunchKernelGGL(pf::ppo_adv_finish_kernel, dim3(1), dim3(pf::kPpoBlock), 0, s, adv_part, (int)grid, r.fin);
-  return r;
-}
 // What pf_ppo_loss_opt and pf_ppo_grad_opt check of their options, A = the action width. *on = an option is on (off: the call is the
 // one without options); K: the kernels' block, an option that is off filled so that nothing of it is chosen (`readable`: M floats)
 static int ppo_options_check(pf_ctx* ctx, const char* who, const pf_ppo_options* o, int A, const float* readable, pf::PpoOptK* K, bool* on) {
@@ -212,11 +275,7 @@ static int ppo_options_check(pf_ctx* ctx, const char* who, const pf_ppo_options*
 }
 // pf_ppo_loss (o = NULL) and pf_ppo_loss_opt
 static int ppo_loss_call(pf_ctx* ctx, const char* who, const pf_ppo_loss_args* a, const pf_ppo_options* o, size_t rows, int width, void* stream) {
-  if (!ctx || !a) {
-    char buf[96];
-    snprintf(buf, sizeof(buf), "%s: ctx and the argument block are required", who);
-    return fail(ctx, PF_ERR_ARG, buf);
-  }
+  if (!ctx || !a) return arg_fail(ctx, who, "ctx and the argument block are required");
   if (rows < 1) return arg_fail(ctx, who, "rows must be >= 1");
   if (width < 1 || width > pf::kPpoMaxA) return arg_fail(ctx, who, "width must be in 1..8");
   const arg_ptr required[] = {{"mean", a->mean}, {"log_std", a->log_std}, {"actions", a->actions}, {"logp_old", a->logp_old},
@@ -224,38 +283,18 @@ static int ppo_loss_call(pf_ctx* ctx, const char* who, const pf_ppo_loss_args* a
                               {"grad_value", a->grad_value}, {"grad_log_std", a->grad_log_std}, {"stats", a->stats}, {nullptr, nullptr}};
   if (int rc = require_args(ctx, who, required)) return rc;
   if (int rc = ppo_coef_check(ctx, who, a->clip, a->vf_coef, a->ent_coef, a->normalize_advantage)) return rc;
-  pf::PpoOptMainK KO;
+  pf::PpoOptMainK K;  // (the call without options passes the PpoK in it)
   bool opt = false;
-  if (int rc = ppo_options_check(ctx, who, o, width, a->returns, &KO.o, &opt)) return rc;
+  if (int rc = ppo_options_check(ctx, who, o, width, a->returns, &K.o, &opt)) return rc;
   if (int rc = ensure_device(ctx)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  const ppo_adv adv = launch_ppo_adv(ctx, a->advantages, a->valid, rows, s);
-  double* main_part = ctx->ppo_scratch + pf::kPpoMainOffset;
-  const unsigned grid = pf::ppo_grid(rows);
-  const pf::PpoK K{a->clip, a->vf_coef, a->normalize_advantage, a->mean, a->log_std, a->actions, a->logp_old, a->advantages, a->returns, a->value,
-                   adv.vbytes, adv.vmask, a->grad_mean, a->grad_value};
-  // (one float4 per row where the rows are four wide and the caller's pointers allow it; the same arithmetic either way)
-  const bool vec = width == 4 && (((uintptr_t)a->actions | (uintptr_t)a->mean | (uintptr_t)a->grad_mean) & 15) == 0;
-  using pf::ppo_main_kernel;
-  using pf::PpoK, pf::PpoOptMainK;
-  void (*const by_width[pf::kPpoMaxA])(PpoK, size_t, const double*, double*) = {
-      ppo_main_kernel<1, false, PpoK>, ppo_main_kernel<2, false, PpoK>, ppo_main_kernel<3, false, PpoK>, ppo_main_kernel<4, false, PpoK>,
-      ppo_main_kernel<5, false, PpoK>, ppo_main_kernel<6, false, PpoK>, ppo_main_kernel<7, false, PpoK>, ppo_main_kernel<8, false, PpoK>};
-  if (opt) {  // the instantiations with the options; the same choice of path
-    void (*const opt_by_width[pf::kPpoMaxA])(PpoOptMainK, size_t, const double*, double*) = {
-        ppo_main_kernel<1, false, PpoOptMainK>, ppo_main_kernel<2, false, PpoOptMainK>, ppo_main_kernel<3, false, PpoOptMainK>, ppo_main_kernel<4, false, PpoOptMainK>,
-        ppo_main_kernel<5, false, PpoOptMainK>, ppo_main_kernel<6, false, PpoOptMainK>, ppo_main_kernel<7, false, PpoOptMainK>, ppo_main_kernel<8, false, PpoOptMainK>};
-    static_cast<PpoK&>(KO) = K;
-    const auto main_opt_kernel = vec ? ppo_main_kernel<4, true, PpoOptMainK> : opt_by_width[width - 1];
-    hipLaunchKernelGGL(main_opt_kernel, dim3(grid), dim3(pf::kPpoBlock), 0, s, KO, rows, (const double*)adv.fin, main_part);
-    hipLaunchKernelGGL(pf::ppo_finish_opt_kernel, dim3(1), dim3(pf::kPpoBlock), 0, s, (const double*)main_part, (int)grid, (const double*)adv.fin, a->log_std,
-                       width, a->vf_coef, a->ent_coef, a->stats, a->grad_log_std, KO.o.vclip, KO.o.bnd, KO.o.bounds_coef);
-    return launched(ctx);
-  }
-  const auto main_kernel = vec ? ppo_main_kernel<4, true, PpoK> : by_width[width - 1];
-  hipLaunchKernelGGL(main_kernel, dim3(grid), dim3(pf::kPpoBlock), 0, s, K, rows, (const double*)adv.fin, main_part);
-  hipLaunchKernelGGL(pf::ppo_finish_kernel, dim3(1), dim3(pf::kPpoBlock), 0, s, (const double*)main_part, (int)grid, (const double*)adv.fin, a->log_std, width,
-                     a->vf_coef, a->ent_coef, a->stats, a->grad_log_std);
+  const ppo_adv adv = launch_ppo_adv(ctx, a->advantages, a->valid, rows, kNoIndex, s);
+  static_cast<pf::PpoK&>(K) = pf::PpoK{a->clip, a->vf_coef, a->normalize_advantage, a->mean, a->log_std, a->actions, a->logp_old, a->advantages, a->returns, a->value,
+                                      adv.vbytes, adv.vmask, a->grad_mean, a->grad_value};
+  if (opt)
+    launch_ppo_loss<pf::PpoOptMainK>(ctx, K, a, rows, width, adv, s);
+  else
+    launch_ppo_loss<pf::PpoK>(ctx, K, a, rows, width, adv, s);
   return launched(ctx);
 }
 int pf_ppo_loss(pf_ctx* ctx, const pf_ppo_loss_args* a, size_t rows, int width, void* stream) {
@@ -280,10 +319,15 @@ static bool mlp_has_params(const pf_mlp* q) {
     if (!q->w[l] || !q->b[l]) return false;
   return true;
 }
-static int rows_check(pf_ctx* ctx, const char* who, int64_t rows) {
-  if (rows < 1) return arg_fail(ctx, who, "rows must be >= 1");
-  if (rows > (int64_t)INT32_MAX - pf::kActRows) return arg_fail(ctx, who, "rows must be below 2^31 - 64 (the kernels index rows with 32 bits)");
-  return PF_OK;
+// a count of rows under the name the call gives it: 1 or more, and below what the tile loops reach in 32 bits (`why`: the call's reason for that)
+static int rows_check(pf_ctx* ctx, const char* who, int64_t rows, const char* name, const char* why) {
+  if (rows >= 1 && rows <= (int64_t)INT32_MAX - pf::kActRows) return PF_OK;
+  char what[128];
+  if (rows < 1)
+    snprintf(what, sizeof(what), "%s must be >= 1", name);
+  else
+    snprintf(what, sizeof(what), "%s must be below 2^31 - 64 (%s)", name, why);
+  return arg_fail(ctx, who, what);
 }
 // pf_mlp_forward / pf_mlp_backward: what both check first, the context included; `who` is the call's name
 static int mlp_check(pf_ctx* ctx, const char* who, const pf_mlp* q, int64_t rows) {
@@ -291,7 +335,7 @@ static int mlp_check(pf_ctx* ctx, const char* who, const pf_mlp* q, int64_t rows
   if (!q) return arg_fail(ctx, who, "mlp is required");
   if (const char* e = mlp_shape_error(q)) return arg_fail(ctx, who, e);
   if (!mlp_has_params(q)) return arg_fail(ctx, who, "w / b: every layer needs w and b");
-  return rows_check(ctx, who, rows);
+  return rows_check(ctx, who, rows, "rows", "the kernels index rows with 32 bits");
 }
 // a network's gradient outputs as spans, layer l's under the names wn[l] and bn[l]; returns the new count
 static int append_grad_spans(arg_span* spans, int ns, const pf_mlp* q, const char* const* wn, const char* const* bn, float* const* gw, float* const* gb) {
@@ -301,16 +345,6 @@ static int append_grad_spans(arg_span* spans, int ns, const pf_mlp* q, const cha
     spans[ns++] = {bn[l], gb[l], sizeof(float) * n_out};
   }
   return ns;
-}
-// the workgroups' partial gradients (`part`, one row of the network's parameters per workgroup of the backward launch) summed into gw / gb
-static void launch_mlp_reduce(const pf_mlp* q, float* const* gw, float* const* gb, const float* part, int grid, hipStream_t s) {
-  pf::MlpOutK O;
-  const int P = pf::mlp_param_count(*q, O.end);
-  for (int l = 0; l < 3; ++l) {
-    O.p[2 * l] = l < q->n_layers ? gw[l] : nullptr;
-    O.p[2 * l + 1] = l < q->n_layers ? gb[l] : nullptr;
-  }
-  hipLaunchKernelGGL(pf::mlp_reduce_kernel, dim3((P + 255) / 256), dim3(256), 0, s, part, grid, P, O);
 }
 int pf_mlp_forward(pf_ctx* ctx, const pf_mlp* q, const float* x, int64_t rows, float* out, void* stream) {
   static const char* who = "pf_mlp_forward";
@@ -387,9 +421,9 @@ size_t pf_ppo_grad_workspace_bytes(const pf_mlp* actor, const pf_mlp* critic, in
   const int grid = pf::mlp_grid(rows);
   return pf::ppo_grad_stat_bytes(grid) + sizeof(float) * (size_t)grid * ((size_t)pf::mlp_param_count(*actor, nullptr) + (size_t)pf::mlp_param_count(*critic, nullptr));
 }
-// pf_ppo_grad (o = NULL), pf_ppo_grad_opt and pf_ppo_grad_rows (indexed: rows = m slots of row_index into a batch of rows_total rows)
-static int ppo_grad_call(pf_ctx* ctx, const char* who, const pf_ppo_grad_args* a, const pf_ppo_options* o, int64_t rows, void* workspace, size_t workspace_bytes,
-                         void* stream, bool indexed = false, const int32_t* row_index = nullptr, int64_t rows_total = 0) {
+// pf_ppo_grad (o = NULL), pf_ppo_grad_opt and pf_ppo_grad_rows (ix.index: rows = m slots of it into a batch of ix.rows_total rows)
+static int ppo_grad_call(pf_ctx* ctx, const char* who, const pf_ppo_grad_args* a, const pf_ppo_options* o, int64_t rows, const ppo_rows& ix, void* workspace,
+                         size_t workspace_bytes, void* stream) {
   if (!ctx) return arg_fail(ctx, who, "ctx is required");
   if (!a) return arg_fail(ctx, who, "the argument block is required");
   if (!a->actor) return arg_fail(ctx, who, "actor is required");
@@ -399,14 +433,15 @@ static int ppo_grad_call(pf_ctx* ctx, const char* who, const pf_ppo_grad_args* a
   const pf_mlp* nets[2] = {a->actor, a->critic};
   if (!mlp_has_params(a->actor)) return arg_fail(ctx, who, "actor: w / b: every layer needs w and b");
   if (!mlp_has_params(a->critic)) return arg_fail(ctx, who, "critic: w / b: every layer needs w and b");
-  if (int rc = rows_check(ctx, who, rows)) return rc;  // (pf_ppo_grad_rows has refused a bad m in its own words)
+  if (!ix.index)  // (pf_ppo_grad_rows has refused a bad m, under that name, before anything else)
+    if (int rc = rows_check(ctx, who, rows, "rows", "the kernels index rows with 32 bits")) return rc;
   const arg_ptr required[] = {{"x", a->x}, {"log_std", a->log_std}, {"actions", a->actions}, {"logp_old", a->logp_old}, {"advantages", a->advantages},
                               {"returns", a->returns}, {"grad_log_std", a->grad_log_std}, {"stats", a->stats}, {"workspace", workspace}, {nullptr, nullptr}};
   if (int rc = require_args(ctx, who, required)) return rc;
   static const char* const gn[2][2][3] = {{{"actor_grad_w[0]", "actor_grad_w[1]", "actor_grad_w[2]"}, {"actor_grad_b[0]", "actor_grad_b[1]", "actor_grad_b[2]"}},
                                           {{"critic_grad_w[0]", "critic_grad_w[1]", "critic_grad_w[2]"}, {"critic_grad_b[0]", "critic_grad_b[1]", "critic_grad_b[2]"}}};
-  float* const* gw[2] = {a->actor_grad_w, a->critic_grad_w};
-  float* const* gb[2] = {a->actor_grad_b, a->critic_grad_b};
+  float* const* const gw[2] = {a->actor_grad_w, a->critic_grad_w};
+  float* const* const gb[2] = {a->actor_grad_b, a->critic_grad_b};
   for (int k = 0; k < 2; ++k)
     for (int l = 0; l < nets[k]->n_layers; ++l) {
       const arg_ptr outs[] = {{gn[k][0][l], gw[k][l]}, {gn[k][1][l], gb[k][l]}, {nullptr, nullptr}};
@@ -417,13 +452,13 @@ static int ppo_grad_call(pf_ctx* ctx, const char* who, const pf_ppo_grad_args* a
   if (workspace_bytes < need) return arg_fail(ctx, who, "workspace_bytes is below pf_ppo_grad_workspace_bytes(actor, critic, rows)");
   if (((uintptr_t)workspace & 7) != 0) return arg_fail(ctx, who, "workspace must be 8-byte aligned (it holds rows of double partial sums)");
   // M: the rows the inputs hold (an indexed call reads anywhere in the batch); the kernels work on `rows` of them
-  const size_t M = (size_t)(indexed ? rows_total : rows), A = (size_t)a->actor->out_dim;
+  const size_t M = (size_t)(ix.index ? ix.rows_total : rows), A = (size_t)a->actor->out_dim;
   pf::PpoOptK KO;
   bool opt = false;
   if (int rc = ppo_options_check(ctx, who, o, (int)A, a->returns, &KO, &opt)) return rc;
   arg_span spans[9 + 15];
   int ns = 0;
-  if (indexed) spans[ns++] = {"row_index", row_index, sizeof(int32_t) * (size_t)rows};
+  if (ix.index) spans[ns++] = {"row_index", ix.index, sizeof(int32_t) * (size_t)rows};
   spans[ns++] = {"x", a->x, sizeof(float) * M * a->actor->in_dim};
   spans[ns++] = {"log_std", a->log_std, sizeof(float) * A};
   spans[ns++] = {"actions", a->actions, sizeof(float) * M * A};
@@ -439,63 +474,24 @@ static int ppo_grad_call(pf_ctx* ctx, const char* who, const pf_ppo_grad_args* a
   for (int k = 0; k < 2; ++k) ns = append_grad_spans(spans, ns, nets[k], gn[k][0], gn[k][1], gw[k], gb[k]);
   if (const char* e = spans_overlap(spans, ns, buf, sizeof(buf), n_read)) return arg_fail(ctx, who, e);
   if (int rc = ensure_device(ctx)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  const int grid = pf::mlp_grid(rows);
-  double* stat_part = (double*)workspace;
-  float* const part0 = (float*)((char*)workspace + pf::ppo_grad_stat_bytes(grid));
-  float* const part[2] = {part0, part0 + (size_t)grid * (size_t)pf::mlp_param_count(*a->actor, nullptr)};
-  if (indexed) {  // the same seven launches through the index list; with the options off, the heads without them
-    const ppo_adv adv = launch_ppo_adv(ctx, a->advantages, a->valid, (size_t)rows, s, row_index, rows_total);
-    if (opt) {
-      launch_ppo_grad_rows_head<pf::kGradActor, true>(a, a->actor, part[0], rows, adv, stat_part, KO, row_index, rows_total, grid, s);
-      launch_ppo_grad_rows_head<pf::kGradCritic, true>(a, a->critic, part[1], rows, adv, stat_part, KO, row_index, rows_total, grid, s);
-    } else {
-      launch_ppo_grad_rows_head<pf::kGradActor, false>(a, a->actor, part[0], rows, adv, stat_part, KO, row_index, rows_total, grid, s);
-      launch_ppo_grad_rows_head<pf::kGradCritic, false>(a, a->critic, part[1], rows, adv, stat_part, KO, row_index, rows_total, grid, s);
-    }
-    for (int k = 0; k < 2; ++k) launch_mlp_reduce(nets[k], gw[k], gb[k], part[k], grid, s);
-    hipLaunchKernelGGL(opt ? pf::ppo_finish_rows_kernel<true> : pf::ppo_finish_rows_kernel<false>, dim3(1), dim3(pf::kPpoBlock), 0, s, (const double*)stat_part, grid,
-                       (const double*)adv.fin, a->log_std, (int)A, a->vf_coef, a->ent_coef, a->stats, a->grad_log_std, opt ? KO.vclip : 0, opt ? KO.bnd : 0,
-                       opt ? KO.bounds_coef : 0.0f, (const double*)(ctx->ppo_scratch + pf::kPpoAdvOffset), (int)pf::ppo_grid((size_t)rows));
-    return launched(ctx);
-  }
-  const ppo_adv adv = launch_ppo_adv(ctx, a->advantages, a->valid, M, s);
-  if (opt) {  // the heads with the options, the same seven launches
-    auto KA = ppo_grad_head<pf::PpoGradOptK<pf::kGradActor>>(a, a->actor, part[0], rows, adv, stat_part);
-    auto KC = ppo_grad_head<pf::PpoGradOptK<pf::kGradCritic>>(a, a->critic, part[1], rows, adv, stat_part);
-    KA.o = KC.o = KO;
-    hipLaunchKernelGGL(pf::mlp_backward_kernel<pf::PpoGradOptK<pf::kGradActor>>, dim3(grid), dim3(256), 0, s, KA);
-    hipLaunchKernelGGL(pf::mlp_backward_kernel<pf::PpoGradOptK<pf::kGradCritic>>, dim3(grid), dim3(256), 0, s, KC);
-    for (int k = 0; k < 2; ++k) launch_mlp_reduce(nets[k], gw[k], gb[k], part[k], grid, s);
-    hipLaunchKernelGGL(pf::ppo_finish_opt_kernel, dim3(1), dim3(pf::kPpoBlock), 0, s, (const double*)stat_part, grid, (const double*)adv.fin, a->log_std, (int)A,
-                       a->vf_coef, a->ent_coef, a->stats, a->grad_log_std, KO.vclip, KO.bnd, KO.bounds_coef);
-    return launched(ctx);
-  }
-  const auto KA = ppo_grad_head<pf::PpoGradK<pf::kGradActor>>(a, a->actor, part[0], rows, adv, stat_part);
-  const auto KC = ppo_grad_head<pf::PpoGradK<pf::kGradCritic>>(a, a->critic, part[1], rows, adv, stat_part);
-  hipLaunchKernelGGL(pf::mlp_backward_kernel<pf::PpoGradK<pf::kGradActor>>, dim3(grid), dim3(256), 0, s, KA);
-  hipLaunchKernelGGL(pf::mlp_backward_kernel<pf::PpoGradK<pf::kGradCritic>>, dim3(grid), dim3(256), 0, s, KC);
-  for (int k = 0; k < 2; ++k) launch_mlp_reduce(nets[k], gw[k], gb[k], part[k], grid, s);
-  hipLaunchKernelGGL(pf::ppo_finish_kernel, dim3(1), dim3(pf::kPpoBlock), 0, s, (const double*)stat_part, grid, (const double*)adv.fin, a->log_std, (int)A, a->vf_coef,
-                     a->ent_coef, a->stats, a->grad_log_std);
+  const auto launches = ix.index ? (opt ? launch_ppo_grad<true, true> : launch_ppo_grad<false, true>) : (opt ? launch_ppo_grad<true, false> : launch_ppo_grad<false, false>);
+  launches(ctx, a, gw, gb, KO, ix, rows, workspace, (hipStream_t)stream);
   return launched(ctx);
 }
 int pf_ppo_grad(pf_ctx* ctx, const pf_ppo_grad_args* a, int64_t rows, void* workspace, size_t workspace_bytes, void* stream) {
-  return ppo_grad_call(ctx, "pf_ppo_grad", a, nullptr, rows, workspace, workspace_bytes, stream);
+  return ppo_grad_call(ctx, "pf_ppo_grad", a, nullptr, rows, kNoIndex, workspace, workspace_bytes, stream);
 }
 int pf_ppo_grad_opt(pf_ctx* ctx, const pf_ppo_grad_args* a, const pf_ppo_options* options, int64_t rows, void* workspace, size_t workspace_bytes, void* stream) {
-  return ppo_grad_call(ctx, "pf_ppo_grad_opt", a, options, rows, workspace, workspace_bytes, stream);
+  return ppo_grad_call(ctx, "pf_ppo_grad_opt", a, options, rows, kNoIndex, workspace, workspace_bytes, stream);
 }
 int pf_ppo_grad_rows(pf_ctx* ctx, const pf_ppo_grad_args* a, const pf_ppo_options* options, const int32_t* row_index, int64_t m, int64_t rows_total, void* workspace,
                      size_t workspace_bytes, void* stream) {
   static const char* who = "pf_ppo_grad_rows";
   // (what the call adds comes first and needs nothing else: m and rows_total decide every extent below)
-  if (m < 1) return arg_fail(ctx, who, "m must be >= 1");
-  if (m > (int64_t)INT32_MAX - pf::kActRows) return arg_fail(ctx, who, "m must be below 2^31 - 64 (the kernels index slots with 32 bits)");
-  if (rows_total < 1) return arg_fail(ctx, who, "rows_total must be >= 1");
-  if (rows_total > (int64_t)INT32_MAX - pf::kActRows) return arg_fail(ctx, who, "rows_total must be below 2^31 - 64 (row_index holds 32-bit row numbers)");
+  if (int rc = rows_check(ctx, who, m, "m", "the kernels index slots with 32 bits")) return rc;
+  if (int rc = rows_check(ctx, who, rows_total, "rows_total", "row_index holds 32-bit row numbers")) return rc;
   if (!row_index) return arg_fail(ctx, who, "row_index is required");
-  return ppo_grad_call(ctx, who, a, options, m, workspace, workspace_bytes, stream, true, row_index, rows_total);
+  return ppo_grad_call(ctx, who, a, options, m, ppo_rows{row_index, rows_total}, workspace, workspace_bytes, stream);
 }
 size_t pf_adam_workspace_bytes(int64_t total_numel) {
   if (total_numel < 1 || total_numel > (int64_t)INT32_MAX) return 0;

@@ -272,6 +272,13 @@ class TrainOps:
         return a
 
     # ------------------------------------------------------------------ the loss
+    def _ppo_tensors(self, table):
+        """What ppo_loss and ppo_grad ask of the tensors they read, a table of (name, tensor, admitted shapes, dtypes) in the order
+        of the refusals: every one is required, but for `valid`."""
+        for name, t, shapes, dtypes in table:
+            if name != "valid" or t is not None:
+                K.tensor(self.device, t, name, shapes, dtypes, required="{name} is required: a tensor of shape {shape}")
+
     @staticmethod
     def _ppo_coefficients(clip, vf_coef, ent_coef, normalize_advantage):
         """What ppo_loss and ppo_grad ask of the loss's coefficients."""
@@ -338,11 +345,9 @@ class TrainOps:
         if M < 1:
             raise ValueError(f"mean must hold at least one row, got shape {tuple(mean.shape)}")
         f32, rows, full = (torch.float32,), (lead, lead + (1,)), (tuple(mean.shape),)  # (this call names its dtypes as torch spells them)
-        for name, x, shapes, dtypes in (("mean", mean, full, f32), ("actions", actions, full, f32), ("log_std", log_std, ((A,),), f32),
-                                        ("value", value, rows, f32), ("logp_old", logp_old, rows, f32), ("advantages", advantages, rows, f32),
-                                        ("returns", returns, rows, f32), ("valid", valid, rows, K.FLAGS)):
-            if name != "valid" or x is not None:
-                K.tensor(self.device, x, name, shapes, dtypes, required="{name} is required: a tensor of shape {shape}")
+        self._ppo_tensors((("mean", mean, full, f32), ("actions", actions, full, f32), ("log_std", log_std, ((A,),), f32), ("value", value, rows, f32),
+                           ("logp_old", logp_old, rows, f32), ("advantages", advantages, rows, f32), ("returns", returns, rows, f32),
+                           ("valid", valid, rows, K.FLAGS)))
         self._ppo_coefficients(clip, vf_coef, ent_coef, normalize_advantage)
         options = self._ppo_options(A, rows, clip_vf, values_old, action_bounds, bounds_coef)
         o = self._lazy("_ppo_out", lambda: dict(M=0, A=0, stats=torch.zeros(16, dtype=torch.float64, device=self.device), calls=0))
@@ -355,10 +360,7 @@ class TrainOps:
         a.mean, a.log_std, a.actions, a.logp_old = _ptr(mean), _ptr(log_std), _ptr(actions), _ptr(logp_old)
         a.advantages, a.returns, a.value, a.valid = _ptr(advantages), _ptr(returns), _ptr(value), _ptr(valid)
         a.grad_mean, a.grad_value, a.grad_log_std, a.stats = _ptr(o["grad_mean"]), _ptr(o["grad_value"]), _ptr(o["grad_log_std"]), _ptr(o["stats"])
-        if options is None:
-            self._launch(self.lib.pf_ppo_loss, C.byref(a), M, A)
-        else:
-            self._launch(self.lib.pf_ppo_loss_opt, C.byref(a), C.byref(options), M, A)
+        self._launch(*((self.lib.pf_ppo_loss, C.byref(a)) if options is None else (self.lib.pf_ppo_loss_opt, C.byref(a), C.byref(options))), M, A)
         return o["grad_mean"], o["grad_value"], o["grad_log_std"], o["stats"]
 
     # ------------------------------------------------------------------ the networks
@@ -417,6 +419,15 @@ class TrainOps:
         self._launch(self.lib.pf_mlp_forward, C.byref(q), _ptr(x), rows, _ptr(out))
         return out
 
+    def _grad_tensors(self, dims, gw, gb):
+        """[(grad_weight, grad_bias), ...] for layers of the shapes `dims` [(out, in), ...], made here, their addresses written into
+        the pointer arrays gw and gb (mlp_backward's own, or those of ppo_grad's argument block)."""
+        kw = dict(dtype=torch.float32, device=self.device)
+        grads = [(torch.empty(n_out, n_in, **kw), torch.empty(n_out, **kw)) for n_out, n_in in dims]
+        for l, (w, b) in enumerate(grads):
+            gw[l], gb[l] = w.data_ptr(), b.data_ptr()
+        return grads
+
     def mlp_backward(self, x, grad_out, layers, activation="tanh"):
         """pf_mlp_backward: [(grad_weight, grad_bias), ...] of the MLP `layers` on the rows of x [..., in_dim] under the
         output-gradients grad_out [rows, out_dim] (a [rows] tensor is accepted for out_dim 1). The hidden activations are computed
@@ -429,15 +440,12 @@ class TrainOps:
         key = (rows, tuple(dims))
         o = cache.get(key)
         if o is None:
-            kw = dict(dtype=torch.float32, device=self.device)
             nbytes = int(self.lib.pf_mlp_backward_workspace_bytes(C.byref(q), rows))
             if nbytes < 1:
                 raise L.PyFlytAmdError("pf_mlp_backward_workspace_bytes refused the network's shape")
-            grads = [(torch.empty(n_out, n_in, **kw), torch.empty(n_out, **kw)) for n_out, n_in in dims]
             gw, gb = (C.c_void_p * 3)(), (C.c_void_p * 3)()
-            for l, (w, b) in enumerate(grads):
-                gw[l], gb[l] = w.data_ptr(), b.data_ptr()
-            o = cache[key] = dict(grads=grads, gw=gw, gb=gb, bytes=nbytes, workspace=torch.empty((nbytes + 3) // 4, **kw))
+            o = cache[key] = dict(grads=self._grad_tensors(dims, gw, gb), gw=gw, gb=gb, bytes=nbytes,
+                                  workspace=torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=self.device))
         self._launch(self.lib.pf_mlp_backward, C.byref(q), _ptr(x), _ptr(grad_out), rows, o["gw"], o["gb"], _ptr(o["workspace"]), o["bytes"])
         return o["grads"]
 
@@ -456,42 +464,36 @@ class TrainOps:
         call is then the one on the m gathered rows, bit for bit, without a gathered copy; the advantages are normalised over those m
         rows; duplicates are allowed; a number outside the batch makes its slot an invalid row and is counted in stats[14]. int64 is
         refused, not converted. The engine's tensors are then those of m rows."""
-        index = rows
-        qa, rows, dims_a = self._mlp_block(x, actor, actor_activation)
+        index = rows  # (the keyword is the caller's word for it)
+        qa, total, dims_a = self._mlp_block(x, actor, actor_activation)
         qc, _, dims_c = self._mlp_block(x, critic, critic_activation)
         A = dims_a[-1][0]
         if dims_c[-1][0] != 1:
             raise ValueError(f"the critic's last layer must be 1 wide, got {dims_c[-1][0]}")
         lead = tuple(x.shape[:-1])
-        f32, per_row = (torch.float32,), (lead, lead + (1,), (rows,), (rows, 1))
-        for name, t, shapes, dtypes in (("log_std", log_std, ((A,),), f32), ("actions", actions, (lead + (A,), (rows, A)), f32),
-                                        ("logp_old", logp_old, per_row, f32), ("advantages", advantages, per_row, f32),
-                                        ("returns", returns, per_row, f32), ("valid", valid, per_row, K.FLAGS)):
-            if name != "valid" or t is not None:
-                K.tensor(self.device, t, name, shapes, dtypes, required="{name} is required: a tensor of shape {shape}")
+        f32, per_row = (torch.float32,), (lead, lead + (1,), (total,), (total, 1))
+        self._ppo_tensors((("log_std", log_std, ((A,),), f32), ("actions", actions, (lead + (A,), (total, A)), f32), ("logp_old", logp_old, per_row, f32),
+                           ("advantages", advantages, per_row, f32), ("returns", returns, per_row, f32), ("valid", valid, per_row, K.FLAGS)))
         self._ppo_coefficients(clip, vf_coef, ent_coef, normalize_advantage)
         options = self._ppo_options(A, per_row, clip_vf, values_old, action_bounds, bounds_coef)
-        total = rows
-        if index is not None:  # (the workspace and the cache are those of the m rows the call works on)
+        if index is None:
+            m = total
+        else:  # (the workspace and the cache are those of the m rows the call works on)
             K.ranked(index, "rows", "{name} must be a 1-D int32 tensor of row numbers", 1)
-            rows = int(index.shape[0])
-            if rows < 1:
+            m = int(index.shape[0])
+            if m < 1:
                 raise ValueError("rows must name at least one row, got an empty tensor")
-            K.tensor(self.device, index, "rows", (rows,), torch.int32)
+            K.tensor(self.device, index, "rows", (m,), torch.int32)
         cache = self._lazy("_ppo_grad", lambda: dict(stats=torch.zeros(16, dtype=torch.float64, device=self.device)))
-        key = (rows, tuple(dims_a), tuple(dims_c))
+        key = (m, tuple(dims_a), tuple(dims_c))
         o = cache.get(key)
         if o is None:
-            kw = dict(dtype=torch.float32, device=self.device)
-            nbytes = int(self.lib.pf_ppo_grad_workspace_bytes(C.byref(qa), C.byref(qc), rows))
+            nbytes = int(self.lib.pf_ppo_grad_workspace_bytes(C.byref(qa), C.byref(qc), m))
             if nbytes < 1:
                 raise L.PyFlytAmdError("pf_ppo_grad_workspace_bytes refused the networks' shapes")
             a = L.PfPpoGradArgs()
-            grads = [[(torch.empty(n_out, n_in, **kw), torch.empty(n_out, **kw)) for n_out, n_in in dims] for dims in (dims_a, dims_c)]
-            for gw, gb, net in ((a.actor_grad_w, a.actor_grad_b, grads[0]), (a.critic_grad_w, a.critic_grad_b, grads[1])):
-                for l, (w, b) in enumerate(net):
-                    gw[l], gb[l] = w.data_ptr(), b.data_ptr()
-            gls = torch.empty(A, **kw)
+            grads = [self._grad_tensors(dims_a, a.actor_grad_w, a.actor_grad_b), self._grad_tensors(dims_c, a.critic_grad_w, a.critic_grad_b)]
+            gls = torch.empty(A, dtype=torch.float32, device=self.device)
             a.grad_log_std, a.stats = gls.data_ptr(), cache["stats"].data_ptr()
             o = cache[key] = dict(args=a, grads=grads, grad_log_std=gls, bytes=nbytes, workspace=torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=self.device))
         a = o["args"]
@@ -499,13 +501,10 @@ class TrainOps:
         a.actor, a.critic = C.addressof(qa), C.addressof(qc)
         a.x, a.log_std, a.actions, a.logp_old = _ptr(x), _ptr(log_std), _ptr(actions), _ptr(logp_old)
         a.advantages, a.returns, a.valid = _ptr(advantages), _ptr(returns), _ptr(valid)
-        if index is not None:
-            self._launch(self.lib.pf_ppo_grad_rows, C.byref(a), None if options is None else C.byref(options), _ptr(index), rows, total, _ptr(o["workspace"]),
-                         o["bytes"])
-        elif options is None:
-            self._launch(self.lib.pf_ppo_grad, C.byref(a), rows, _ptr(o["workspace"]), o["bytes"])
-        else:
-            self._launch(self.lib.pf_ppo_grad_opt, C.byref(a), C.byref(options), rows, _ptr(o["workspace"]), o["bytes"])
+        # the call and what it takes between the argument block and the workspace
+        fn, between = ((self.lib.pf_ppo_grad_rows, (None if options is None else C.byref(options), _ptr(index), m, total)) if index is not None
+                       else (self.lib.pf_ppo_grad, (m,)) if options is None else (self.lib.pf_ppo_grad_opt, (C.byref(options), m)))
+        self._launch(fn, C.byref(a), *between, _ptr(o["workspace"]), o["bytes"])
         return o["grads"][0], o["grads"][1], o["grad_log_std"], cache["stats"]
 
     # ------------------------------------------------------------------ the optimiser

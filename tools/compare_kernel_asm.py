@@ -4,18 +4,19 @@ symbol name normalised, so that a kernel whose mangled name gained a template ar
 
     python -c "import __graft_entry__ as g; g.compile_hip('/tmp/parent.so', keep_asm='/tmp/parent.s')"    # in a checkout of the parent
     python -c "import __graft_entry__ as g; g.compile_hip('/tmp/this.so', keep_asm='/tmp/this.s')"        # in this tree
-    python tools/compare_kernel_asm.py /tmp/parent.s /tmp/this.s [regex of the kernels to compare]
+    python tools/compare_kernel_asm.py /tmp/parent.s /tmp/this.s [regex of the kernels to compare [regex of the new kernels]]
 
 Prints one line per kernel (verdict, lines compared, sha256 prefix of either text, name) and the first lines of a difference; exits 1
-if a kernel differs or is missing. profiles/ppo_grad_rows/nothing_moved.txt is its output."""
+if a kernel differs or is missing. The kernels to compare are those of the first file: by default the training kernels, "." for every
+kernel and device function. A commit that adds kernels names them with the second regex: they are on one side only, listed and not
+compared. The nothing_moved.txt files under profiles/ hold its output or its counts."""
 import difflib
 import hashlib
 import re
 import sys
 
-TRAINING = (r"ppo_main_kernel|ppo_finish_kernel|ppo_finish_opt_kernel|ppo_adv|PpoGradK|PpoGradOptK|adam_update_kernel|adam_norm_kernel|kl_control|"
-            r"mlp_backward_kernelINS_4MlpK|mlp_reduce|policy_act_kernel")
-NEW = r"PpoGradRowsK|_rows_kernel"  # the kernels of the commit under comparison: on one side only, listed and not compared
+TRAINING = (r"ppo_main_kernel|ppo_finish_kernel|ppo_finish_opt_kernel|ppo_finish_rows_kernel|ppo_adv|PpoGradK|PpoGradOptK|PpoGradRowsK|adam_update_kernel|"
+            r"adam_norm_kernel|kl_control|mlp_backward_kernelINS_4MlpK|mlp_reduce|policy_act_kernel")
 
 
 def functions(path):
@@ -53,9 +54,9 @@ def normalised(lines, name):
     return out
 
 
-def key(name):
-    """What a kernel is called on both sides; None for the kernels this comparison is not about (the new instantiations)."""
-    if re.search(NEW, name):
+def key(name, new=None):
+    """What a kernel is called on both sides; None for the kernels this comparison is not about (`new`: a regex of the new instantiations)."""
+    if new and re.search(new, name):
         return None
     m = re.search(r"ppo_main_kernelILi(\d)ELb(\d)E", name)
     if m:
@@ -68,10 +69,11 @@ def key(name):
 def main():
     old_path, new_path = sys.argv[1], sys.argv[2]
     pat = re.compile(sys.argv[3] if len(sys.argv) > 3 else TRAINING)
+    new = sys.argv[4] if len(sys.argv) > 4 else None
     a, am = functions(old_path)
     b, bm = functions(new_path)
-    A = {key(n): n for n in a if pat.search(n) and key(n)}
-    B = {key(n): n for n in b if pat.search(n) and key(n)}
+    A = {key(n, new): n for n in a if pat.search(n) and key(n, new)}
+    B = {key(n, new): n for n in b if pat.search(n) and key(n, new)}
     same = 0
     for k in sorted(A):
         if k not in B:
@@ -88,7 +90,7 @@ def main():
     print("%d of %d kernels are identical" % (same, len(A)))
     print("kernels only in the second file:")
     for n in sorted(set(b) - set(a)):
-        if key(n) is None:
+        if pat.search(n) and key(n, new) not in A:  # (the named new ones, and any other that has no former self)
             print("  ", n)
     return 0 if same == len(A) else 1
 
