@@ -873,6 +873,95 @@ int pf_ppo_grad_rows(pf_ctx* ctx, const pf_ppo_grad_args* a, const pf_ppo_option
                      const int32_t* row_index /* device, [m] */, int64_t m, int64_t rows_total,
                      void* workspace, size_t workspace_bytes, void* stream);
 
+/* SHARDED PPO: the gradient of ONE batch from shards of it that live on several devices, one context (and stream) per device. Adding
+ * up the outputs of pf_ppo_grad_rows on the shards is wrong: each call normalises the advantages over its own rows and weights its
+ * rows by 1 / (its own valid count). Here c, w = 1 / c, mu and sigma come from ALL shards and the raw sums are combined before the
+ * finish formulas run, so the result is the joint batch's. The order of a step:
+ *     per shard:  pf_ppo_adv_sums                      -> 4 doubles          (copied to the combining device by the caller)
+ *     once:       pf_adv_sums_add                      -> the global block   (copied back to every shard's device)
+ *     per shard:  pf_ppo_grad_shard                    -> the shard's share of the gradients, its block of raw totals
+ *     once:       pf_ppo_shard_combine                 -> the gradients, grad_log_std and stats of the joint batch
+ * The library makes no copy between devices and uses no collective: the caller moves 4 doubles, PF_PPO_SHARD_WORDS doubles and one
+ * flat gradient buffer per shard. Any context. Every call is enqueued on `stream`: no host synchronisation, no allocation, no
+ * copy, no atomics -- capturable in a HIP graph; the same inputs give the same bits on any stream and at every repetition. (Added
+ * without a new PF_ABI_VERSION: new functions and a new block, every existing struct as it was.)
+ *   - pf_ppo_adv_sums. sums[4], device, double: 0 the valid count c of the m rows (row_index NULL: rows 0..m-1 of the batch, and
+ *     rows_total is ignored) or of the m slots of row_index into a batch of rows_total rows; 1 sum A; 2 sum A^2, each square and every
+ *     sum in double about 0; 3 the slots whose index lay outside [0, rows_total) (0 without row_index). These are the totals that
+ *     pf_ppo_grad / pf_ppo_grad_rows form from the same rows in the same order before they divide: mu = sums[1] / c,
+ *     sigma = sqrt(max(sums[2] / c - mu^2, 0)). Three launches into the context's advantage block: a call must not overlap another
+ *     pf_ppo_* call on the same context on a different stream. ERRORS (PF_ERR_ARG, the argument named): m < 1 or m >= 2^31 - 64
+ *     (first, before the context is looked at); a NULL ctx, advantages or sums; with row_index, rows_total < 1 or >= 2^31 - 64;
+ *     sums overlapping an input.
+ *   - pf_adv_sums_add. dst[4] = src[0] + src[1] + ... + src[n_src - 1], element by element, in double, in that order. n_src in
+ *     1..PF_PPO_MAX_SHARDS; `src` is a HOST array of device pointers. ERRORS: n_src out of range (first); a NULL ctx, dst, src or
+ *     src[g]; dst overlapping a src[g].
+ *   - pf_ppo_grad_shard is pf_ppo_grad_opt (row_index NULL: the shard is rows 0..m-1 of a's tensors) or pf_ppo_grad_rows (the shard is
+ *     the m slots of row_index) with three differences:
+ *       (a) c, w32 = float32(1 / c), mu32 and inv32, which every row's float32 sequence applies, come from adv_sums[0..2] -- the
+ *           sums of ALL shards -- by the formulas above. The shard's own advantage pass still runs, to count its valid rows and its
+ *           out-of-range slots.
+ *       (b) a->stats and a->grad_log_std must be NULL: they are outputs of the joint batch. In their place shard_block
+ *           [PF_PPO_SHARD_WORDS], device, double, receives the raw totals the finish formulas read, over this shard's valid rows:
+ *               0 sum min(u, v)      1 sum (V - R)^2     2 sum (r - 1) - d    3 rows with |r - 1| > clip
+ *               4 sum R              5 sum R^2           6 sum (V - R)        7 min r (+inf: no valid row)   8 max r (-inf)
+ *               9..16 the sums behind grad_log_std[0..7], without the -ent_coef (0 from A on)
+ *               17 sum of the chosen squared value error (value clipping)   18 rows with |V - V_old| > clip_vf   19 sum b (bounds)
+ *               20 this shard's valid count    21 its out-of-range slots    22, 23 0
+ *           Words 17-19 are 0 in a call without options (an option that is off leaves a sum nobody reads). Words 0-19 have the bits
+ *           of the totals pf_ppo_grad_rows forms on the same rows.
+ *       (c) the weight and bias gradients written are this shard's SHARE of the joint gradient: already weighted by the global w32,
+ *           to be added to the other shards', not averaged.
+ *     The workspace (pf_ppo_grad_workspace_bytes(actor, critic, m)), the overlap checks and the refusals are pf_ppo_grad_rows's, with
+ *     row_index allowed to be NULL (rows_total is then not read); in addition: a non-NULL a->stats or a->grad_log_std; a NULL
+ *     adv_sums or shard_block; either overlapping anything. Eight launches. A shard without a valid row is fine: zero gradients.
+ *   - pf_ppo_shard_combine. blocks[g], grads[g]: shard g's block and ONE flat contiguous buffer of numel floats -- all gradient
+ *     tensors of both networks in a layout the caller chooses and gives pf_ppo_grad_shard views into; adv_sums: the global block.
+ *       grad_out[i] = float32(grads[0][i] + grads[1][i] + ... in double, g ascending), i < numel.
+ *       Every raw total is the sum of the shards' words in ascending shard order, in double; words 7 / 8 the min / max. stats[16]
+ *       and grad_log_std[width] are what pf_ppo_grad_rows' finish formulas make of those totals, c, mu and sigma from adv_sums:
+ *       slot 0 the global c, slots 7 / 8 mu and sigma, slot 14 the sum of the shards' out-of-range counts. With ONE shard every
+ *       output has the bits of pf_ppo_grad_rows (pf_ppo_grad_opt) on that shard's rows.
+ *     vclip / bnd: 0 / 1, whether the shards ran with value clipping (slots 3 and 12 then come from words 17 and 18) / with the
+ *     bounds loss (slot 13 from word 19, and the loss gains bounds_coef times it).
+ *     Two launches. ERRORS: n_shards outside 1..PF_PPO_MAX_SHARDS (first); a NULL ctx, argument block, blocks[g] or grads[g] with
+ *     g < n_shards, adv_sums, grad_out, log_std, grad_log_std or stats; numel < 1; width outside 1..8; vf_coef, ent_coef or
+ *     bounds_coef negative or not finite (pf_ppo_loss's checks); vclip or bnd other than 0 / 1; an output overlapping an input or
+ *     another output.
+ *   - pf_moments_merge, for the running normalisers of pf_traj_stats on sharded envs. dst, src[g]: device blocks of 1 + 2 D doubles
+ *     (count, mean[D], M2[D]), pf_traj_stats's obs_moments (D = pf_obs_dim) and ret_moments (D = 1). dst = dst merged with src[0],
+ *     ..., src[n_src - 1] in that order by the pairwise update pf_traj_stats itself uses (Chan et al.): n = na + nb, d = mean_b -
+ *     mean_a, mean = mean_a + d nb / n, M2 = M2_a + M2_b + d^2 na nb / n. A block with count 0 merges as nothing; into an empty
+ *     dst a block is copied, bit for bit. One launch. ERRORS: n_src outside 1..PF_PPO_MAX_SHARDS, D outside 1..128 (these first); a
+ *     NULL ctx, dst, src or src[g]; dst overlapping a src[g]. */
+#define PF_PPO_MAX_SHARDS 16
+#define PF_PPO_SHARD_WORDS 24
+typedef struct pf_ppo_shard_combine_args {
+  int32_t n_shards;                /* 1..PF_PPO_MAX_SHARDS */
+  int32_t width;                   /* A, the action width: 1..8 */
+  int64_t numel;                   /* floats of a flat gradient buffer, >= 1 */
+  float vf_coef, ent_coef;         /* >= 0, the shards' */
+  int32_t vclip, bnd;              /* 0 / 1: the shards' options */
+  float bounds_coef;               /* >= 0; read with bnd = 1 */
+  const double* blocks[PF_PPO_MAX_SHARDS];  /* device, [PF_PPO_SHARD_WORDS] each */
+  const double* adv_sums;          /* device, [4]: the sums of all shards */
+  const float*  grads[PF_PPO_MAX_SHARDS];   /* device, [numel] each */
+  float*  grad_out;                /* [numel] */
+  const float*  log_std;           /* [A] */
+  float*  grad_log_std;            /* [A] */
+  double* stats;                   /* [16], pf_ppo_loss's slots */
+} pf_ppo_shard_combine_args;
+size_t pf_sizeof_ppo_shard_combine(void);
+int pf_ppo_adv_sums(pf_ctx* ctx, const float* advantages, const uint8_t* valid /* NULL = all 1 */, const int32_t* row_index /* NULL = rows 0..m-1 */,
+                    int64_t m, int64_t rows_total, double* sums /* device, [4] */, void* stream);
+int pf_adv_sums_add(pf_ctx* ctx, double* dst /* device, [4] */, const double* const src[], int n_src, void* stream);
+int pf_ppo_grad_shard(pf_ctx* ctx, const pf_ppo_grad_args* a, const pf_ppo_options* options /* may be NULL */,
+                      const int32_t* row_index /* device, [m], or NULL */, int64_t m, int64_t rows_total,
+                      const double* adv_sums /* device, [4]: the sums of ALL shards */, double* shard_block /* device, [PF_PPO_SHARD_WORDS] */,
+                      void* workspace, size_t workspace_bytes, void* stream);
+int pf_ppo_shard_combine(pf_ctx* ctx, const pf_ppo_shard_combine_args* a, void* stream);
+int pf_moments_merge(pf_ctx* ctx, double* dst /* device, [1 + 2 D] */, const double* const src[], int n_src, int D, void* stream);
+
 /* What a PPO recipe decides from the measured KL, on the device: one launch of one thread behind the loss, no host synchronisation,
  * capturable. Any context. (Added without a new PF_ABI_VERSION: a new function and a new block.)
  *   - kl = stats[5] (approx_kl of pf_ppo_loss / pf_ppo_grad and their _opt forms).

@@ -12,6 +12,7 @@ from .policy import MLPPolicy
 from .ppo import minibatches, ppo_grad, ppo_loss, ppo_stats_dict
 from .nets import mlp
 from .optim import Adam
+from .sharded import Replicas, ppo_grad_sharded
 
-__all__ = ["_lib", "PyFlytAmdError", "build_params", "MLPPolicy", "RunningMoments", "ppo_loss", "ppo_grad", "ppo_stats_dict", "minibatches", "mlp", "Adam"]
+__all__ = ["_lib", "PyFlytAmdError", "build_params", "MLPPolicy", "RunningMoments", "ppo_loss", "ppo_grad", "ppo_stats_dict", "minibatches", "mlp", "Adam", "Replicas", "ppo_grad_sharded"]
 __version__ = "0.1.0"

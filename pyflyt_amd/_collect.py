@@ -40,7 +40,13 @@ class ClosedLoopEnv(EpisodeStats):
         k + 1 observation rows and, where `t` has them (SAME_STEP), of the final_obs rows; with `stats` pf_traj_stats before pf_gae.
         `episode_start` [n]: NEXT_STEP only, for both kernels. `valid` [k, n]: the mask of a trajectory that brings its own
         (pf_world_sync's: pf_traj_stats_masked, and what the batch returns); None = pf_gae's. `outcomes`: the closed loop ran with
-        them, and the batch gains outcome [k, n] uint8 and outcome_counts [G, 16] int64."""
+        them, and the batch gains outcome [k, n] uint8 and outcome_counts [G, 16] int64.
+        Two halves, cut behind pf_traj_stats: a sharded env (gym_envs/sharded.py) merges the shards' running moments between them."""
+        head = self._collect_head(t, value_fn, gamma, stats, episode_start, valid, outcomes)
+        return self._collect_tail(t, head, policy, gamma, lam, stats and normalize_reward, infos, episode_start, valid)
+
+    def _collect_head(self, t, value_fn, gamma, stats, episode_start, valid, outcomes):
+        """_collect_batch up to and including pf_traj_stats: (values, final_values, the batch's extra entries so far)."""
         eng = self.engine
 
         def value(rows, what):
@@ -54,16 +60,23 @@ class ClosedLoopEnv(EpisodeStats):
         with torch.no_grad():
             values = value(t["obs_all"], "observations")
             final_values = value(t["final_obs"], "final observations") if t["final_obs"] is not None else None
-        has_std = policy.log_std is not None
-        extra, reward = {}, t["reward"]
+        extra = {}
         if outcomes:
             extra = dict(outcome=t["outcome"], outcome_counts=t["outcome_counts"])
         if stats:
             ep_ret, ep_len, summary = eng.traj_stats(t["reward"], t["terminated"], t["truncated"], gamma=gamma, episode_start=episode_start,
                                                      obs=t["obs_all"][:-1], valid=valid)
             extra.update(episode_return=ep_ret, episode_length=ep_len, episode_summary=summary)
-            if normalize_reward:
-                reward = extra["reward_scaled"] = t["reward"] / (self.ret_rms.var + 1e-8).sqrt()
+        return values, final_values, extra
+
+    def _collect_tail(self, t, head, policy, gamma, lam, normalize_reward, infos, episode_start, valid):
+        """_collect_batch behind pf_traj_stats: the reward scaled by ret_rms as it stands now, pf_gae, the result dict."""
+        eng = self.engine
+        values, final_values, extra = head
+        has_std = policy.log_std is not None
+        reward = t["reward"]
+        if normalize_reward:
+            reward = extra["reward_scaled"] = t["reward"] / (self.ret_rms.var + 1e-8).sqrt()
         adv, ret, logp, gae_valid = eng.gae(reward, t["terminated"], t["truncated"], values, gamma=gamma, lam=lam, final_values=final_values,
                                             episode_start=episode_start, actions=t["actions"] if has_std else None,
                                             mean=t["mean"] if has_std else None, log_std=policy.log_std if has_std else None)

@@ -85,6 +85,7 @@ PfPpoGradArgs = _STRUCTS["pf_ppo_grad_args"]
 PfPpoOptions, PfKlControl = _STRUCTS["pf_ppo_options"], _STRUCTS["pf_kl_control_args"]
 PfOutcome, PF_OUTCOME_SLOTS, PF_OUTCOME_MAX_GROUPS = _STRUCTS["pf_outcome_args"], _DEFINES["PF_OUTCOME_SLOTS"], _DEFINES["PF_OUTCOME_MAX_GROUPS"]
 PF_POLICY_POOL_MAX = _DEFINES["PF_POLICY_POOL_MAX"]
+PfPpoShardCombine, PF_PPO_MAX_SHARDS, PF_PPO_SHARD_WORDS = _STRUCTS["pf_ppo_shard_combine_args"], _DEFINES["PF_PPO_MAX_SHARDS"], _DEFINES["PF_PPO_SHARD_WORDS"]
 # pf_episode_outcomes' slots by name (include/pyflyt_amd.h): 0-9 per agent, 10-13 per world
 OUTCOME_SLOT_NAMES = ("episodes", "terminated", "truncated", "collision", "out_of_bounds", "complete", "dead", "nonfinite", "second_word_sum", "clean",
                       "worlds", "team0_wins", "team1_wins", "draws")
@@ -176,6 +177,13 @@ def lib():
     L.pf_ppo_grad_opt.argtypes = [C.c_void_p, C.POINTER(PfPpoGradArgs), C.POINTER(PfPpoOptions), C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]
     L.pf_ppo_grad_rows.argtypes = [C.c_void_p, C.POINTER(PfPpoGradArgs), C.POINTER(PfPpoOptions), C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t,
                                    C.c_void_p]
+    L.pf_sizeof_ppo_shard_combine.restype = C.c_size_t
+    L.pf_ppo_adv_sums.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
+    L.pf_adv_sums_add.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_void_p]
+    L.pf_moments_merge.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_void_p]
+    L.pf_ppo_grad_shard.argtypes = [C.c_void_p, C.POINTER(PfPpoGradArgs), C.POINTER(PfPpoOptions), C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_size_t, C.c_void_p]
+    L.pf_ppo_shard_combine.argtypes = [C.c_void_p, C.POINTER(PfPpoShardCombine), C.c_void_p]
     L.pf_sizeof_kl_control.restype = C.c_size_t
     L.pf_kl_control.argtypes = [C.c_void_p, C.POINTER(PfKlControl), C.c_void_p]
     L.pf_adam_step_gated.argtypes = [C.c_void_p, C.POINTER(PfAdam), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
@@ -190,7 +198,8 @@ def lib():
             or L.pf_sizeof_ppo_loss() != C.sizeof(PfPpoLoss) or L.pf_sizeof_mlp() != C.sizeof(PfMlp) or L.pf_sizeof_adam() != C.sizeof(PfAdam) \
             or L.pf_sizeof_world_sync() != C.sizeof(PfWorldSync) or L.pf_sizeof_ppo_grad() != C.sizeof(PfPpoGradArgs) \
             or L.pf_sizeof_traj_stats_masked() != C.sizeof(PfTrajStatsMasked) or L.pf_sizeof_outcome() != C.sizeof(PfOutcome) \
-            or L.pf_sizeof_ppo_options() != C.sizeof(PfPpoOptions) or L.pf_sizeof_kl_control() != C.sizeof(PfKlControl):
+            or L.pf_sizeof_ppo_options() != C.sizeof(PfPpoOptions) or L.pf_sizeof_kl_control() != C.sizeof(PfKlControl) \
+            or L.pf_sizeof_ppo_shard_combine() != C.sizeof(PfPpoShardCombine):
         raise PyFlytAmdError("struct layout mismatch between pyflyt_amd/_lib.py and include/pyflyt_amd.h")
     if L.pf_abi_version() != PF_ABI_VERSION:
         raise PyFlytAmdError("ABI version mismatch between pyflyt_amd/_lib.py and libpyflyt_amd.so")

@@ -1,5 +1,5 @@
 // abi_train.hpp -- the C ABI's training side: pf_policy_act, pf_gae, pf_traj_stats / pf_traj_stats_masked, pf_ppo_loss, pf_mlp_forward / pf_mlp_backward, pf_ppo_grad (and pf_ppo_grad_rows),
-// pf_adam_step, pf_world_sync and pf_episode_outcomes, each behind the checks and launches it shares with another. Host code.
+// the sharded calls (pf_ppo_adv_sums, pf_ppo_grad_shard, pf_ppo_shard_combine, pf_adv_sums_add, pf_moments_merge), pf_adam_step, pf_world_sync and pf_episode_outcomes, each behind the checks and launches it shares with another. Host code.
 #pragma once
 #include <cmath>
 #include <type_traits>
@@ -12,6 +12,7 @@
 #include "policy_act.hpp"
 #include "mlp.hpp"
 #include "ppo_grad.hpp"
+#include "ppo_shard.hpp"
 #include "adam.hpp"
 #include "kl_control.hpp"
 #include "world_sync.hpp"
@@ -39,8 +40,14 @@ struct ppo_rows {
   int64_t rows_total;
 };
 constexpr ppo_rows kNoIndex{nullptr, 0};
-// the moments over `rows` rows, or over the `rows` slots of the index list ix
-static ppo_adv launch_ppo_adv(pf_ctx* ctx, const float* advantages, const uint8_t* valid, size_t rows, const ppo_rows& ix, hipStream_t s) {
+// pf_ppo_grad_shard's two additions: the advantage sums of ALL shards, and the shard's block of raw totals; adv_sums null = any other call
+struct ppo_shard {
+  const double* adv_sums;
+  double* block;
+};
+constexpr ppo_shard kNoShard{nullptr, nullptr};
+// the advantage pass over `rows` rows, or over the `rows` slots of the index list ix: its rows of partials in the context's block, nothing finished
+static ppo_adv launch_ppo_adv_part(pf_ctx* ctx, const float* advantages, const uint8_t* valid, size_t rows, const ppo_rows& ix, hipStream_t s) {
   double* adv_part = ctx->ppo_scratch + pf::kPpoAdvOffset;
   // (no valid: the byte loads read the advantages' first M bytes and the mask drops them)
   const ppo_adv r{valid ? valid : reinterpret_cast<const uint8_t*>(advantages), valid ? 0xFFu : 0u, ctx->ppo_scratch + pf::kPpoFinOffset};
@@ -49,7 +56,12 @@ static ppo_adv launch_ppo_adv(pf_ctx* ctx, const float* advantages, const uint8_
     hipLaunchKernelGGL(pf::ppo_adv_rows_kernel, dim3(grid), dim3(pf::kPpoBlock), 0, s, advantages, r.vbytes, r.vmask, ix.index, rows, (uint32_t)ix.rows_total, adv_part);
   else
     hipLaunchKernelGGL(pf::ppo_adv_kernel, dim3(grid), dim3(pf::kPpoBlock), 0, s, advantages, r.vbytes, r.vmask, rows, adv_part);
-  hipLaunchKernelGGL(pf::ppo_adv_finish_kernel, dim3(1), dim3(pf::kPpoBlock), 0, s, adv_part, (int)grid, r.fin);
+  return r;
+}
+// the moments over `rows` rows, or over the `rows` slots of the index list ix
+static ppo_adv launch_ppo_adv(pf_ctx* ctx, const float* advantages, const uint8_t* valid, size_t rows, const ppo_rows& ix, hipStream_t s) {
+  const ppo_adv r = launch_ppo_adv_part(ctx, advantages, valid, rows, ix, s);
+  hipLaunchKernelGGL(pf::ppo_adv_finish_kernel, dim3(1), dim3(pf::kPpoBlock), 0, s, (const double*)(ctx->ppo_scratch + pf::kPpoAdvOffset), (int)pf::ppo_grid(rows), r.fin);
   return r;
 }
 // What pf_ppo_loss and pf_ppo_grad launch last: `kernel`, one of the finish kernels, over n_blocks rows of partials. `a`: either call's
@@ -108,20 +120,25 @@ static void launch_mlp_reduce(const pf_mlp* q, float* const* gw, float* const* g
 }
 // The seven launches of a gradient call on `rows` rows, or slots of ix: the advantage pass and its finish, the actor's head and the critic's,
 // a reduction for each, the finish. OPT: the heads and the finish with the options KO; IDX: all of them through the index list (DESIGN.md
-// section 31 has the table). gw / gb: either network's gradient outputs.
+// section 31 has the table). gw / gb: either network's gradient outputs. sh (pf_ppo_grad_shard): the advantage block comes
+// from sh.adv_sums behind the shard's own pass, and the last launch leaves the raw totals in sh.block.
 template <bool OPT, bool IDX>
 static void launch_ppo_grad(pf_ctx* ctx, const pf_ppo_grad_args* a, float* const* const (&gw)[2], float* const* const (&gb)[2], const pf::PpoOptK& KO,
-                            const ppo_rows& ix, int64_t rows, void* workspace, hipStream_t s) {
+                            const ppo_rows& ix, const ppo_shard& sh, int64_t rows, void* workspace, hipStream_t s) {
   const pf_mlp* nets[2] = {a->actor, a->critic};
   const int grid = pf::mlp_grid(rows), A = a->actor->out_dim;
   double* stat_part = (double*)workspace;
   float* const part0 = (float*)((char*)workspace + pf::ppo_grad_stat_bytes(grid));
   float* const part[2] = {part0, part0 + (size_t)grid * (size_t)pf::mlp_param_count(*a->actor, nullptr)};
-  const ppo_adv adv = launch_ppo_adv(ctx, a->advantages, a->valid, (size_t)rows, ix, s);
+  const ppo_adv adv = sh.adv_sums ? launch_ppo_adv_part(ctx, a->advantages, a->valid, (size_t)rows, ix, s) : launch_ppo_adv(ctx, a->advantages, a->valid, (size_t)rows, ix, s);
+  if (sh.adv_sums) hipLaunchKernelGGL(pf::ppo_shard_fin_kernel, dim3(1), dim3(64), 0, s, sh.adv_sums, adv.fin);
   launch_ppo_grad_head<pf::kGradActor, OPT, IDX>(a, nets[0], part[0], rows, adv, stat_part, KO, ix, grid, s);
   launch_ppo_grad_head<pf::kGradCritic, OPT, IDX>(a, nets[1], part[1], rows, adv, stat_part, KO, ix, grid, s);
   for (int k = 0; k < 2; ++k) launch_mlp_reduce(nets[k], gw[k], gb[k], part[k], grid, s);
-  if constexpr (IDX)  // (with the options off, the finish without them: nothing of KO is read)
+  if (sh.adv_sums)
+    hipLaunchKernelGGL(pf::ppo_shard_finish_kernel, dim3(1), dim3(pf::kPpoBlock), 0, s, (const double*)stat_part, grid, OPT ? pf::kPpoStride : pf::kPpoQ,
+                       (const double*)(ctx->ppo_scratch + pf::kPpoAdvOffset), (int)pf::ppo_grid((size_t)rows), IDX ? 1 : 0, sh.block);
+  else if constexpr (IDX)  // (with the options off, the finish without them: nothing of KO is read)
     launch_ppo_finish(pf::ppo_finish_rows_kernel<OPT>, s, stat_part, grid, adv, a, A, OPT ? KO.vclip : 0, OPT ? KO.bnd : 0, OPT ? KO.bounds_coef : 0.0f,
                       (const double*)(ctx->ppo_scratch + pf::kPpoAdvOffset), (int)pf::ppo_grid((size_t)rows));
   else if constexpr (OPT)
@@ -421,9 +438,10 @@ size_t pf_ppo_grad_workspace_bytes(const pf_mlp* actor, const pf_mlp* critic, in
   const int grid = pf::mlp_grid(rows);
   return pf::ppo_grad_stat_bytes(grid) + sizeof(float) * (size_t)grid * ((size_t)pf::mlp_param_count(*actor, nullptr) + (size_t)pf::mlp_param_count(*critic, nullptr));
 }
-// pf_ppo_grad (o = NULL), pf_ppo_grad_opt and pf_ppo_grad_rows (ix.index: rows = m slots of it into a batch of ix.rows_total rows)
+// pf_ppo_grad (o = NULL), pf_ppo_grad_opt, pf_ppo_grad_rows (ix.index: rows = m slots of it into a batch of ix.rows_total rows) and
+// pf_ppo_grad_shard (`shard`: sh holds its two blocks, which stand where grad_log_std and stats stand in the other calls)
 static int ppo_grad_call(pf_ctx* ctx, const char* who, const pf_ppo_grad_args* a, const pf_ppo_options* o, int64_t rows, const ppo_rows& ix, void* workspace,
-                         size_t workspace_bytes, void* stream) {
+                         size_t workspace_bytes, void* stream, bool shard = false, const ppo_shard& sh = kNoShard) {
   if (!ctx) return arg_fail(ctx, who, "ctx is required");
   if (!a) return arg_fail(ctx, who, "the argument block is required");
   if (!a->actor) return arg_fail(ctx, who, "actor is required");
@@ -435,8 +453,11 @@ static int ppo_grad_call(pf_ctx* ctx, const char* who, const pf_ppo_grad_args* a
   if (!mlp_has_params(a->critic)) return arg_fail(ctx, who, "critic: w / b: every layer needs w and b");
   if (!ix.index)  // (pf_ppo_grad_rows has refused a bad m, under that name, before anything else)
     if (int rc = rows_check(ctx, who, rows, "rows", "the kernels index rows with 32 bits")) return rc;
+  if (shard && a->grad_log_std) return arg_fail(ctx, who, "grad_log_std must be NULL (an output of the joint batch: pf_ppo_shard_combine writes it)");
+  if (shard && a->stats) return arg_fail(ctx, who, "stats must be NULL (an output of the joint batch: pf_ppo_shard_combine writes it)");
   const arg_ptr required[] = {{"x", a->x}, {"log_std", a->log_std}, {"actions", a->actions}, {"logp_old", a->logp_old}, {"advantages", a->advantages},
-                              {"returns", a->returns}, {"grad_log_std", a->grad_log_std}, {"stats", a->stats}, {"workspace", workspace}, {nullptr, nullptr}};
+                              {"returns", a->returns}, {shard ? "adv_sums" : "grad_log_std", shard ? (const void*)sh.adv_sums : a->grad_log_std},
+                              {shard ? "shard_block" : "stats", shard ? (const void*)sh.block : a->stats}, {"workspace", workspace}, {nullptr, nullptr}};
   if (int rc = require_args(ctx, who, required)) return rc;
   static const char* const gn[2][2][3] = {{{"actor_grad_w[0]", "actor_grad_w[1]", "actor_grad_w[2]"}, {"actor_grad_b[0]", "actor_grad_b[1]", "actor_grad_b[2]"}},
                                           {{"critic_grad_w[0]", "critic_grad_w[1]", "critic_grad_w[2]"}, {"critic_grad_b[0]", "critic_grad_b[1]", "critic_grad_b[2]"}}};
@@ -456,7 +477,7 @@ static int ppo_grad_call(pf_ctx* ctx, const char* who, const pf_ppo_grad_args* a
   pf::PpoOptK KO;
   bool opt = false;
   if (int rc = ppo_options_check(ctx, who, o, (int)A, a->returns, &KO, &opt)) return rc;
-  arg_span spans[9 + 15];
+  arg_span spans[10 + 15];
   int ns = 0;
   if (ix.index) spans[ns++] = {"row_index", ix.index, sizeof(int32_t) * (size_t)rows};
   spans[ns++] = {"x", a->x, sizeof(float) * M * a->actor->in_dim};
@@ -467,15 +488,20 @@ static int ppo_grad_call(pf_ctx* ctx, const char* who, const pf_ppo_grad_args* a
   spans[ns++] = {"returns", a->returns, sizeof(float) * M};
   if (a->valid) spans[ns++] = {"valid", a->valid, M};
   if (o && o->values_old) spans[ns++] = {"values_old", o->values_old, sizeof(float) * M};
+  if (shard) spans[ns++] = {"adv_sums", sh.adv_sums, sizeof(double) * 4};
   const int n_read = ns;
   spans[ns++] = {"workspace", workspace, need};
-  spans[ns++] = {"grad_log_std", a->grad_log_std, sizeof(float) * A};
-  spans[ns++] = {"stats", a->stats, sizeof(double) * 16};
+  if (shard) {
+    spans[ns++] = {"shard_block", sh.block, sizeof(double) * PF_PPO_SHARD_WORDS};
+  } else {
+    spans[ns++] = {"grad_log_std", a->grad_log_std, sizeof(float) * A};
+    spans[ns++] = {"stats", a->stats, sizeof(double) * 16};
+  }
   for (int k = 0; k < 2; ++k) ns = append_grad_spans(spans, ns, nets[k], gn[k][0], gn[k][1], gw[k], gb[k]);
   if (const char* e = spans_overlap(spans, ns, buf, sizeof(buf), n_read)) return arg_fail(ctx, who, e);
   if (int rc = ensure_device(ctx)) return rc;
   const auto launches = ix.index ? (opt ? launch_ppo_grad<true, true> : launch_ppo_grad<false, true>) : (opt ? launch_ppo_grad<true, false> : launch_ppo_grad<false, false>);
-  launches(ctx, a, gw, gb, KO, ix, rows, workspace, (hipStream_t)stream);
+  launches(ctx, a, gw, gb, KO, ix, sh, rows, workspace, (hipStream_t)stream);
   return launched(ctx);
 }
 int pf_ppo_grad(pf_ctx* ctx, const pf_ppo_grad_args* a, int64_t rows, void* workspace, size_t workspace_bytes, void* stream) {
@@ -492,6 +518,138 @@ int pf_ppo_grad_rows(pf_ctx* ctx, const pf_ppo_grad_args* a, const pf_ppo_option
   if (int rc = rows_check(ctx, who, rows_total, "rows_total", "row_index holds 32-bit row numbers")) return rc;
   if (!row_index) return arg_fail(ctx, who, "row_index is required");
   return ppo_grad_call(ctx, who, a, options, m, ppo_rows{row_index, rows_total}, workspace, workspace_bytes, stream);
+}
+// ---- the sharded calls (include/pyflyt_amd.h: SHARDED PPO)
+size_t pf_sizeof_ppo_shard_combine(void) { return sizeof(pf_ppo_shard_combine_args); }
+int pf_ppo_adv_sums(pf_ctx* ctx, const float* advantages, const uint8_t* valid, const int32_t* row_index, int64_t m, int64_t rows_total, double* sums, void* stream) {
+  static const char* who = "pf_ppo_adv_sums";
+  if (int rc = rows_check(ctx, who, m, "m", "the kernels index slots with 32 bits")) return rc;
+  if (!ctx) return arg_fail(ctx, who, "ctx is required");
+  const arg_ptr required[] = {{"advantages", advantages}, {"sums", sums}, {nullptr, nullptr}};
+  if (int rc = require_args(ctx, who, required)) return rc;
+  if (row_index)
+    if (int rc = rows_check(ctx, who, rows_total, "rows_total", "row_index holds 32-bit row numbers")) return rc;
+  const size_t M = (size_t)(row_index ? rows_total : m);
+  arg_span spans[4];
+  int ns = 0;
+  if (row_index) spans[ns++] = {"row_index", row_index, sizeof(int32_t) * (size_t)m};
+  spans[ns++] = {"advantages", advantages, sizeof(float) * M};
+  if (valid) spans[ns++] = {"valid", valid, M};
+  const int n_read = ns;
+  spans[ns++] = {"sums", sums, sizeof(double) * 4};
+  char buf[128];
+  if (const char* e = spans_overlap(spans, ns, buf, sizeof(buf), n_read)) return arg_fail(ctx, who, e);
+  if (int rc = ensure_device(ctx)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  launch_ppo_adv_part(ctx, advantages, valid, (size_t)m, row_index ? ppo_rows{row_index, rows_total} : kNoIndex, s);
+  hipLaunchKernelGGL(pf::ppo_adv_sums_kernel, dim3(1), dim3(pf::kPpoBlock), 0, s, (const double*)(ctx->ppo_scratch + pf::kPpoAdvOffset), (int)pf::ppo_grid((size_t)m),
+                     row_index ? 1 : 0, sums);
+  return launched(ctx);
+}
+// what pf_adv_sums_add and pf_moments_merge check of their list of blocks of `words` doubles, and the kernels' copy of it
+static int shard_src_check(pf_ctx* ctx, const char* who, const double* dst, const double* const src[], int n_src, size_t words, pf::ShardSrcK* K) {
+  if (!ctx) return arg_fail(ctx, who, "ctx is required");
+  const arg_ptr required[] = {{"dst", dst}, {"src", src}, {nullptr, nullptr}};
+  if (int rc = require_args(ctx, who, required)) return rc;
+  char buf[128];
+  K->n_src = n_src;
+  for (int g = 0; g < PF_PPO_MAX_SHARDS; ++g) {
+    K->src[g] = g < n_src ? src[g] : nullptr;
+    if (g >= n_src) continue;
+    snprintf(buf, sizeof(buf), "src[%d]", g);
+    if (!src[g]) {
+      char what[64];
+      snprintf(what, sizeof(what), "%s is required", buf);
+      return arg_fail(ctx, who, what);
+    }
+    const arg_span spans[2] = {{buf, src[g], sizeof(double) * words}, {"dst", dst, sizeof(double) * words}};
+    char msg[128];
+    if (const char* e = spans_overlap(spans, 2, msg, sizeof(msg))) return arg_fail(ctx, who, e);
+  }
+  return PF_OK;
+}
+int pf_adv_sums_add(pf_ctx* ctx, double* dst, const double* const src[], int n_src, void* stream) {
+  static const char* who = "pf_adv_sums_add";
+  if (n_src < 1 || n_src > PF_PPO_MAX_SHARDS) return arg_fail(ctx, who, "n_src must be in 1..PF_PPO_MAX_SHARDS (16)");
+  pf::ShardSrcK K;
+  if (int rc = shard_src_check(ctx, who, dst, src, n_src, 4, &K)) return rc;
+  if (int rc = ensure_device(ctx)) return rc;
+  hipLaunchKernelGGL(pf::adv_sums_add_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, K, dst);
+  return launched(ctx);
+}
+int pf_moments_merge(pf_ctx* ctx, double* dst, const double* const src[], int n_src, int D, void* stream) {
+  static const char* who = "pf_moments_merge";
+  if (n_src < 1 || n_src > PF_PPO_MAX_SHARDS) return arg_fail(ctx, who, "n_src must be in 1..PF_PPO_MAX_SHARDS (16)");
+  if (D < 1 || D > pf::kTsMaxD) return arg_fail(ctx, who, "D must be in 1..128");
+  pf::ShardSrcK K;
+  if (int rc = shard_src_check(ctx, who, dst, src, n_src, 1 + 2 * (size_t)D, &K)) return rc;
+  if (int rc = ensure_device(ctx)) return rc;
+  hipLaunchKernelGGL(pf::moments_merge_kernel, dim3(1), dim3(pf::kTsMaxD), 0, (hipStream_t)stream, K, dst, D);
+  return launched(ctx);
+}
+int pf_ppo_grad_shard(pf_ctx* ctx, const pf_ppo_grad_args* a, const pf_ppo_options* options, const int32_t* row_index, int64_t m, int64_t rows_total,
+                      const double* adv_sums, double* shard_block, void* workspace, size_t workspace_bytes, void* stream) {
+  static const char* who = "pf_ppo_grad_shard";
+  if (int rc = rows_check(ctx, who, m, "m", "the kernels index slots with 32 bits")) return rc;
+  if (row_index)
+    if (int rc = rows_check(ctx, who, rows_total, "rows_total", "row_index holds 32-bit row numbers")) return rc;
+  return ppo_grad_call(ctx, who, a, options, m, row_index ? ppo_rows{row_index, rows_total} : kNoIndex, workspace, workspace_bytes, stream, true,
+                       ppo_shard{adv_sums, shard_block});
+}
+int pf_ppo_shard_combine(pf_ctx* ctx, const pf_ppo_shard_combine_args* a, void* stream) {
+  static const char* who = "pf_ppo_shard_combine";
+  if (a && (a->n_shards < 1 || a->n_shards > PF_PPO_MAX_SHARDS)) return arg_fail(ctx, who, "n_shards must be in 1..PF_PPO_MAX_SHARDS (16)");
+  if (!ctx) return arg_fail(ctx, who, "ctx is required");
+  if (!a) return arg_fail(ctx, who, "the argument block is required");
+  if (a->numel < 1) return arg_fail(ctx, who, "numel must be >= 1");
+  if (a->width < 1 || a->width > pf::kPpoMaxA) return arg_fail(ctx, who, "width must be in 1..8");
+  // (clip and normalize_advantage are the shards' business: what the rows made of them is in the totals)
+  if (int rc = ppo_coef_check(ctx, who, 1.0f, a->vf_coef, a->ent_coef, 0)) return rc;
+  if (!(a->bounds_coef >= 0.0f && a->bounds_coef < INFINITY)) return arg_fail(ctx, who, "bounds_coef must be finite and >= 0");
+  if ((a->vclip != 0 && a->vclip != 1) || (a->bnd != 0 && a->bnd != 1)) return arg_fail(ctx, who, "vclip and bnd must be 0 or 1");
+  const size_t A = (size_t)a->width, G = (size_t)a->n_shards;
+  arg_span spans[2 * PF_PPO_MAX_SHARDS + 5];
+  char names[2 * PF_PPO_MAX_SHARDS][16];
+  int ns = 0;
+  for (size_t g = 0; g < G; ++g) {
+    const void* const ptrs[2] = {a->blocks[g], a->grads[g]};
+    for (int k = 0; k < 2; ++k) {
+      snprintf(names[ns], sizeof(names[ns]), "%s[%d]", k ? "grads" : "blocks", (int)g);
+      const arg_ptr one[] = {{names[ns], ptrs[k]}, {nullptr, nullptr}};
+      if (int rc = require_args(ctx, who, one)) return rc;
+      spans[ns] = {names[ns], ptrs[k], k ? sizeof(float) * (size_t)a->numel : sizeof(double) * PF_PPO_SHARD_WORDS};
+      ++ns;
+    }
+  }
+  const arg_ptr required[] = {{"adv_sums", a->adv_sums}, {"grad_out", a->grad_out}, {"log_std", a->log_std}, {"grad_log_std", a->grad_log_std},
+                              {"stats", a->stats}, {nullptr, nullptr}};
+  if (int rc = require_args(ctx, who, required)) return rc;
+  spans[ns++] = {"adv_sums", a->adv_sums, sizeof(double) * 4};
+  spans[ns++] = {"log_std", a->log_std, sizeof(float) * A};
+  const int n_read = ns;
+  spans[ns++] = {"grad_out", a->grad_out, sizeof(float) * (size_t)a->numel};
+  spans[ns++] = {"grad_log_std", a->grad_log_std, sizeof(float) * A};
+  spans[ns++] = {"stats", a->stats, sizeof(double) * 16};
+  char buf[128];
+  if (const char* e = spans_overlap(spans, ns, buf, sizeof(buf), n_read)) return arg_fail(ctx, who, e);
+  if (int rc = ensure_device(ctx)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  pf::ShardSumK S;
+  pf::ShardCombineK K;
+  S.n_shards = K.n_shards = a->n_shards;
+  for (size_t g = 0; g < PF_PPO_MAX_SHARDS; ++g) {
+    S.grads[g] = g < G ? a->grads[g] : nullptr;
+    K.blocks[g] = g < G ? a->blocks[g] : nullptr;
+  }
+  S.out = a->grad_out;
+  K.width = a->width, K.vclip = a->vclip, K.bnd = a->bnd;
+  K.vf_coef = a->vf_coef, K.ent_coef = a->ent_coef, K.bounds_coef = a->bounds_coef;
+  K.adv_sums = a->adv_sums, K.log_std = a->log_std, K.grad_log_std = a->grad_log_std, K.stats = a->stats;
+  const size_t blocks = ((size_t)a->numel + pf::kShardSumBlock - 1) / pf::kShardSumBlock;
+  const unsigned grid = (unsigned)(blocks < (size_t)pf::kShardSumMaxGrid ? blocks : (size_t)pf::kShardSumMaxGrid);
+  hipLaunchKernelGGL(pf::ppo_shard_sum_kernel, dim3(grid), dim3(pf::kShardSumBlock), 0, s, S, (size_t)a->numel);
+  hipLaunchKernelGGL(pf::ppo_shard_combine_kernel, dim3(1), dim3(pf::kPpoBlock), 0, s, K);
+  return launched(ctx);
 }
 size_t pf_adam_workspace_bytes(int64_t total_numel) {
   if (total_numel < 1 || total_numel > (int64_t)INT32_MAX) return 0;

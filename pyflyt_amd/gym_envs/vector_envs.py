@@ -484,10 +484,15 @@ _REGISTRY = {
 }
 
 
-def make_vec(env_id: str, num_envs: int, **kwargs):
-    """The batched counterpart of `gymnasium.make_vec(id, num_envs=...)` for the supported ids."""
+def make_vec(env_id: str, num_envs: int, devices=None, **kwargs):
+    """The batched counterpart of `gymnasium.make_vec(id, num_envs=...)` for the supported ids. devices=[...]: the num_envs lanes cut
+    into one vector env per device, behind a ShardedVecEnv (gym_envs/sharded.py)."""
     if env_id not in _REGISTRY:
         raise KeyError(f"{env_id!r} is not on the batched hot path; available: {sorted(_REGISTRY)}")
+    if devices is not None:
+        from .sharded import ShardedVecEnv
+
+        return ShardedVecEnv(_REGISTRY[env_id], num_envs, devices, **kwargs)
     return _REGISTRY[env_id](num_envs, **kwargs)
 
 

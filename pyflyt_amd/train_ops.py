@@ -34,6 +34,7 @@ class TrainOps:
     _mlp_fwd = None   # {(rows, out_dim): mlp_forward()'s output}
     _mlp_bwd = None   # {(rows, layer shapes): mlp_backward()'s gradients, pointer arrays and workspace}
     _ppo_grad = None  # {(rows, both networks' layer shapes): ppo_grad()'s gradients, argument block and workspace}; "stats": its [16] block
+    _ppo_shard = None  # {(rows, both networks' layer shapes): ppo_grad_shard()'s flat gradients, block, argument block and workspace}; the sums' and the combine's outputs
     _adam = None      # {addresses: adam_step()'s filled argument block}, the 64 most recent
     _adam_ws = None   # {total elements: adam_step()'s workspace}
     _world_done = None  # [n] uint8: world_sync's latch as the world rollouts keep it (BatchEngine.world_done)
@@ -449,21 +450,10 @@ class TrainOps:
         self._launch(self.lib.pf_mlp_backward, C.byref(q), _ptr(x), _ptr(grad_out), rows, o["gw"], o["gb"], _ptr(o["workspace"]), o["bytes"])
         return o["grads"]
 
-    def ppo_grad(self, x, actor, critic, log_std, actions, logp_old, advantages, returns, valid=None, clip: float = 0.2, vf_coef: float = 0.5,
-                 ent_coef: float = 0.0, normalize_advantage: bool = True, actor_activation="tanh", critic_activation="tanh", clip_vf=None,
-                 action_bounds=None, bounds_coef: float = 0.0, values_old=None, rows=None):
-        """pf_ppo_grad: what mlp_forward(actor), mlp_forward(critic), ppo_loss, mlp_backward(actor), mlp_backward(critic) give on the
-        rows of x [..., in_dim], without the mean, value, grad_mean and grad_value tensors between them (include/pyflyt_amd.h has the
-        semantics). actor, critic: [(weight, bias), ...] as for mlp_forward, the critic one wide and on the same in_dim; actions
-        [..., A]; logp_old, advantages, returns [...] (a trailing axis of 1 is accepted); valid [...] bool / uint8 or None. Returns
-        (actor_grads, critic_grads, grad_log_std [A], stats [16] float64), the first two [(grad_weight, grad_bias), ...]: tensors the
-        engine owns, overwritten by the next call with the same rows and layer shapes (stats by every call); so is the workspace.
-        clip_vf with values_old [...], action_bounds with bounds_coef: ppo_loss's options (pf_ppo_grad_opt; with the defaults the call
-        is pf_ppo_grad).
-        rows: None, or a minibatch as a 1-D contiguous int32 tensor [m] of row numbers into the flattened batch (pf_ppo_grad_rows): the
-        call is then the one on the m gathered rows, bit for bit, without a gathered copy; the advantages are normalised over those m
-        rows; duplicates are allowed; a number outside the batch makes its slot an invalid row and is counted in stats[14]. int64 is
-        refused, not converted. The engine's tensors are then those of m rows."""
+    def _ppo_grad_inputs(self, x, actor, critic, log_std, actions, logp_old, advantages, returns, valid, clip, vf_coef, ent_coef, normalize_advantage,
+                         actor_activation, critic_activation, clip_vf, action_bounds, bounds_coef, values_old, rows):
+        """What ppo_grad and ppo_grad_shard check of their inputs, in the order of the refusals. Returns (actor block, critic block, the
+        two lists of layer shapes, A, the rows of x, the options block or None, the index list or None, m = the rows the call works on)."""
         index = rows  # (the keyword is the caller's word for it)
         qa, total, dims_a = self._mlp_block(x, actor, actor_activation)
         qc, _, dims_c = self._mlp_block(x, critic, critic_activation)
@@ -484,6 +474,26 @@ class TrainOps:
             if m < 1:
                 raise ValueError("rows must name at least one row, got an empty tensor")
             K.tensor(self.device, index, "rows", (m,), torch.int32)
+        return qa, qc, dims_a, dims_c, A, total, options, index, m
+
+    def ppo_grad(self, x, actor, critic, log_std, actions, logp_old, advantages, returns, valid=None, clip: float = 0.2, vf_coef: float = 0.5,
+                 ent_coef: float = 0.0, normalize_advantage: bool = True, actor_activation="tanh", critic_activation="tanh", clip_vf=None,
+                 action_bounds=None, bounds_coef: float = 0.0, values_old=None, rows=None):
+        """pf_ppo_grad: what mlp_forward(actor), mlp_forward(critic), ppo_loss, mlp_backward(actor), mlp_backward(critic) give on the
+        rows of x [..., in_dim], without the mean, value, grad_mean and grad_value tensors between them (include/pyflyt_amd.h has the
+        semantics). actor, critic: [(weight, bias), ...] as for mlp_forward, the critic one wide and on the same in_dim; actions
+        [..., A]; logp_old, advantages, returns [...] (a trailing axis of 1 is accepted); valid [...] bool / uint8 or None. Returns
+        (actor_grads, critic_grads, grad_log_std [A], stats [16] float64), the first two [(grad_weight, grad_bias), ...]: tensors the
+        engine owns, overwritten by the next call with the same rows and layer shapes (stats by every call); so is the workspace.
+        clip_vf with values_old [...], action_bounds with bounds_coef: ppo_loss's options (pf_ppo_grad_opt; with the defaults the call
+        is pf_ppo_grad).
+        rows: None, or a minibatch as a 1-D contiguous int32 tensor [m] of row numbers into the flattened batch (pf_ppo_grad_rows): the
+        call is then the one on the m gathered rows, bit for bit, without a gathered copy; the advantages are normalised over those m
+        rows; duplicates are allowed; a number outside the batch makes its slot an invalid row and is counted in stats[14]. int64 is
+        refused, not converted. The engine's tensors are then those of m rows."""
+        qa, qc, dims_a, dims_c, A, total, options, index, m = self._ppo_grad_inputs(
+            x, actor, critic, log_std, actions, logp_old, advantages, returns, valid, clip, vf_coef, ent_coef, normalize_advantage, actor_activation,
+            critic_activation, clip_vf, action_bounds, bounds_coef, values_old, rows)
         cache = self._lazy("_ppo_grad", lambda: dict(stats=torch.zeros(16, dtype=torch.float64, device=self.device)))
         key = (m, tuple(dims_a), tuple(dims_c))
         o = cache.get(key)
@@ -506,6 +516,165 @@ class TrainOps:
                        else (self.lib.pf_ppo_grad, (m,)) if options is None else (self.lib.pf_ppo_grad_opt, (C.byref(options), m)))
         self._launch(fn, C.byref(a), *between, _ptr(o["workspace"]), o["bytes"])
         return o["grads"][0], o["grads"][1], o["grad_log_std"], cache["stats"]
+
+    # ------------------------------------------------------------------ the sharded gradient (include/pyflyt_amd.h: SHARDED PPO)
+    def _flat_grads(self, dims_a, dims_c, flat, gw_a, gb_a, gw_c, gb_c):
+        """[(grad_weight, grad_bias), ...] of both networks as views into `flat` [numel] float32, the actor's layers and then the
+        critic's, each weight in front of its bias -- the layout ppo_shard_combine's callers share; the views' addresses go into
+        the four pointer arrays of a pf_ppo_grad_args block."""
+        views, at = [], 0
+        for dims, gw, gb in ((dims_a, gw_a, gb_a), (dims_c, gw_c, gb_c)):
+            net = []
+            for l, (n_out, n_in) in enumerate(dims):
+                w = flat[at:at + n_out * n_in].view(n_out, n_in)
+                b = flat[at + n_out * n_in:at + n_out * n_in + n_out]
+                at += n_out * n_in + n_out
+                gw[l], gb[l] = w.data_ptr(), b.data_ptr()
+                net.append((w, b))
+            views.append(net)
+        return views
+
+    @staticmethod
+    def grad_numel(dims_a, dims_c):
+        """The floats of a flat gradient buffer for networks of the layer shapes [(out, in), ...]."""
+        return sum(n_out * n_in + n_out for dims in (dims_a, dims_c) for n_out, n_in in dims)
+
+    def ppo_adv_sums(self, advantages, valid=None, rows=None, out=None):
+        """pf_ppo_adv_sums: [4] float64 (valid count, sum A, sum A^2, out-of-range slots) of this shard's rows -- what ppo_grad makes
+        c, mu and sigma of, undivided, so that the sums of several shards add up to the joint batch's. advantages [...] float32,
+        valid [...] bool / uint8 or None, flattened; rows: None or an int32 index list [m] as for ppo_grad. Returns `out`, or a
+        tensor the engine owns, overwritten by the next call."""
+        K.ranked(advantages, "advantages", "{name} must be a float32 tensor with at least one axis")
+        total = advantages.numel()
+        if total < 1:
+            raise ValueError(f"advantages must hold at least one row, got shape {tuple(advantages.shape)}")
+        K.tensor(self.device, advantages, "advantages", tuple(advantages.shape))
+        K.tensor(self.device, valid, "valid", tuple(advantages.shape), K.FLAGS)
+        m = total
+        if rows is not None:
+            K.ranked(rows, "rows", "{name} must be a 1-D int32 tensor of row numbers", 1)
+            m = int(rows.shape[0])
+            if m < 1:
+                raise ValueError("rows must name at least one row, got an empty tensor")
+            K.tensor(self.device, rows, "rows", (m,), torch.int32)
+        if out is None:
+            out = self._lazy("_ppo_shard", dict).setdefault("adv_sums", torch.zeros(4, dtype=torch.float64, device=self.device))
+        else:
+            K.tensor(self.device, out, "out", (4,), torch.float64)
+        self._launch(self.lib.pf_ppo_adv_sums, _ptr(advantages), _ptr(valid), _ptr(rows), m, total, _ptr(out))
+        return out
+
+    def _block_list(self, blocks, name, shape, dtype=torch.float64):
+        """A list of 1..PF_PPO_MAX_SHARDS tensors of one shape on this device as the (void* x 16) array the sharded calls take."""
+        if not isinstance(blocks, (list, tuple)) or not 1 <= len(blocks) <= L.PF_PPO_MAX_SHARDS:
+            raise ValueError(f"{name} must be a list of 1..{L.PF_PPO_MAX_SHARDS} tensors (PF_PPO_MAX_SHARDS), got "
+                             f"{len(blocks) if isinstance(blocks, (list, tuple)) else type(blocks).__name__}")
+        arr = (C.c_void_p * L.PF_PPO_MAX_SHARDS)()
+        for g, t in enumerate(blocks):
+            K.tensor(self.device, t, f"{name}[{g}]", shape, dtype, required="{name} must be a tensor of shape {shape}")
+            arr[g] = t.data_ptr()
+        return arr
+
+    def adv_sums_add(self, blocks, out=None):
+        """pf_adv_sums_add: the [4] float64 sum of the shards' ppo_adv_sums blocks (copies on this device), added in the list's
+        order: the global block every shard's ppo_grad_shard takes. Returns `out`, or a tensor the engine owns."""
+        arr = self._block_list(blocks, "blocks", (4,))
+        if out is None:
+            out = self._lazy("_ppo_shard", dict).setdefault("adv_total", torch.zeros(4, dtype=torch.float64, device=self.device))
+        else:
+            K.tensor(self.device, out, "out", (4,), torch.float64)
+        self._launch(self.lib.pf_adv_sums_add, _ptr(out), arr, len(blocks))
+        return out
+
+    def moments_merge(self, dst, blocks):
+        """pf_moments_merge: `dst` [1 + 2 D] float64 (count, mean[D], M2[D]) merged in place with the blocks of the same shape, in
+        the list's order, by traj_stats' own pairwise update; an empty block changes nothing, an empty dst takes a block's bits.
+        Returns dst."""
+        K.ranked(dst, "dst", "{name} must be a float64 tensor of shape (1 + 2 D,)", 1)
+        D = (int(dst.shape[0]) - 1) // 2
+        if dst.shape[0] != 1 + 2 * D or not 1 <= D <= 128:
+            raise ValueError(f"dst must hold 1 + 2 D doubles with D in 1..128, got {int(dst.shape[0])}")
+        K.tensor(self.device, dst, "dst", (1 + 2 * D,), torch.float64)
+        arr = self._block_list(blocks, "blocks", (1 + 2 * D,))
+        self._launch(self.lib.pf_moments_merge, _ptr(dst), arr, len(blocks), D)
+        return dst
+
+    def ppo_grad_shard(self, x, actor, critic, log_std, actions, logp_old, advantages, returns, adv_sums, valid=None, clip: float = 0.2,
+                       vf_coef: float = 0.5, ent_coef: float = 0.0, normalize_advantage: bool = True, actor_activation="tanh", critic_activation="tanh",
+                       clip_vf=None, action_bounds=None, bounds_coef: float = 0.0, values_old=None, rows=None):
+        """pf_ppo_grad_shard: ppo_grad on this shard's rows with c, mu and sigma of the JOINT batch, taken from adv_sums ([4] float64:
+        adv_sums_add's block over all shards, on this device). Returns (actor_grads, critic_grads, flat [numel] float32, block [24]
+        float64): the shard's share of the network gradients as views into `flat` (_flat_grads has the layout), and its block of
+        raw totals; ppo_shard_combine makes the joint gradients, grad_log_std and stats of the shards' flats and blocks. Tensors the
+        engine owns, overwritten by the next call with the same rows and layer shapes; so is the workspace."""
+        qa, qc, dims_a, dims_c, A, total, options, index, m = self._ppo_grad_inputs(
+            x, actor, critic, log_std, actions, logp_old, advantages, returns, valid, clip, vf_coef, ent_coef, normalize_advantage, actor_activation,
+            critic_activation, clip_vf, action_bounds, bounds_coef, values_old, rows)
+        K.tensor(self.device, adv_sums, "adv_sums", (4,), torch.float64, required="{name} is required: a tensor of shape {shape}")
+        cache = self._lazy("_ppo_shard", dict)
+        key = (m, tuple(dims_a), tuple(dims_c))
+        o = cache.get(key)
+        if o is None:
+            nbytes = int(self.lib.pf_ppo_grad_workspace_bytes(C.byref(qa), C.byref(qc), m))
+            if nbytes < 1:
+                raise L.PyFlytAmdError("pf_ppo_grad_workspace_bytes refused the networks' shapes")
+            a = L.PfPpoGradArgs()  # (grad_log_std and stats stay NULL: the combine's outputs)
+            flat = torch.empty(self.grad_numel(dims_a, dims_c), dtype=torch.float32, device=self.device)
+            grads = self._flat_grads(dims_a, dims_c, flat, a.actor_grad_w, a.actor_grad_b, a.critic_grad_w, a.critic_grad_b)
+            o = cache[key] = dict(args=a, grads=grads, flat=flat, block=torch.zeros(L.PF_PPO_SHARD_WORDS, dtype=torch.float64, device=self.device), bytes=nbytes,
+                                  workspace=torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=self.device))
+        a = o["args"]
+        a.clip, a.vf_coef, a.ent_coef, a.normalize_advantage = float(clip), float(vf_coef), float(ent_coef), int(normalize_advantage)
+        a.actor, a.critic = C.addressof(qa), C.addressof(qc)
+        a.x, a.log_std, a.actions, a.logp_old = _ptr(x), _ptr(log_std), _ptr(actions), _ptr(logp_old)
+        a.advantages, a.returns, a.valid = _ptr(advantages), _ptr(returns), _ptr(valid)
+        self._launch(self.lib.pf_ppo_grad_shard, C.byref(a), None if options is None else C.byref(options), _ptr(index), m, total, _ptr(adv_sums),
+                     _ptr(o["block"]), _ptr(o["workspace"]), o["bytes"])
+        return o["grads"][0], o["grads"][1], o["flat"], o["block"]
+
+    def ppo_shard_combine(self, blocks, adv_sums, flats, log_std, vf_coef: float = 0.5, ent_coef: float = 0.0, value_clip: bool = False,
+                          bounds_coef: float = 0.0, out=None):
+        """pf_ppo_shard_combine: the joint batch's gradients from the shards' ppo_grad_shard outputs, all on this device (copies of
+        the other devices'). blocks: the [24] float64 blocks; flats: the [numel] float32 flat gradients, one per shard in the same
+        order; adv_sums: the global [4] block; log_std [A]; vf_coef, ent_coef, bounds_coef: the shards'; value_clip: whether they
+        ran with clip_vf. Returns (grad [numel] float32 -- `out`, or a tensor the engine owns per numel --, grad_log_std [A],
+        stats [16] float64): the sums over the shards in the list's order, and what ppo_grad's finish makes of the summed totals."""
+        K.ranked(log_std, "log_std", "{name} must be a float32 tensor of shape (A,)", 1)
+        A = int(log_std.shape[0])
+        if not 1 <= A <= 8:
+            raise ValueError(f"log_std's length (the action width) must be in 1..8, got {A}")
+        K.tensor(self.device, log_std, "log_std", (A,))
+        K.tensor(self.device, adv_sums, "adv_sums", (4,), torch.float64, required="{name} is required: a tensor of shape {shape}")
+        a = L.PfPpoShardCombine()
+        a.blocks = self._block_list(blocks, "blocks", (L.PF_PPO_SHARD_WORDS,))
+        if not isinstance(flats, (list, tuple)) or len(flats) != len(blocks):
+            raise ValueError(f"flats must hold one flat gradient per block ({len(blocks)}), got {len(flats) if isinstance(flats, (list, tuple)) else type(flats).__name__}")
+        K.ranked(flats[0], "flats[0]", "{name} must be a 1-D float32 tensor", 1)
+        numel = int(flats[0].shape[0])
+        if numel < 1:
+            raise ValueError("flats[0] must hold at least one element")
+        a.grads = self._block_list(flats, "flats", (numel,), torch.float32)
+        for name, v in (("vf_coef", vf_coef), ("ent_coef", ent_coef), ("bounds_coef", bounds_coef)):
+            K.number(v, name)
+            K.non_negative(v, name)
+        K.boolean(value_clip, "value_clip")
+        cache = self._lazy("_ppo_shard", dict)
+        o = cache.get(("combine", numel, A))
+        if o is None:
+            o = cache[("combine", numel, A)] = dict(grad=torch.empty(numel, dtype=torch.float32, device=self.device),
+                                                    grad_log_std=torch.empty(A, dtype=torch.float32, device=self.device),
+                                                    stats=torch.zeros(16, dtype=torch.float64, device=self.device))
+        if out is None:
+            out = o["grad"]
+        else:
+            K.tensor(self.device, out, "out", (numel,))
+        a.n_shards, a.width, a.numel = len(blocks), A, numel
+        a.vf_coef, a.ent_coef, a.bounds_coef = float(vf_coef), float(ent_coef), float(bounds_coef)
+        a.vclip, a.bnd = int(value_clip), int(float(bounds_coef) > 0.0)
+        a.adv_sums, a.log_std = adv_sums.data_ptr(), log_std.data_ptr()
+        a.grad_out, a.grad_log_std, a.stats = out.data_ptr(), o["grad_log_std"].data_ptr(), o["stats"].data_ptr()
+        self._launch(self.lib.pf_ppo_shard_combine, C.byref(a))
+        return out, o["grad_log_std"], o["stats"]
 
     # ------------------------------------------------------------------ the optimiser
     def adam_step(self, params, grads, exp_avg, exp_avg_sq, state, *, lr=3e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
